@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: env-steps/s of the vectorised imitate env (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--envs 4096] [--scene humanoid3d_walk]
+    python bench.py --gpus N --steps K --warmup W [--envs 4096] [--scene humanoid3d_walk] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs (--dump-outputs) and prints the line.  `--full` adds
+everything else the line can carry: `checks.parity`, `sustained`, the exposed-exchange re-run, `closed_loop`, `roofline.valu.latency_ceiling`
+and `cpu_baseline` (each takes runs of its own); without it those fields are null or say that they were skipped.
 
 One "step" = one 30 Hz control step of EVERY env on the rank = 20 scene updates (20 SPD solves + 40 rigid-body substeps) + reward + observation
 + auto-reset per env.  By default (`--groups 0` = auto) the rank's envs run as two env groups of n / 2 on their own streams (deepmimic_amd/groups.py:
@@ -451,6 +455,17 @@ def closed_loop(envs, stream_handles, dev, steps, tables=None, parity_envs=0, pa
     return res
 
 
+def dump_outputs(out_dir, views, valid, ends):
+    """--dump-outputs: the learner record of the last timed control step (per group: state, reward, terminate; concatenated in env order) and the
+    per-env flags, as float32 .npy files (4096 humanoids: 3.8 MB in all)"""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"state": torch.cat([v[0] for v in views]), "reward": torch.cat([v[1] for v in views]), "terminate": torch.cat([v[2] for v in views]),
+              "valid": valid, "episode_end": ends}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a.detach().cpu().numpy().astype(np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -486,6 +501,12 @@ def main():
     ap.add_argument("--min-warmup", type=int, default=60,
                     help="control steps run before the timed region regardless of --warmup: the first episodes of a fresh batch are a "
                          "lighter mixture than steady state (nobody has fallen yet); two episode lengths reach it")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: checks.parity, the sustained window, the exposed-exchange re-run, closed_loop, the live latency ceiling "
+                         "and the CPU baseline (each takes runs of its own; a plain run skips them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller (rank 0's envs: state, reward, terminate, "
+                         "valid, episode_end) as DIR/<name>.npy in float32")
     args = ap.parse_args()
     if args.cpu_baseline_worker is not None:
         cpu_baseline_worker(args.scene, args.cpu_baseline_worker, args.cpu_budget)
@@ -619,6 +640,8 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed_local = elapsed
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, [exs[g].views((tick[0] - 1) & 1) for g in range(G)], valid, ends)
     if world > 1:
         tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
@@ -628,7 +651,7 @@ def main():
     # state on every box for the same flags (deterministic resets, bit-reproducible kernels), so the sample -- and its result -- is reproducible.  Rank 0 compares; with
     # a record exchange every rank takes the same steps
     parity = None
-    if not args.no_parity_check:
+    if args.full and not args.no_parity_check:
         taken = [0]
 
         def step_and_read():
@@ -661,7 +684,7 @@ def main():
     # a sustained window behind the --steps region: >= sustain-seconds of back-to-back control steps (same step function, same exchange), so
     # that the line also carries a rate measured over seconds (DVFS settled, visible to an outside GPU-busy sampler) next to the short one
     sustained = None
-    if on_gpu and args.sustain_seconds > 0:
+    if on_gpu and args.full and args.sustain_seconds > 0:
         k2 = int(np.ceil(args.sustain_seconds / (elapsed / args.steps)))       # `elapsed` is the max over ranks: the same count on every rank
         el2, _ = timed(k2)
         if world > 1:
@@ -674,7 +697,7 @@ def main():
     # interpretable -- value / N vs per_rank_no_gather tells exposed collective time from slow ranks
     local_rate = n * args.steps / elapsed_local
     exposed_ms = None
-    if gather:
+    if gather and args.full:
         gather_saved, gather = gather, False
         el_ng, _ = timed(args.steps)
         gather = gather_saved
@@ -696,7 +719,7 @@ def main():
     # extra, N = 1: the same envs driven by the on-device policy (dm_policy.h: S -> 1024 -> 512 -> A on the MFMA units -- 227 / 28 for the humanoid --, random init, sampled
     # actions) instead of fixed actions -- what a sampler sees per control step.  Never `value`; a failure here is reported, not fatal.
     closed = None
-    if on_gpu and world == 1 and not args.no_closed_loop and not gather:
+    if on_gpu and world == 1 and args.full and not args.no_closed_loop and not gather:
         try:
             closed = closed_loop(envs, [s.cuda_stream for s in gstreams] if G > 1 else [0], dev, min(max(args.steps, 200), 1000),      # >= 200 steps whatever --steps: a 20-step window is a transient
                                  tables=tables, parity_envs=(0 if args.no_parity_check else args.parity_envs), parity_steps=args.parity_steps, physics=args.physics)
@@ -718,7 +741,7 @@ def main():
             traffic = traffic * envs_per_launch / n
         value = world * n * args.steps / elapsed
         valu_obj = measured_valu(args.scene, n, kname, value, physics=args.physics) or {"binding": "VALU issue + dependent-chain latency (fp32 vector)", "source": []}
-        if on_gpu:
+        if on_gpu and args.full:
             try:
                 # kernel family of dm_kernels.cpp this workload launches (deepmimic_amd/csrc/Makefile KIDS): plain / AMP-or-perturbation / v2 instantiation of the
                 # two-per-wave kernel, or of the one-per-wave kernel on the compiled humanoid3d / dog3d topology, or biped + free body
@@ -766,10 +789,10 @@ def main():
             "checks": {"mean_reward": mean_reward, "finite": finite, "parity": parity},
             "closed_loop": closed,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"] = cpu_baseline(args.scene, args.cpu_budget)
         else:
-            out["cpu_baseline"] = {"value": None, "unit": "env-steps/s", "cores": 1, "kind": "port", "sample": "skipped (N>1 or --no-cpu-baseline)"}
+            out["cpu_baseline"] = {"value": None, "unit": "env-steps/s", "cores": 1, "kind": "port", "sample": "skipped (N>1, --no-cpu-baseline or no --full)"}
         print(json.dumps(out))
     if dist.is_initialized():
         dist.destroy_process_group()

@@ -517,6 +517,9 @@ class SharedEnv:
                     if time.monotonic() > t_end:
                         raise RuntimeError("DM_FACADE_SHARED: the owner process did not come up (see /dev/shm/%s.log)" % name)
                     time.sleep(0.05)
+                # the dimensions were read when the region was opened, which may have been before the owner wrote them (W = 0, no slots): open it again now that it is live
+                R.close()
+                R = Region(name)
             # still under the lock: claim a slot of the region that was just seen live
             free = np.nonzero(R.owner == 0)[0]
             if free.size == 0:

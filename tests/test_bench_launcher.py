@@ -7,15 +7,17 @@ import os
 import subprocess
 import sys
 
+import numpy as np
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def run_bench(emu_lib, extra, env_extra=None, timeout=900):
+def run_bench(emu_lib, extra, env_extra=None, timeout=900, full=True):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     env.update(DM_HIP_LIB=emu_lib, DM_ALLOW_EMULATOR="1")
     env.update(env_extra or {})
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--backend", "gloo", "--envs", "4", "--steps", "2", "--warmup", "1",
-                        "--min-warmup", "1", "--no-cpu-baseline", "--precision", "64"] + extra,
+                        "--min-warmup", "1", "--no-cpu-baseline", "--precision", "64"] + (["--full"] if full else []) + extra,
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=timeout)
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     return p, (json.loads(lines[-1]) if lines else None)
@@ -59,6 +61,25 @@ def test_bench_gpus_1_single_process(emu_lib):
     assert "traffic_source" in line["roofline"]
 
 
+def test_bench_plain_run_dumps_reproducible_outputs(emu_lib, tmp_path):
+    """a plain run (no --full) times its --steps, skips the extras and, with --dump-outputs, writes the last timed step's record as float32 .npy;
+    the same arguments give the same outputs"""
+    dumps = []
+    for k in range(2):
+        d = tmp_path / ("run%d" % k)
+        p, line = run_bench(emu_lib, ["--gpus", "1", "--dump-outputs", str(d)], full=False)
+        assert p.returncode == 0, p.stderr[-2000:]
+        assert line["steps"] == 2 and line["ms_per_step"] > 0 and abs(line["ms_per_step"] * line["value"] / 1e3 - 4) < 1e-6 * line["value"]
+        assert line["checks"]["parity"] is None and line["sustained"] is None and line["closed_loop"] is None and line["cpu_baseline"]["value"] is None
+        dumps.append({f.stem: np.load(f) for f in sorted(d.glob("*.npy"))})
+    a, b = dumps
+    assert sorted(a) == ["episode_end", "reward", "state", "terminate", "valid"]
+    assert a["state"].shape[0] == 4 and a["state"].ndim == 2 and a["reward"].shape == (4,)
+    for name in a:
+        assert a[name].dtype == np.float32 and np.array_equal(a[name], b[name]), name
+    assert np.isfinite(a["state"]).all() and np.all((a["valid"] == 0) | (a["valid"] == 1))
+
+
 def test_bench_refuses_rank_count_mismatch(emu_lib):
     # an external launcher that started ONE rank for --gpus 2 must not yield an N = 1 number under an N = 2 command
     p, line = run_bench(emu_lib, ["--gpus", "2"], env_extra={"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
@@ -95,7 +116,7 @@ def test_bench_record_exchange_is_hidden_gpu(hip_lib, gather):
             sk.bind(("127.0.0.1", 0)); port = sk.getsockname()[1]
         env.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK="0", WORLD_SIZE="1", LOCAL_RANK="0", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "200", "--warmup", "10", "--force-gather", "--gather", gather,
-                        "--no-cpu-baseline", "--sustain-seconds", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline", "--sustain-seconds", "0"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
     assert line["record_exchange"]["backend"] == gather and line["config"]["groups"] == 2      # (round 5: one exchange per env group on either route)
@@ -108,7 +129,7 @@ def test_bench_record_exchange_is_hidden_gpu(hip_lib, gather):
 def test_bench_default_line_gpu(hip_lib):
     """the driver's command: the line carries the two env groups, the binding bound (roofline.valu) and the sustained window"""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT", "DM_HIP_LIB", "DM_ALLOW_EMULATOR")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--no-cpu-baseline"], env=env, stdout=subprocess.PIPE,
                        stderr=subprocess.PIPE, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])

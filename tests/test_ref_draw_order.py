@@ -698,10 +698,10 @@ def test_imitate_scenes_live(emu_lib, monkeypatch, arg_file, steps, resets):
 
 
 def _shipped_arg_files():
-    import glob
-    files = sorted(os.path.relpath(f, REF) for f in glob.glob(os.path.join(REF, "args", "*.txt")))
-    # no agent (the viewer's kin_char scenes) / motion files that are not in the reference's repository
-    files = [f for f in files if "play_motion" not in f and "_locomotion_args" not in f and "walk_punch" not in f]
+    # the reference's args/*.txt, as a committed list so that the cases are the same on every machine (tests/golden/ref_arg_files.txt); left out: the viewer's
+    # kin_char scenes (no agent) and the files whose motions are not in the reference's repository (play_motion, *_locomotion_args, walk_punch)
+    with open(os.path.join(ROOT, "tests", "golden", "ref_arg_files.txt")) as f:
+        files = [l.strip() for l in f if l.strip()]
     return files[::9] if os.environ.get("DM_LIVE_SWEEP") == "sample" else files
 
 
