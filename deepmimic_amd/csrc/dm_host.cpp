@@ -295,6 +295,22 @@ static int build_host_model(const dm_scene_tables& t, int max_contacts, HostMode
     return 0;
 }
 
+// ---------------------------------------------------------------- kernel family of a step launch
+// The object a step-kernel launch runs: DM_FAMILY_<id> of dm_kernels.cpp (KIDS of the Makefiles), from the class (CtxT::cls numbering), the
+// variant (SV_PLAIN / SV_AMP / SV_TAPS / SV_V2) and the wave packing; -1 for a combination no family instantiates.  Reported by dm_get_debug "family".
+template <typename C> struct ClsId;
+template <> struct ClsId<ClsBiped> { static constexpr int v = 0; };
+template <> struct ClsId<ClsLarge> { static constexpr int v = 1; };
+template <> struct ClsId<ClsBipedObj> { static constexpr int v = 2; };
+template <> struct ClsId<ClsLargeTree> { static constexpr int v = 3; };
+template <> struct ClsId<ClsBipedTree> { static constexpr int v = 4; };
+static int step_family(int cls, int variant, bool duo) {
+    static const int one[5][4] = {{3, 4, 5, 18}, {6, 7, 8, 19}, {-1, 9, 10, 23}, {12, 13, 14, 20}, {15, 16, 17, 21}};      // [class][variant], one character per wavefront
+    static const int two[5][4] = {{0, 1, 2, 22}, {-1, -1, -1, -1}, {-1, 24, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};  // two characters per wavefront
+    if (cls < 0 || cls > 4 || variant < 0 || variant > 3) return -1;
+    return duo ? two[cls][variant] : one[cls][variant];
+}
+
 // ---------------------------------------------------------------- device-side context, typed on the kernel precision
 struct CtxBase {
     HostModel hm; int N = 0; int env_off = 0; uint64_t seed = 0; int precision = 32; int max_contacts = 20; int device_id = 0;
@@ -302,6 +318,7 @@ struct CtxBase {
     std::vector<void*> allocs;
     float *d_actions = nullptr, *d_states = nullptr, *d_rewards = nullptr; int *d_term = nullptr, *d_valid = nullptr, *d_end = nullptr;
     bool duo = false, duo_obj = true, upload_failed = false; int physics = 1;
+    int last_family = -1;                  // step_family() of the last step-kernel launch (step, dm_probe 3 / 4); -1 before any
     int* d_ids = nullptr; const int* step_ids = nullptr; int step_n_ids = 0;      // dm_step_envs: the subset the next step() call runs (device ids), cleared after it
     virtual ~CtxBase() { for (void* p : allocs) rt_free(p); }
     void* dalloc(size_t n) { void* p = nullptr; if (rt_malloc(&p, n) != 0) return nullptr; allocs.push_back(p); return p; }
@@ -543,6 +560,16 @@ struct CtxT : CtxBase {
         d_prof = (long long*)dalloc(sizeof(long long) * N * 16);
         return dbg.links ? 0 : fail("device allocation failed");
     }
+    // every step-kernel launch goes through these: they record the family it runs (dm_get_debug "family")
+    template <typename C, int V> void run_step(unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
+        last_family = step_family(ClsId<C>::v, V, false); launch_step<Real, C, V>(grid, stream, md, st, io, d);
+    }
+    template <int V> void run_step_duo(unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
+        last_family = step_family(ClsId<ClsBiped>::v, V, true); launch_step_duo<Real, V>(grid, stream, md, st, io, d);
+    }
+    template <typename C, int V> void run_step_duo_c(unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
+        last_family = step_family(ClsId<C>::v, V, true); launch_step_duo_c<Real, C, V>(grid, stream, md, st, io, d);
+    }
 #define DM_DISPATCH(LAUNCH, grid, ...)                                                       \
     do {                                                                                     \
         if (cls == 0) LAUNCH<Real, ClsBiped>(grid, stream, __VA_ARGS__);                         \
@@ -569,38 +596,38 @@ struct CtxT : CtxBase {
         io.n_updates = n_updates; io.dt = dt; io.auto_reset = (flags & DM_AUTO_RESET) ? 1 : 0; io.emit = (flags & DM_NO_EMIT) ? 0 : 1; io.open_loop = (flags & DM_OPEN_LOOP) ? 1 : 0; io.end_early = (flags & DM_END_EPISODE_EARLY) ? 1 : 0;
         // two characters per wavefront: biped class, even batch, no debug taps armed (DM_DUO=0 keeps one character per wave)
         if (duo && cls == 0 && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape) {      // (31 row lanes per character assume exactly 34 dofs; a bound draw tape is read by the one-per-wave kernels only -- EnvSim::tape() -- so such a batch takes them: ADVICE r5)
-            if (st.manif) launch_step_duo<Real, SV_V2>(N / 2, stream, md, st, io, dbg);               // DM-physics v2, two characters per wavefront (round 4)
-            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) launch_step_duo<Real, SV_AMP>(N / 2, stream, md, st, io, dbg);      // (the AMP instantiation also carries the perturbation code)
-            else launch_step_duo<Real, SV_PLAIN>(N / 2, stream, md, st, io, dbg);
+            if (st.manif) run_step_duo<SV_V2>(N / 2, io, dbg);               // DM-physics v2, two characters per wavefront (round 4)
+            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) run_step_duo<SV_AMP>(N / 2, io, dbg);      // (the AMP instantiation also carries the perturbation code)
+            else run_step_duo<SV_PLAIN>(N / 2, io, dbg);
             return 0;
         }
         // biped + free body (dribble_amp), two characters per wavefront (round 6; DM-physics v1 -- v2 and armed taps keep the one-per-wave kernel).  DM_DUO_OBJ=0: one per wave
         if (duo && duo_obj && cls == 2 && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape && !st.manif) {
-            launch_step_duo_c<Real, ClsBipedObj, SV_AMP>(N / 2, stream, md, st, io, dbg);
+            run_step_duo_c<ClsBipedObj, SV_AMP>(N / 2, io, dbg);
             return 0;
         }
         // production launch: the tap-free instantiation unless a parity test armed the debug taps (dm_probe)
         if (cls == 2) {
-            if (dbg.H) launch_step<Real, ClsBipedObj, SV_TAPS>(GN, stream, md, st, io, dbg);
-            else if (st.manif) launch_step<Real, ClsBipedObj, SV_V2>(GN, stream, md, st, io, dbg);      // round 5: the links' ground contacts through the persistent manifolds, the ball's single-point contacts as under v1
-            else launch_step<Real, ClsBipedObj, SV_AMP>(GN, stream, md, st, io, dbg);
+            if (dbg.H) run_step<ClsBipedObj, SV_TAPS>(GN, io, dbg);
+            else if (st.manif) run_step<ClsBipedObj, SV_V2>(GN, io, dbg);      // round 5: the links' ground contacts through the persistent manifolds, the ball's single-point contacts as under v1
+            else run_step<ClsBipedObj, SV_AMP>(GN, io, dbg);
         }
         else if (cls == 4) {
-            if (dbg.H) launch_step<Real, ClsBipedTree, SV_TAPS>(GN, stream, md, st, io, dbg);
-            else if (st.manif) launch_step<Real, ClsBipedTree, SV_V2>(GN, stream, md, st, io, dbg);
-            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) launch_step<Real, ClsBipedTree, SV_AMP>(GN, stream, md, st, io, dbg);
-            else launch_step<Real, ClsBipedTree, SV_PLAIN>(GN, stream, md, st, io, dbg);
+            if (dbg.H) run_step<ClsBipedTree, SV_TAPS>(GN, io, dbg);
+            else if (st.manif) run_step<ClsBipedTree, SV_V2>(GN, io, dbg);
+            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) run_step<ClsBipedTree, SV_AMP>(GN, io, dbg);
+            else run_step<ClsBipedTree, SV_PLAIN>(GN, io, dbg);
         }
         else if (cls == 3) {
-            if (dbg.H) launch_step<Real, ClsLargeTree, SV_TAPS>(GN, stream, md, st, io, dbg);
-            else if (st.manif) launch_step<Real, ClsLargeTree, SV_V2>(GN, stream, md, st, io, dbg);
-            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) launch_step<Real, ClsLargeTree, SV_AMP>(GN, stream, md, st, io, dbg);
-            else launch_step<Real, ClsLargeTree, SV_PLAIN>(GN, stream, md, st, io, dbg);
+            if (dbg.H) run_step<ClsLargeTree, SV_TAPS>(GN, io, dbg);
+            else if (st.manif) run_step<ClsLargeTree, SV_V2>(GN, io, dbg);
+            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) run_step<ClsLargeTree, SV_AMP>(GN, io, dbg);
+            else run_step<ClsLargeTree, SV_PLAIN>(GN, io, dbg);
         }
-        else if (dbg.H) { if (cls == 0) launch_step<Real, ClsBiped, SV_TAPS>(GN, stream, md, st, io, dbg); else launch_step<Real, ClsLarge, SV_TAPS>(GN, stream, md, st, io, dbg); }
-        else if (st.manif) { if (cls == 0) launch_step<Real, ClsBiped, SV_V2>(GN, stream, md, st, io, dbg); else launch_step<Real, ClsLarge, SV_V2>(GN, stream, md, st, io, dbg); }      // DM-physics v2: its own instantiation (AMP code + manifolds)
-        else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) { if (cls == 0) launch_step<Real, ClsBiped, SV_AMP>(GN, stream, md, st, io, dbg); else launch_step<Real, ClsLarge, SV_AMP>(GN, stream, md, st, io, dbg); }
-        else { if (cls == 0) launch_step<Real, ClsBiped, SV_PLAIN>(GN, stream, md, st, io, dbg); else launch_step<Real, ClsLarge, SV_PLAIN>(GN, stream, md, st, io, dbg); }
+        else if (dbg.H) { if (cls == 0) run_step<ClsBiped, SV_TAPS>(GN, io, dbg); else run_step<ClsLarge, SV_TAPS>(GN, io, dbg); }
+        else if (st.manif) { if (cls == 0) run_step<ClsBiped, SV_V2>(GN, io, dbg); else run_step<ClsLarge, SV_V2>(GN, io, dbg); }      // DM-physics v2: its own instantiation (AMP code + manifolds)
+        else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) { if (cls == 0) run_step<ClsBiped, SV_AMP>(GN, io, dbg); else run_step<ClsLarge, SV_AMP>(GN, io, dbg); }
+        else { if (cls == 0) run_step<ClsBiped, SV_PLAIN>(GN, io, dbg); else run_step<ClsLarge, SV_PLAIN>(GN, io, dbg); }
         return 0;
     }
     int amp_expert(int n, const double* times_dev, const double* gh_dev, float* out_dev) override { return amp_expert_clips(n, nullptr, times_dev, gh_dev, out_dev); }
@@ -770,12 +797,12 @@ struct CtxT : CtxBase {
             io.states = d_states; io.rewards = d_rewards; io.terminate = d_term; io.valid = d_valid; io.episode_end = d_end;
             io.n_updates = 20; io.dt = dt; io.auto_reset = 1; io.emit = 1; io.open_loop = (what == 3) ? 1 : 0; io.end_early = 1;
             if (what == 4) io.actions = d_actions;
-            if (duo && cls == 0 && hm.D == ClsBiped::ND && (N % 2) == 0 && !st.manif) launch_step_duo<Real, SV_TAPS>(N / 2, stream, md, st, io, d2);
-            else if (cls == 0) launch_step<Real, ClsBiped, SV_TAPS>(N, stream, md, st, io, d2);
-            else if (cls == 2) launch_step<Real, ClsBipedObj, SV_TAPS>(N, stream, md, st, io, d2);
-            else if (cls == 3) launch_step<Real, ClsLargeTree, SV_TAPS>(N, stream, md, st, io, d2);
-            else if (cls == 4) launch_step<Real, ClsBipedTree, SV_TAPS>(N, stream, md, st, io, d2);
-            else launch_step<Real, ClsLarge, SV_TAPS>(N, stream, md, st, io, d2);
+            if (duo && cls == 0 && hm.D == ClsBiped::ND && (N % 2) == 0 && !st.manif) run_step_duo<SV_TAPS>(N / 2, io, d2);
+            else if (cls == 0) run_step<ClsBiped, SV_TAPS>(N, io, d2);
+            else if (cls == 2) run_step<ClsBipedObj, SV_TAPS>(N, io, d2);
+            else if (cls == 3) run_step<ClsLargeTree, SV_TAPS>(N, io, d2);
+            else if (cls == 4) run_step<ClsBipedTree, SV_TAPS>(N, io, d2);
+            else run_step<ClsLarge, SV_TAPS>(N, io, d2);
             return 0;
         }
         DM_DISPATCH(launch_probe, N, md, st, dbg, what, dt);
@@ -817,6 +844,10 @@ struct CtxT : CtxBase {
     int get_debug(const char* name, double* out) override {
         const size_t n = N; const HostModel& h = hm; std::string s(name);
         if (s == "tau") return dl(st.tau, n * h.D, out);
+        if (s == "family") {        // N: the kernel family (DM_FAMILY_<id>) of the last step-kernel launch, the same for every env; -1 before any
+            for (size_t e = 0; e < n; ++e) out[e] = (double)last_family;
+            return 0;
+        }
         if (s == "borrowed") {      // N: substeps the env's pair ran with one character's rows 32.. on lanes borrowed from its partner's half (two-per-wave kernel, DuoSim::substep_rows_xd)
             std::vector<double> t6(n * 6); if (rt_d2h(t6.data(), st.clock, sizeof(double) * n * 6, stream)) return fail("copy failed");
             for (size_t e = 0; e < n; ++e) out[e] = t6[e * 6 + 5];
