@@ -80,7 +80,9 @@ DMP_DEV f32x4 mfma16(const bf16x8& a, const bf16x8& b, f32x4 c) { return __built
 DMP_DEV float lane_xor_f(float v, int mask) { return __shfl_xor(v, mask, 64); }
 #endif
 
-DMP_DEV uint16_t f32_to_bf16(float f) {          // round to nearest even (inputs are finite)
+// round to nearest even.  Never called on a NaN (some NaN payloads would carry into the sign bit): every caller passes the value through fminf / fmaxf
+// first, which return their other operand -- a NaN observation becomes -s_clip (-inf without a clip), a NaN pre-activation 0; +-inf stays +-inf
+DMP_DEV uint16_t f32_to_bf16(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
     u += 0x7fffu + ((u >> 16) & 1u);
     return (uint16_t)(u >> 16);

@@ -4,6 +4,7 @@
 
 struct dm_policy {
     dmp::PolicyDev pd; int device_id = 0; int cap = 0;
+    int last_path = DM_POLICY_PATH_NONE, last_rows = 0;      // dm_policy_info: the kernels of the last dm_policy_forward(_ex)
     uint16_t *h1 = nullptr, *h2 = nullptr, *s16 = nullptr;
     std::vector<void*> allocs;
     ~dm_policy() { for (void* p : allocs) rt_free(p); if (h1) rt_free(h1); if (h2) rt_free(h2); if (s16) rt_free(s16); }
@@ -42,7 +43,32 @@ static std::vector<uint16_t> pack_fused_stream(const std::vector<uint16_t>& w1p,
     return out;
 }
 
+// The ONE place that decides which kernels a forward call runs (ids: include/dm_hip.h dm_policy_path): dm_policy_forward_ex launches from the id
+// this returns and dm_policy_info reports it, so the report cannot drift from the launch.
+// One launch for the whole actor (k_policy_fused) where it is compiled for the widths; DM_POLICY_LAYERED=1 keeps the per-layer kernels (A/B, tests).
+// Per layer: the LDS-tiled four-wave GEMM when the width allows it (a multiple of 128), the one-wave kernel otherwise or under DM_POLICY_ONE_WAVE.
+// 64-row tiles by default (measured: 45 / 82 us at 4096 / 16384 rows against 56 / 85 us with 128-row tiles: more workgroups per CU hide more
+// of the L2 latency than the bigger tile saves in traffic); DM_POLICY_TILE=128 selects the tall tile
+static int policy_path(const dmp::PolicyDev& d) {
+    if (d.wfs && getenv("DM_POLICY_LAYERED") == nullptr) {
+        if (d.K1 == 256) return d.N3 == 32 ? DM_POLICY_PATH_FUSED_8_2 : DM_POLICY_PATH_FUSED_8_4;
+        return d.N3 == 32 ? DM_POLICY_PATH_FUSED_12_2 : DM_POLICY_PATH_FUSED_12_4;
+    }
+    const bool tiled = (getenv("DM_POLICY_ONE_WAVE") == nullptr);
+    int tile = DM_POLICY_LAYER_TILE64;
+    if (const char* tl = getenv("DM_POLICY_TILE")) if (atoi(tl) == 128) tile = DM_POLICY_LAYER_TILE128;
+    const int l1 = (tiled && d.H1 % 128 == 0) ? tile : DM_POLICY_LAYER_ONE_WAVE, l2 = (tiled && d.H2 % 128 == 0) ? tile : DM_POLICY_LAYER_ONE_WAVE;
+    return DM_POLICY_PATH_LAYERED(l1, l2);
+}
+
 extern "C" {
+
+int dm_policy_info(dm_policy* p, int32_t* out) {
+    if (!p || !out) return fail("null argument");
+    for (int i = 0; i < 8; ++i) out[i] = 0;
+    out[0] = p->pd.K1; out[1] = p->pd.N3; out[2] = p->pd.wfs ? 1 : 0; out[3] = p->last_path; out[4] = p->last_rows;
+    return 0;
+}
 
 int dm_policy_create(int device_id, const dm_policy_params* pp, dm_policy** out) {
     if (!pp || !out) return fail("null argument");
@@ -114,17 +140,20 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
     if (const char* pr = getenv("DM_POLICY_PROBE")) io.probe = atoi(pr);
     io.goals = goal_dim ? goals_dev : nullptr; io.G = goal_dim; io.exp_rate = (float)exp_rate; io.exp_flags = exp_flags_dev;
     const dmp::PolicyDev& d = p->pd;
-    // one launch for the whole actor (k_policy_fused) where it is compiled for the widths; DM_POLICY_LAYERED=1 keeps the per-layer kernels (A/B, tests)
-    if (d.wfs && getenv("DM_POLICY_LAYERED") == nullptr) {
+    const int path = policy_path(d);
+    p->last_path = path; p->last_rows = n;
+    if (path < DM_POLICY_PATH_LAYERED_BASE) {
         const unsigned grid = (unsigned)((n + 31) / 32);
 #ifndef DM_EMU
         static unsigned long long* prof_buf = nullptr; static int prof_calls = 0;
         if (io.probe == 2) { if (!prof_buf && hipMalloc((void**)&prof_buf, (size_t)8192 * 8 * 8) != hipSuccess) prof_buf = nullptr; io.prof = grid <= 8192 ? prof_buf : nullptr; }
 #endif
-        if (d.K1 == 256 && d.N3 == 32) RT_LAUNCH4((dmp::k_policy_fused<8, 2>), grid, stream, d, io);
-        else if (d.K1 == 256) RT_LAUNCH4((dmp::k_policy_fused<8, 4>), grid, stream, d, io);
-        else if (d.N3 == 32) RT_LAUNCH4((dmp::k_policy_fused<12, 2>), grid, stream, d, io);
-        else RT_LAUNCH4((dmp::k_policy_fused<12, 4>), grid, stream, d, io);
+        switch (path) {
+        case DM_POLICY_PATH_FUSED_8_2: RT_LAUNCH4((dmp::k_policy_fused<8, 2>), grid, stream, d, io); break;
+        case DM_POLICY_PATH_FUSED_8_4: RT_LAUNCH4((dmp::k_policy_fused<8, 4>), grid, stream, d, io); break;
+        case DM_POLICY_PATH_FUSED_12_2: RT_LAUNCH4((dmp::k_policy_fused<12, 2>), grid, stream, d, io); break;
+        default: RT_LAUNCH4((dmp::k_policy_fused<12, 4>), grid, stream, d, io); break;
+        }
 #ifndef DM_EMU
         hipError_t le0 = hipGetLastError(); if (le0 != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le0));
         if (io.prof && ++prof_calls == 100) {          // DM_POLICY_PROBE=2: phase times of the 100th launch (100 MHz constant clock -> ns), mean over the workgroups
@@ -140,20 +169,16 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
     }
     // tiles sized so that every launch has at least ~1 wave per SIMD at 4096 rows: 64 x 64 (layer 1), 32 x 64 (layer 2), 16 x 32 (layer 3)
     RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
-    // layers 1 and 2: the LDS-tiled four-wave GEMM when the width allows it, the one-wave kernel otherwise
-    const bool tiled = (getenv("DM_POLICY_ONE_WAVE") == nullptr);
-    // 64-row tiles by default (measured: 45 / 82 us at 4096 / 16384 rows against 56 / 85 us with 128-row tiles: more workgroups per CU hide more
-    // of the L2 latency than the bigger tile saves in traffic); DM_POLICY_TILE=128 selects the tall tile
-    bool big1 = false, big2 = false;
-    if (const char* tl = getenv("DM_POLICY_TILE")) big1 = big2 = (atoi(tl) == 128);
-    if (tiled && d.H1 % 128 == 0) {
-        if (big1) RT_LAUNCH4((dmp::k_policy_gemm<0, 128>), ((n + 127) / 128) * (d.H1 / 128), stream, d, io);
-        else RT_LAUNCH4((dmp::k_policy_gemm<0, 64>), ((n + 63) / 64) * (d.H1 / 128), stream, d, io);
-    } else RT_LAUNCH((dmp::k_policy_layer<0, 4, 4>), ((n + 63) / 64) * (d.H1 / 64), stream, d, io);
-    if (tiled && d.H2 % 128 == 0) {
-        if (big2) RT_LAUNCH4((dmp::k_policy_gemm<1, 128>), ((n + 127) / 128) * (d.H2 / 128), stream, d, io);
-        else RT_LAUNCH4((dmp::k_policy_gemm<1, 64>), ((n + 63) / 64) * (d.H2 / 128), stream, d, io);
-    } else RT_LAUNCH((dmp::k_policy_layer<1, 2, 4>), ((n + 31) / 32) * (d.H2 / 64), stream, d, io);
+    switch (DM_POLICY_PATH_LAYER1(path)) {
+    case DM_POLICY_LAYER_TILE128: RT_LAUNCH4((dmp::k_policy_gemm<0, 128>), ((n + 127) / 128) * (d.H1 / 128), stream, d, io); break;
+    case DM_POLICY_LAYER_TILE64: RT_LAUNCH4((dmp::k_policy_gemm<0, 64>), ((n + 63) / 64) * (d.H1 / 128), stream, d, io); break;
+    default: RT_LAUNCH((dmp::k_policy_layer<0, 4, 4>), ((n + 63) / 64) * (d.H1 / 64), stream, d, io); break;
+    }
+    switch (DM_POLICY_PATH_LAYER2(path)) {
+    case DM_POLICY_LAYER_TILE128: RT_LAUNCH4((dmp::k_policy_gemm<1, 128>), ((n + 127) / 128) * (d.H2 / 128), stream, d, io); break;
+    case DM_POLICY_LAYER_TILE64: RT_LAUNCH4((dmp::k_policy_gemm<1, 64>), ((n + 63) / 64) * (d.H2 / 128), stream, d, io); break;
+    default: RT_LAUNCH((dmp::k_policy_layer<1, 2, 4>), ((n + 31) / 32) * (d.H2 / 64), stream, d, io); break;
+    }
     RT_LAUNCH((dmp::k_policy_layer<2, 1, 2>), (n + 15) / 16, stream, d, io);   // one workgroup per 16 rows owns all N3 columns (logp is a row sum)
 #ifndef DM_EMU
     hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));

@@ -90,6 +90,15 @@ class Policy:
         self.forward_device(s.ctypes.data, n, a.ctypes.data, lp.ctypes.data, sample, seed, step, env_id_offset)
         return a, lp
 
+    def info(self) -> dict:
+        """dm_policy_info (include/dm_hip.h): the padded widths K1 / N3, whether the one-launch actor's weight stream exists, and the
+        dm_policy_path id and row count of the last forward call (path -1 before any)"""
+        out = (C.c_int32 * 8)()
+        self.lib.dm_policy_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
+        if self.lib.dm_policy_info(self.h, out) != 0:
+            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        return dict(K1=int(out[0]), N3=int(out[1]), fused=bool(out[2]), path=int(out[3]), rows=int(out[4]))
+
     def close(self):
         if getattr(self, "h", None):
             self.lib.dm_policy_destroy(self.h)

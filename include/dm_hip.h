@@ -370,7 +370,8 @@ int dm_scene_free(dm_scene* scene);
  * learning/nets/fc_2layers_1024units.py and the normalisers of learning/normalizer.py:95-102, on the matrix cores (bf16
  * operands, fp32 accumulate), so that observation -> action -> control step stays on the GPU.  Weights are fp32 host
  * arrays in tf.layers.dense layout (kernel [in x out] row-major, bias [out]); NULL normaliser / logstd arrays mean
- * identity / 0.  s_clip <= 0: no clipping. */
+ * identity / 0.  s_clip <= 0: no clipping.  Non-finite observations: with a clip +-inf is clipped like any large value and NaN enters the net
+ * as -s_clip; without one the actions of THAT row are unspecified (inf, NaN or finite).  No other row is affected either way. */
 typedef struct dm_policy dm_policy;
 typedef struct {
     int state_dim, hidden1, hidden2, action_dim;      /* reference: S, 1024, 512, A; hidden widths multiples of 64 */
@@ -397,6 +398,33 @@ int dm_policy_forward(dm_policy* policy, const float* states_dev, int n, float* 
 int dm_policy_forward_ex(dm_policy* policy, const float* states_dev, const float* goals_dev, int goal_dim, int n, float* actions_dev,
                          float* logp_dev, int32_t* exp_flags_dev, double exp_rate, int sample, uint64_t seed, uint32_t step, int env_id_offset,
                          void* hip_stream);
+/* Which kernels a forward call ran (deepmimic_amd/csrc/dm_policy_host.h policy_path, the one function every launch goes through):
+ * the one-launch actor k_policy_fused<K1 / 32, N3 / 16> where it is compiled for the widths (1024, 512, K1 256 / 384, N3 32 / 64), else k_policy_prep +
+ * one kernel per layer: layers 1 and 2 each on the one-wave kernel (k_policy_layer<0,4,4> / <1,2,4>) or on the LDS-tiled GEMM with 64- or 128-row
+ * tiles (k_policy_gemm<layer, 64 | 128>), then k_policy_layer<2,1,2>.  A per-layer id is DM_POLICY_PATH_LAYERED(layer-1 choice, layer-2 choice). */
+enum { DM_POLICY_LAYER_ONE_WAVE = 0, DM_POLICY_LAYER_TILE64 = 1, DM_POLICY_LAYER_TILE128 = 2 };
+#define DM_POLICY_PATH_LAYERED_BASE 16
+#define DM_POLICY_PATH_LAYERED(l1, l2) (DM_POLICY_PATH_LAYERED_BASE + (l1) + 4 * (l2))
+#define DM_POLICY_PATH_LAYER1(path) (((path) - DM_POLICY_PATH_LAYERED_BASE) & 3)
+#define DM_POLICY_PATH_LAYER2(path) (((path) - DM_POLICY_PATH_LAYERED_BASE) >> 2)
+enum dm_policy_path {
+    DM_POLICY_PATH_NONE = -1,                /* no forward call yet */
+    DM_POLICY_PATH_FUSED_8_2 = 0,            /* k_policy_fused<8, 2>:  K1 = 256, N3 = 32 */
+    DM_POLICY_PATH_FUSED_8_4 = 1,            /* k_policy_fused<8, 4>:  K1 = 256, N3 = 64 */
+    DM_POLICY_PATH_FUSED_12_2 = 2,           /* k_policy_fused<12, 2>: K1 = 384, N3 = 32 */
+    DM_POLICY_PATH_FUSED_12_4 = 3,           /* k_policy_fused<12, 4>: K1 = 384, N3 = 64 */
+    DM_POLICY_PATH_WAVE_WAVE = 16,           /* layer<0,4,4>, layer<1,2,4>: DM_POLICY_ONE_WAVE, or neither hidden width a multiple of 128 */
+    DM_POLICY_PATH_TILE64_WAVE = 17,         /* gemm<0,64>,   layer<1,2,4> */
+    DM_POLICY_PATH_TILE128_WAVE = 18,        /* gemm<0,128>,  layer<1,2,4> */
+    DM_POLICY_PATH_WAVE_TILE64 = 20,         /* layer<0,4,4>, gemm<1,64> */
+    DM_POLICY_PATH_TILE64_TILE64 = 21,       /* gemm<0,64>,   gemm<1,64>: the per-layer default at 1024 / 512 */
+    DM_POLICY_PATH_WAVE_TILE128 = 24,        /* layer<0,4,4>, gemm<1,128> */
+    DM_POLICY_PATH_TILE128_TILE128 = 26      /* gemm<0,128>,  gemm<1,128>: DM_POLICY_TILE=128 */
+};
+/* out[0] = K1 and out[1] = N3, the padded input / action widths the context really uses; out[2] = 1 if it holds a fused weight stream;
+ * out[3] = dm_policy_path of the LAST dm_policy_forward(_ex) on this context (DM_POLICY_PATH_NONE before any; the environment switches
+ * DM_POLICY_LAYERED / DM_POLICY_ONE_WAVE / DM_POLICY_TILE are read per call); out[4] = its row count; out[5..7] = 0 (reserved) */
+int dm_policy_info(dm_policy* policy, int32_t* out);
 
 /* ---- Running observation statistics on the device: the Normalizer of the reference's learner (learning/normalizer.py:6-152; the
  * s_norm / g_norm / amp_obs_norm of learning/rl_agent.py:466-483, amp_agent.py:290-291) for records that stay in HBM.
