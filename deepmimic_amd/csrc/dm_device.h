@@ -29,7 +29,6 @@
 #ifdef DM_EMU
 static inline long long dm_clock() { return 0; }
 template <int P> static inline void dm_setprio() {}
-template <typename T> static inline T* dm_uniform_ptr(T* p) { return p; }
 #define DM_DEV inline
 #define DM_OPAQUE_S(x) ((void)0)
 #define DM_OPAQUE_V(x) ((void)0)
@@ -82,10 +81,7 @@ template <int NP2, typename R2, typename Real> static inline void wave_gram32(co
     __syncthreads();
 }
 // two / four packed reals (GCC vector extension on the host emulator)
-// 64-row Gram: generic statement (the emulator build and fp64)
-template <int NP2, typename R2, typename Real> static inline void wave_gram64(const R2* y2, Real (&out)[64]) {
-    for (int i = 0; i < 64; ++i) { Real a = 0; for (int p = 0; p < NP2; ++p) a += y2[p][0] * lane_bcast(y2[p][0], i) + y2[p][1] * lane_bcast(y2[p][1], i); out[i] = a; }
-}
+// 64-row Gram, one half of the entries at a time: generic statement (the emulator build and fp64)
 template <int NP2, int H, typename R2, typename Real> static inline void wave_gram64_half(const R2* y2, Real (&out)[32]) {
     for (int i = 0; i < 32; ++i) { Real a = 0; for (int p = 0; p < NP2; ++p) a += y2[p][0] * lane_bcast(y2[p][0], 32 * H + i) + y2[p][1] * lane_bcast(y2[p][1], 32 * H + i); out[i] = a; }
 }
@@ -106,12 +102,6 @@ template <> struct VecT<double> { typedef double v2 __attribute__((vector_size(1
 #define DM_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 __device__ __forceinline__ long long dm_clock() { return (long long)__builtin_readcyclecounter(); }
 template <int P> __device__ __forceinline__ void dm_setprio() { __builtin_amdgcn_s_setprio(P); }
-// a pointer the caller knows to be wave-uniform, handed to the compiler as a scalar pair (global accesses then take the SGPR base + VGPR offset form)
-template <typename T> __device__ __forceinline__ T* dm_uniform_ptr(T* p) {
-    const uint64_t v = (uint64_t)p;
-    const uint32_t lo = __builtin_amdgcn_readfirstlane((uint32_t)v), hi = __builtin_amdgcn_readfirstlane((uint32_t)(v >> 32));
-    return (T*)(((uint64_t)hi << 32) | (uint64_t)lo);
-}
 __device__ __forceinline__ int dm_atomic_or(int* p, int v) { return atomicOr(p, v); }
 __device__ __forceinline__ int dm_atomic_min(int* p, int v) { return atomicMin(p, v); }
 __device__ __forceinline__ int dm_atomic_add(int* p, int v) { return atomicAdd(p, v); }
@@ -241,37 +231,12 @@ template <int NP2> __device__ __forceinline__ void wave_gram32(const VecT<float>
         out[8 * (v / 4) + 4 + (v % 4)] = __uint_as_float(sw[1]);
     }
 }
-// G[i] = sum_k y_l[k] y_i[k], i < 64: all 64 Gram rows on the matrix core.  With op0 = [Y[k0][0..31] | Y[k1][0..31]] and
+// G[i] = sum_k y_l[k] y_i[k], i < 64: all 64 Gram rows on the matrix core, half of each row per call.  With op0 = [Y[k0][0..31] | Y[k1][0..31]] and
 // op1 = [Y[k0][32..63] | Y[k1][32..63]] (one v_permlane32_swap of the lane's column pair) the four 32 x 32 blocks are the MFMA
 // chains (op0,op0), (op0,op1), (op1,op0), (op1,op1); lane j of either half holds column j of each block, rows split between the
 // halves.  Row r < 32 of G is [block00 column r | block10 column r], row 32 + r is [block01 column r | block11 column r] (G is
-// symmetric), so two swaps per accumulator pair hand every lane its full row.
-template <int NP2> __device__ __forceinline__ void wave_gram64(const VecT<float>::v2* y2, float (&out)[64]) {
-    typedef float f16v __attribute__((ext_vector_type(16)));
-    const f16v z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
-    f16v a00 = z, a01 = z, a10 = z, a11 = z;
-#pragma unroll
-    for (int p = 0; p < NP2; ++p) {
-        const auto sw = __builtin_amdgcn_permlane32_swap(__float_as_uint(y2[p][0]), __float_as_uint(y2[p][1]), false, false);
-        const float op0 = __uint_as_float(sw[0]), op1 = __uint_as_float(sw[1]);
-        a00 = __builtin_amdgcn_mfma_f32_32x32x2f32(op0, op0, a00, 0, 0, 0);
-        a01 = __builtin_amdgcn_mfma_f32_32x32x2f32(op0, op1, a01, 0, 0, 0);
-        a10 = __builtin_amdgcn_mfma_f32_32x32x2f32(op1, op0, a10, 0, 0, 0);
-        a11 = __builtin_amdgcn_mfma_f32_32x32x2f32(op1, op1, a11, 0, 0, 0);
-    }
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-        // lower lanes keep block00 / block10 and receive the upper partner's halves of them; upper lanes the same for block01 / block11
-        const auto s0 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a00[v]), __float_as_uint(a01[v]), false, false);
-        const auto s1 = __builtin_amdgcn_permlane32_swap(__float_as_uint(a10[v]), __float_as_uint(a11[v]), false, false);
-        out[8 * (v / 4) + (v % 4)] = __uint_as_float(s0[0]);
-        out[8 * (v / 4) + 4 + (v % 4)] = __uint_as_float(s0[1]);
-        out[32 + 8 * (v / 4) + (v % 4)] = __uint_as_float(s1[0]);
-        out[32 + 8 * (v / 4) + 4 + (v % 4)] = __uint_as_float(s1[1]);
-    }
-}
-// Half of the above: H = 0 gives every lane entries 0..31 of its row, H = 1 entries 32..63 (two MFMA chains and 32 accumulators live
-// at a time instead of four and 64: the fallback of the two-per-wave kernel runs inside its register budget)
+// symmetric), so one swap per accumulator pair hands every lane half of its row: H = 0 gives entries 0..31, H = 1 entries 32..63 (two MFMA
+// chains and 32 accumulators live at a time instead of four and 64: the fallback of the two-per-wave kernel runs inside its register budget)
 template <int NP2, int H> __device__ __forceinline__ void wave_gram64_half(const VecT<float>::v2* y2, float (&out)[32]) {
     typedef float f16v __attribute__((ext_vector_type(16)));
     const f16v z = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
@@ -298,15 +263,6 @@ template <int NP2, int H> __device__ __forceinline__ void wave_gram64_half(const
         out[i] = a;
     }
 }
-template <int NP2> __device__ __forceinline__ void wave_gram64(const VecT<double>::v2* y2, double (&out)[64]) {
-#pragma unroll 1
-    for (int i = 0; i < 64; ++i) {
-        double a = 0;
-#pragma unroll
-        for (int p = 0; p < NP2; ++p) a += y2[p][0] * lane_bcast(y2[p][0], i) + y2[p][1] * lane_bcast(y2[p][1], i);
-        out[i] = a;
-    }
-}
 template <int NP2> __device__ __forceinline__ void wave_gram32(const VecT<double>::v2* y2, double (&out)[32]) {
 #pragma unroll 1
     for (int i = 0; i < 32; ++i) {
@@ -319,67 +275,26 @@ template <int NP2> __device__ __forceinline__ void wave_gram32(const VecT<double
 }
 #endif
 
-#ifndef DM_PRIO
-#define DM_PRIO 1      // s_setprio by phase and load (dm_device_duo.h has the rationale and the measurements); 0: the round-3 kernels
-#endif
-// one character per wavefront: the same rule -- dependent-chain phases above the throughput phases of the SIMD's other wave
-// DM_YPREF: the tree classes' y = L^-T J^T loop requests dof k - 1's records before dof k's arithmetic (EnvSim::substep_post)
-#ifndef DM_YPREF
-#define DM_YPREF 1
-#endif
-// DM_STPREF: dyn_subtree of the one-per-wave tree classes statically unrolled, one member ahead.  OFF: -0.5 % kernel time on the dog, but the compiler contracts the
-// unrolled sums into different FMAs than the rolled loop's -- the dog's 6 committed replay bundles no longer reproduce bit for bit on the GPU (they do on the emulator), and the
-// free-running DM-physics v2 dog leaves its oracle trajectory (tests/test_physics_v2.py).  Every other look-ahead of round 6 keeps the bits.
-#ifndef DM_STPREF
-#define DM_STPREF 0
-#endif
-// DM_PAIRPREF: the self-collision passes read their operands unpredicated, the two-per-wave kernel one pass ahead
-#ifndef DM_PAIRPREF
-#define DM_PAIRPREF 1
-#endif
-// DM_DRPREF: dyn_row (the dense classes' mass-matrix rows) requests pair p + 1's dof records before pair p's dot products; 2: one pair per scheduling region
-#ifndef DM_DRPREF
-#define DM_DRPREF 2
-#endif
-// DM_ELPREF: tree_elim requests pivot q + 1's published entries before pivot q's rank-1 update
-#ifndef DM_ELPREF
-#define DM_ELPREF 1
-#endif
-// DM_TFPREF: tree_fwd requests all its row reads before the first lane select
-#ifndef DM_TFPREF
-#define DM_TFPREF 1
-#endif
-#ifndef DM_YPREF_DENSE_FENCE
-#define DM_YPREF_DENSE_FENCE 1
-#endif
-// DM_LCPREF: tree_load_col reads the momentum records in groups of this many, one group ahead (0: the fenced groups of 8 of rounds 3-5)
-#ifndef DM_LCPREF
-#define DM_LCPREF 4
-#endif
-#ifndef DM_PRIO_ONE_CHOL
-#define DM_PRIO_ONE_CHOL (DM_PRIO ? 1 : 0)
-#define DM_PRIO_ONE_Y (DM_PRIO ? 1 : 0)
-#define DM_PRIO_ONE_BACK (DM_PRIO ? 1 : 0)
-#define DM_PRIO_ONE_KIN (DM_PRIO ? 1 : 0)
-#endif
+// Wave priorities (s_setprio) by phase and load: dm_device_duo.h has the rationale and the measurements.  One character per wavefront: the same rule -- the dependent-chain
+// phases (factorisation and solves, y = L^-1 J^T, back substitution and integration, link kinematics) above the throughput phases of the SIMD's other wave.
 namespace dmk {
 
-// compile-time loop: f(std::integral_constant<int, I>) for I = B .. E - 1 (where the index has to be a template argument)
+constexpr int kPrioChain = 1;      // wave priority of the dependent-chain phases
+constexpr int kLoadColGroup = 4;   // tree_load_col of the PIPE classes reads the momentum records in groups of this many, one group ahead (8 measured slower: profiles/r06_ab_lds_lookahead.json)
+
 // Workgroup -> unit of work (env / env pair), XCD-aware (round 6).  The dispatcher deals consecutive workgroups round-robin over the 8 XCDs, each with its own L2; an env's
 // rows (172 B of pose, 136 B of torque, ...) are not multiples of a cache line, so with unit = blockIdx the line shared by two neighbouring envs was fetched into two L2s
 // and written back from two -- the "1.41 x" HBM traffic of rounds 2-5.  XCD x takes the contiguous units [x G / 8, (x + 1) G / 8): neighbours in memory meet in one L2.
 // Which workgroup steps an env changes nothing in its arithmetic.
-#ifndef DM_XCD_MAP
-#define DM_XCD_MAP 1
-#endif
 #ifdef DM_EMU
 static inline int dm_wg_unit() { return (int)blockIdx.x; }
 #else
 __device__ __forceinline__ int dm_wg_unit() {
     const int b = (int)blockIdx.x, G = (int)gridDim.x;
-    return (DM_XCD_MAP && (G & 7) == 0) ? (b & 7) * (G >> 3) + (b >> 3) : b;
+    return (G & 7) == 0 ? (b & 7) * (G >> 3) + (b >> 3) : b;
 }
 #endif
+// compile-time loop: f(std::integral_constant<int, I>) for I = B .. E - 1 (where the index has to be a template argument)
 template <int B, int E, typename F> DM_DEV void static_for(F&& f) {
     if constexpr (B < E) { f(std::integral_constant<int, B>{}); static_for<B + 1, E>(f); }
 }
@@ -738,41 +653,9 @@ struct EnvSim {
         const int lk = l / G, g = l % G;
         v3 Fs = zero3(), Ns = Fs, h = Fs;
         Real mc = 0, Ic[6] = { 0, 0, 0, 0, 0, 0 };
-        if constexpr (DM_STPREF != 0 && C::TREE && LW == kWave) {
-            // (round 6, second pass; the dog) statically unrolled over the member slots, the next member's records requested before the current one is accumulated --
-            // every lane reads (a lane without a member at this slot its own link), only the accumulation is predicated: the rolled loop below waited for each member's
-            // reads in turn, ten times per call for the root.  Same members in the same order.
-            constexpr int NIT = (NJ + G - 1) / G;
-            const bool lane_on = lk < J;
-            const int lkc = lane_on ? lk : 0;
-            const uint32_t mask = s.mdl.subtree_mask[lkc];
-            const v3 pj = ld3(s.p[lkc]);
-            v3 cm[2], fk2[2], nk2[2]; Real mk2[2], iw2[2][6]; bool on2[2];
-            auto stload = [&](auto ic) {
-                constexpr int it = decltype(ic)::value, sl = it & 1;
-                const int k = lk + g + G * it;
-                const bool on = lane_on && k < J && ((mask >> (k < 32 ? k : 0)) & 1u);
-                const int kc = on ? k : lkc;
-                on2[sl] = on; cm[sl] = ld3(s.com[kc]); fk2[sl] = ld3(s.f[kc]); nk2[sl] = ld3(s.n[kc]); mk2[sl] = s.mdl.mass[kc];
-#pragma unroll
-                for (int q = 0; q < 6; ++q) iw2[sl][q] = s.Iw[kc][q];
-            };
-            stload(std::integral_constant<int, 0>{});
-            static_for<0, NIT>([&](auto ic) {
-                constexpr int it = decltype(ic)::value, sl = it & 1;
-                if (G * it < J) {                                      // (wave-uniform: no slot past the last link)
-                    if constexpr (it + 1 < NIT) stload(std::integral_constant<int, (it + 1 < NIT ? it + 1 : 0)>{});
-                    if (on2[sl]) {
-                        const v3 d = cm[sl] - pj, fk = fk2[sl];
-                        Fs = Fs + fk; Ns = Ns + nk2[sl] + cross(d, fk);
-                        const Real mk = mk2[sl], dd = dot(d, d);
-                        mc += mk; h = h + mk * d;
-                        Ic[0] += iw2[sl][0] + mk * (dd - d.x * d.x); Ic[1] += iw2[sl][1] - mk * d.x * d.y; Ic[2] += iw2[sl][2] - mk * d.x * d.z;
-                        Ic[3] += iw2[sl][3] + mk * (dd - d.y * d.y); Ic[4] += iw2[sl][4] - mk * d.y * d.z; Ic[5] += iw2[sl][5] + mk * (dd - d.z * d.z);
-                    }
-                }
-            });
-        } else
+        // (Statically unrolled over the member slots with the next member's records requested ahead, the dog ran -0.5 % kernel time, but the compiler contracts the
+        // unrolled sums into other FMAs than this loop's: the dog's committed replay bundles no longer reproduced bit for bit on the GPU and the free-running DM-physics v2
+        // dog left its oracle trajectory.  Rejected, profiles/r06_ab_lds_lookahead.json.)
         if (lk < J) {
             const uint32_t mask = s.mdl.subtree_mask[lk];
             const v3 pj = ld3(s.p[lk]);
@@ -815,7 +698,7 @@ struct EnvSim {
         // and whose trip count is the longest chain of the wave.
         const uint32_t lo = s.mdl.chain_lo[dj] & ((k < 31) ? ((2u << k) - 1u) : ~0u), hi = (k < 32) ? 0u : (s.mdl.chain_hi[dj] & ((k < 63) ? ((2u << (k - 32)) - 1u) : ~0u));
         const Real dk = diag_scale * s.mdl.kd[dj];
-        if constexpr (DM_DRPREF != 0 && LW == 32) {      // (two characters per wavefront: 256 registers; the one-per-wave biped kernels run at 128)
+        if constexpr (LW == 32) {      // (two characters per wavefront: 256 registers; the one-per-wave biped kernels run at 128)
         // (round 6) the records of pair p + 1 are requested before the dot products of pair p, and the pair is computed by every lane (only the store is
         // predicated): with the arithmetic sunk under the lanes' `2 p <= k` test -- what the optimizer made of the loop below -- every pair waited for
         // its own three reads behind a branch.  Same values.
@@ -844,7 +727,7 @@ struct EnvSim {
                 v2[c] = v;
             });
             if (2 * p <= k) *reinterpret_cast<R2*>(&row[2 * p]) = v2;
-            if (DM_DRPREF >= 2) DM_SCHED_FENCE();
+            DM_SCHED_FENCE();      // one pair per scheduling region (without the fence: profiles/r06_ab_lds_lookahead.json)
         });
         } else {
 #pragma unroll
@@ -894,10 +777,10 @@ struct EnvSim {
         uint64_t z = 0; DM_OPAQUE_S(z);
         const R4 q0 = *reinterpret_cast<const R4*>(&s.dofrec[lr][0]);
         const R2 q1 = *reinterpret_cast<const R2*>(&s.dofrec[lr][4]);
-#if DM_LCPREF
-        // (round 6) groups of DM_LCPREF records, the next group's reads requested before the current group's dot products: one exposed LDS round
+        if constexpr (C::PIPE) {
+        // (round 6) groups of kLoadColGroup records, the next group's reads requested before the current group's dot products: one exposed LDS round
         // trip for the whole column instead of one per fenced group
-        constexpr int G = DM_LCPREF, NG = (ND + G - 1) / G;        // (the last group may be short: ND = 34)
+        constexpr int G = kLoadColGroup, NG = (ND + G - 1) / G;        // (the last group may be short: ND = 34)
         R4 ra[2][G]; R2 rb[2][G];
         auto grp_load = [&](auto gc) {
             constexpr int g = decltype(gc)::value;
@@ -918,7 +801,7 @@ struct EnvSim {
             });
             DM_SCHED_FENCE();
         });
-#else
+        } else {
         static_for<0, ND>([&](auto ic) {
             constexpr int i = decltype(ic)::value;
             const R4 r0 = *reinterpret_cast<const R4*>(&s.Lt[i * 8]);
@@ -928,7 +811,7 @@ struct EnvSim {
             c2[i >> 1][i & 1] = lane_sel<TP::T.anc[i]>(v, (Real)0, l, z);       // dof i is a descendant of exactly the lanes anc(i)
             if ((i & 7) == 7) DM_SCHED_FENCE();        // keeps the 64 record reads from being issued (and kept live) all at once
         });
-#endif
+        }
         const Real* mo = &s.Lt[lr * 8];
         hd = (l < ND) ? q0[0] * mo[0] + q0[1] * mo[1] + q0[2] * mo[2] + q0[3] * mo[3] + q1[0] * mo[4] + q1[1] * mo[5] + mo[6] : (Real)1;
     }
@@ -1078,7 +961,7 @@ struct EnvSim {
                 if (TP::T.anc[k] != 0 && (ND >= kWave || l < ND)) cbuf[q * CS + l] = x;       // (no lane test when every lane is a dof: a divergent store here makes the optimizer sink the level's arithmetic behind it)
             }
             sync();
-#if DM_ELPREF
+            if constexpr (C::PIPE) {
             // (round 6) the published entries of pivot q + 1 are requested before the rank-1 update of pivot q runs (two register sets by the parity of q): left to
             // itself the scheduler keeps two or three reads in flight, a third of what the LDS latency needs.  Same updates in the same order per entry.
             constexpr int NQ = (NP2 + 1) / 2;
@@ -1115,7 +998,7 @@ struct EnvSim {
                 }
                 if constexpr (q + 1 < W) DM_SCHED_FENCE();
             });
-#else
+            } else {
 #pragma unroll
             for (int q = 0; q < W; ++q) {
                 const int k = TP::T.order[S0 + q];
@@ -1137,7 +1020,7 @@ struct EnvSim {
                     if ((own0 || own1) && (k & 1) && ((TP::T.anc[k] >> (k - 1)) & 1ull)) c2[k >> 1][0] -= lk[q] * cbuf[q * CS + k - 1];
                 }
             }
-#endif
+            }
             tree_elim<V + 1>(c2, hd, dinv, z);
         }
     }
@@ -1161,7 +1044,7 @@ struct EnvSim {
         uint64_t z = 0; DM_OPAQUE_S(z);
         const int lr = l < ND ? l : 0;
         Real r[ND];
-#if DM_TFPREF
+        if constexpr (C::PIPE) {
         // (round 6) all row reads are requested first, the lane selects follow behind one wait: interleaved, each select (an opaque asm) waited for its own read
         static_for<0, ND>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
@@ -1172,12 +1055,12 @@ struct EnvSim {
             constexpr int j = decltype(jc)::value;
             if constexpr (TP::T.desc[j] != 0) r[j] = lane_sel<TP::T.desc[j]>(r[j], (Real)0, l, z);
         });
-#else
+        } else {
         static_for<0, ND>([&](auto jc) {
             constexpr int j = decltype(jc)::value;
             if constexpr (TP::T.desc[j] != 0) r[j] = lane_sel<TP::T.desc[j]>(s.Lt[L::lcb(j) + lr], (Real)0, l, z); else r[j] = 0;
         });
-#endif
+        }
         tree_fwd_lev<TP::T.nlev - 1>(r, x, dinv);
         return x * dinv;
     }
@@ -1587,14 +1470,10 @@ struct EnvSim {
             for (int base = 0; base < nsurv; base += kWave) {
                 const int code = (base + l < nsurv) ? plist[base + l] : -1;
                 v3 x = zero3(), n = zero3(); Real dsc = 0; bool act = false;
-#if DM_PAIRPREF
                 {   // every lane reads (an idle lane pair 0 / 0): with the reads under the lanes' `code >= 0` branch they went out one dependent round trip at a time
                     const PairIn pin = pair_load(code >= 0 ? (code & 0xff) : 0, code >= 0 ? (code >> 8) : 0);
                     act = pair_eval(pin, x, n, dsc) && code >= 0;
                 }
-#else
-                if (code >= 0) act = self_pair(code & 0xff, code >> 8, x, n, dsc);
-#endif
                 const uint64_t mk = wave_ballot(act);
                 if (mk != 0) {
                     const int slot = nc + dm_popc64(mk & lt);
@@ -1681,12 +1560,12 @@ struct EnvSim {
         if (C::OBJ && ball_sg != 0) { mu_row = m.ball_friction; jbl = (Real)ball_sg * dd; jba = (Real)ball_sg * cross(ball_cx - bpos, dd); }
         // y := L^-1 J_l^T in registers (static indices; dof records and L rows are wave-uniform LDS broadcasts)
         R2 y2[NP2X]; Real cvec = 0;
-        dm_setprio<prio_of(DM_PRIO_ONE_Y)>();
+        dm_setprio<prio_of(kPrioChain)>();
         if constexpr (C::TREE) {
             // H = L^T L: y = L^-T J^T runs from the last dof down, against COLUMN k of L (wave-uniform broadcasts); only the pairs that
             // hold a descendant of k are touched (744 multiply-adds per row for dog3d instead of 2 016)
             typedef typename C::Topo TP;
-#if DM_YPREF
+            if constexpr (C::PIPE) {
             // Software-pipelined over the dofs (round 6): the records of dof k - 1 (its axis record, the quads of column k - 1 of L that hold a
             // descendant, the diagonal) are REQUESTED before the arithmetic of dof k, which needs none of them -- the two LDS round trips a dof
             // used to wait for in turn (record -> Jacobian entry, then column -> substitution) now pass behind the previous dof's chain.  Two
@@ -1717,7 +1596,7 @@ struct EnvSim {
             yload(std::integral_constant<int, ND - 1>{});
             static_for<0, ND>([&](auto kkc) {
                 constexpr int k = ND - 1 - decltype(kkc)::value, sl = k & 1;
-                if constexpr (k > 0) { yload(std::integral_constant<int, (k > 0 ? k - 1 : 0)>{}); if (DM_YPREF >= 2) DM_SCHED_FENCE(); }      // (requests first: the waits below then count the older ones only)
+                if constexpr (k > 0) yload(std::integral_constant<int, (k > 0 ? k - 1 : 0)>{});      // (requests first: the waits below then count the older ones only; a scheduling fence behind them measured slower, profiles/r06_ab_lds_lookahead.json)
                 const R4 r0 = pr0[sl], r1 = pr1[sl];
                 Real val = r0[0] * xd.x + r0[1] * xd.y + r0[2] * xd.z + r0[3] * dd.x + r1[0] * dd.y + r1[1] * dd.z;
                 DM_OPAQUE_V(val);
@@ -1740,7 +1619,7 @@ struct EnvSim {
                 y2[k >> 1][k & 1] = yk;
                 DM_SCHED_FENCE();
             });
-#else
+            } else {
 #pragma unroll
             for (int kk = 0; kk < ND; ++kk) {
                 const int k = ND - 1 - kk;
@@ -1770,8 +1649,8 @@ struct EnvSim {
                 y2[k >> 1][k & 1] = yk;
                 DM_SCHED_FENCE();      // the branches of the tree are independent chains: without a fence the scheduler hoists their loads and spills
             }
-#endif
-        } else if constexpr (DM_YPREF != 0 && C::FULLD) {      // (the fallback class of the two-per-wave kernel only: at the one-per-wave biped kernels' 128 registers the second row buffer spills)
+            }
+        } else if constexpr (C::FULLD) {      // (the fallback class of the two-per-wave kernel only: at the one-per-wave biped kernels' 128 registers the second row buffer spills)
         // (round 6) the dense loop software-pipelined like the two-per-wave kernel's: row k + 1 of the factor and its dof record are requested before the
         // accumulation chain of step k -- this is the loop of the 64-lane fallback of a two-per-wave pair, i.e. of the waves a closed-loop launch waits for
         R2 lrp[2][NP2]; R4 rrp[2][2];
@@ -1804,7 +1683,7 @@ struct EnvSim {
                 if (C::FULLD) DM_OPAQUE_V(yk);
             }
             y2[k >> 1][k & 1] = yk;
-            if (DM_YPREF_DENSE_FENCE) DM_SCHED_FENCE();
+            DM_SCHED_FENCE();
         });
         } else {
 #pragma unroll
@@ -1864,14 +1743,6 @@ struct EnvSim {
                 wave_gram32<NP2X>(y2, g);
 #pragma unroll
                 for (int r = 0; r < 32; ++r) arow.set(r, (l == r) ? (Real)0 : g[r] * inv_adiag);
-            } else if (RREG >= kMaxRows && ND <= 34) {
-                // the wide biped class (fallback of the two-per-wave kernel): all 64 rows on the matrix core, straight into registers
-                Real g[64];
-#pragma unroll
-                for (int p = 0; p < NP2X; ++p) DM_OPAQUE_V(y2[p]);
-                wave_gram64<NP2X>(y2, g);
-#pragma unroll
-                for (int r = 0; r < 64; ++r) arow.set(r, (l == r) ? (Real)0 : g[r] * inv_adiag);
             } else if (C::GRAM64) {
                 // narrow row file, Gram on the matrix core: rows 32..63 go to the overflow block ([row][lane]; all of them, the sweep reads
                 // rows < R only)
@@ -1913,11 +1784,9 @@ struct EnvSim {
             int Rv = R, RNv = RN, lv = l;
             constexpr int PFD = C::PFD;             // rows of look-ahead for the overflow block (a ring of PFD + 1 registers)
             Real pre[PFD + 1] = {};
-#if DM_PRIO
             // wave priority by load for the duration of the sweep (see DuoSim::substep_post; dog3d +1.6 %): thresholds at the median / p90 row count of the class
             { constexpr int PLO = (ND > 34) ? 28 : 16, PHI = (ND > 34) ? 40 : 22;
               if (Rv > PHI) dm_setprio<3>(); else if (Rv > PLO) dm_setprio<prio_of(2)>(); else dm_setprio<prio_of(1)>(); }
-#endif
             for (int it = 0; it < m.solver_iters; ++it) {
                 DM_OPAQUE_S(Rv); DM_OPAQUE_S(RNv); DM_OPAQUE_V(lv);
                 uint32_t one = 1; DM_OPAQUE_S(one);
@@ -1944,7 +1813,7 @@ struct EnvSim {
             }
             if (l >= R) lam = 0;
         } else mark(10);
-        dm_setprio<prio_of(DM_PRIO_ONE_BACK)>();
+        dm_setprio<prio_of(kPrioChain)>();
         mark(11);
         if (TAPS && dbg.lambda) { dbg.lambda[(size_t)e * kMaxRows + l] = lam; if (l < 2) dbg.rows[(size_t)e * 2 + l] = s.flg[FLG_NROWS + l]; }
         // delta v = L^-T (Y lambda): transposing wave reduction of y_r[k] lambda_r, dof k's total lands in lane k
@@ -2154,7 +2023,7 @@ struct EnvSim {
         if (reuse_kin) {
             if (l < m.J) { v3 da = gravity_a0() - spd_a0(); st3(s.aj[l], ld3(s.aj[l]) + da); }
             sync();
-        } else if (!kin_done) { dm_setprio<DM_PRIO_ONE_KIN>(); kinematics(s.pose, s.vel, ph == 0 ? spd_a0() : gravity_a0()); dm_setprio<0>(); }      // (kin_done: kin_pre() ran it for this state)
+        } else if (!kin_done) { dm_setprio<kPrioChain>(); kinematics(s.pose, s.vel, ph == 0 ? spd_a0() : gravity_a0()); dm_setprio<0>(); }      // (kin_done: kin_pre() ran it for this state)
         mark(ph == 0 ? 1 : 5);
         dynamics(ph == 0 ? 0 : 1, ph == 0 ? dt : (Real)0);
         mark(ph == 0 ? 2 : 6);
@@ -2177,7 +2046,7 @@ struct EnvSim {
         if (ph == 0) spd_rhs(dt);
         else { if (l < m.D) { Real r = s.tau[l] - s.dofrec[l][7]; if (PERT && pert) r += pert_gen_force(l); s.rhs[l] = r; } sync(); }
         DM_OPAQUE_V(l);
-        dm_setprio<DM_PRIO_ONE_CHOL>();
+        dm_setprio<kPrioChain>();
         if constexpr (C::TREE) tree_solve(s.rhs); else chol_solve(s.rhs);
         dm_setprio<0>();
         DM_OPAQUE_V(l); DM_OPAQUE_V(li);
@@ -3031,18 +2900,9 @@ DM_DEV void reset_goal_env(EnvSim<Real, C, TAPS, LW>& sim, const ModelDev<Real>&
 template <typename Real, typename C> struct StepWaves { static constexpr int value = 1; };
 template <> struct StepWaves<float, ClsBiped> { static constexpr int value = 4; };
 template <> struct StepWaves<float, ClsLarge> { static constexpr int value = 2; };
-#ifndef DM_LT_WAVES
-#define DM_LT_WAVES 2
-#endif
-template <> struct StepWaves<float, ClsLargeTree> { static constexpr int value = DM_LT_WAVES; };
-#ifndef DM_BT_WAVES
-#define DM_BT_WAVES 4
-#endif
-template <> struct StepWaves<float, ClsBipedTree> { static constexpr int value = DM_BT_WAVES; };
-#ifndef DM_OBJ_WAVES
-#define DM_OBJ_WAVES 2
-#endif
-template <> struct StepWaves<float, ClsBipedObj> { static constexpr int value = DM_OBJ_WAVES; };
+template <> struct StepWaves<float, ClsLargeTree> { static constexpr int value = 2; };
+template <> struct StepWaves<float, ClsBipedTree> { static constexpr int value = 4; };
+template <> struct StepWaves<float, ClsBipedObj> { static constexpr int value = 2; };
 #ifdef DM_EMU
 #define DM_WAVES_PER_EU(n)
 #else

@@ -12,46 +12,17 @@
 // routine of dm_device.h on each record in turn (same LDS record layout), so the results do not depend on the pairing.
 #pragma once
 #include "dm_device.h"
-// The borrowed-lane path's Y stash (duo_rows_xd): DM_XD_YSOPQ forms its address inside the path (opaque), DM_XD_YSLANE lays it out [lane][dof] (one address for all entries).
-// Either removes the 13 hoisted row addresses (26 kernel-long VGPRs, spilled in the prologue: 17 MB of scratch stores per 4096-env launch) -- and makes the allocator reload
-// 12-15 other values INSIDE the update loop (dynamics, factor, collision).  Shipped: both 0 (no scratch access on the hot path; tests/test_build_resources.py).
-#ifndef DM_XD_YSOPQ
-#define DM_XD_YSOPQ 0
-#endif
-#ifndef DM_XD_YSUNI
-#define DM_XD_YSUNI 0
-#endif
-#ifndef DM_XD_YSLANE
-#define DM_XD_YSLANE 0
-#endif
 // Wave priorities by phase (round 4; profiles/r04_ab_setprio.json).  Two waves share a SIMD; when both have an instruction ready the arbiter takes the
 // higher priority, then the older.  A wave in a phase with much independent work per lane (dynamics, collision, the Gram MFMA chains) has an instruction
 // ready almost every cycle and delays the ONE ready instruction of a wave that sits in a dependent chain (factorisation columns, substitutions,
-// level-synchronous kinematics, Gauss-Seidel rows) by a few cycles each time.  Raising the chain phases costs the other wave next to nothing -- it fills
-// the gaps -- and shortens the chains: sweep 1 / 2 / 3 by load +3.0 %, the other chain phases at 1 another +3.2 % (same-box A/Bs, outputs bit-identical).
-#if DM_PRIO
-#ifndef DM_PRIO_CHOL
-#define DM_PRIO_CHOL 1      // factorisation + the two triangular solves
-#define DM_PRIO_Y 1         // Y = L^-1 J^T (row lanes)
-#define DM_PRIO_BACK 1      // L^-T (Y lambda), integration
-#define DM_PRIO_KIN 1       // level-synchronous link kinematics
-#endif
-#else
-#define DM_PRIO_CHOL 0
-#define DM_PRIO_Y 0
-#define DM_PRIO_BACK 0
-#define DM_PRIO_KIN 0
-#endif
-#ifndef DM_PRIO_BASE
-#define DM_PRIO_BASE 1      // the sweep: 1, 2 above DM_PRIO_LO rows, 3 above DM_PRIO_HI
-#define DM_PRIO_MID 2
-#endif
-#ifndef DM_PRIO_LO
-#define DM_PRIO_LO 16      // rows of the heavier character of a pair above which the sweep runs at priority 2 / 3 (median pair: 16)
-#define DM_PRIO_HI 22
-#endif
+// level-synchronous kinematics, Gauss-Seidel rows) by a few cycles each time.  Raising the chain phases (kPrioChain) costs the other wave next to nothing -- it
+// fills the gaps -- and shortens the chains: sweep 1 / 2 / 3 by load +3.0 %, the other chain phases at 1 another +3.2 % (same-box A/Bs, outputs bit-identical;
+// against a build that never raises a priority the headline kernel is +4.0 %, the dog +2.8 %).
 
 namespace dmk {
+
+// the sweep of the two-per-wave kernel by load: kPrioSweepBase, kPrioSweepMid above kPrioSweepLo rows of the heavier character of a pair (median pair: 16), 3 above kPrioSweepHi
+constexpr int kPrioSweepBase = 1, kPrioSweepMid = 2, kPrioSweepLo = 16, kPrioSweepHi = 22;
 
 #ifdef DM_EMU
 template <typename T> static inline T half_bcast(T v, int src, int half) { return wave_shfl(v, half * 32 + src); }
@@ -153,17 +124,12 @@ template <int NP2> __device__ __forceinline__ void duo_gram32(const VecT<double>
 // function -- s_swappc -- the values live across the call site were spilled instead, again with reloads on the hot path).  So: Y waits in the pair's overflow block
 // (HBM / L2, 34 coalesced stores and loads) while the sweep runs, the Gram comes off the matrix core one 16-accumulator chain at a time, and the row file holds 48
 // entries (a heavy character of up to 48 rows: 14 contacts; beyond that the pair falls back as before).
-#ifndef DM_DUO_XD
-#define DM_DUO_XD 1
-#endif
 #ifdef DM_EMU
 #define DM_REGION_MARK(n) ((void)0)
 #else
 #define DM_REGION_MARK(n) asm volatile("s_nop " #n)
 #endif
-#ifndef DM_XD_ROWS
-#define DM_XD_ROWS 48
-#endif
+constexpr int kXdRows = 48;      // row file of the borrowed-lane routine (RowFile sizes: 40, 48, 64)
 template <int N, int MASK, int NP2, typename Real> DM_DEV void xd_tr_stage(Real (&w)[NP2], int hl) {
     const bool bit = (hl & MASK) != 0;
 #pragma unroll
@@ -223,11 +189,12 @@ template <int NP2, int X, int Y, typename F> __device__ __forceinline__ void xd_
     });
 }
 #endif
-template <typename Real, bool V2>
+// YFULL: no per-dof `k < D` tests in the y loop (DuoSim::YFULL)
+template <typename Real, bool V2, bool YFULL>
 DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R, int Ra, int Rb, int D, int NL, Real erp, Real friction, Real lim_max_impulse, int solver_iters, Real* ystash) {
     typedef ClsBiped C; typedef Lds<Real, C> L; typedef EnvSim<Real, C, false, 32> Base;
     typedef V3<Real> v3; typedef typename VecT<Real>::v2 R2; typedef typename VecT<Real>::v4 R4;
-    constexpr int ND = C::ND, NP2 = ND / 2, NJ = C::NJ, HW = 32, XR = DM_XD_ROWS;
+    constexpr int ND = C::ND, NP2 = ND / 2, NJ = C::NJ, HW = 32, XR = kXdRows;
     static_assert(XR == 40 || XR == 48 || XR == 64, "RowFile sizes");
     const int half = wl >> 5, hl = wl & 31;
     L& s = rec[half];
@@ -273,10 +240,7 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
     }
     // y := L^-1 J^T against this lane's character (EnvSim::substep_post's dense loop with per-lane record addresses)
     R2 y2[NP2]; Real cvec = 0;
-#if DM_PRIO_Y
-    dm_setprio<DM_PRIO_Y>();
-#endif
-#if DM_YPREF
+    dm_setprio<kPrioChain>();
     // software-pipelined like DuoSim::substep_post's loop (round 6, second pass): the factor row and the dof record of step k + 1 are requested before the
     // accumulation chain of step k (per-lane addresses here: a lane reads the record of the character whose row it holds); one dof per scheduling region
     R2 lr[2][NP2]; R4 rr[2][2];
@@ -291,11 +255,11 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
 #pragma unroll
     for (int k = 0; k < ND; ++k) {
         Real yk = 0;
-        if (k + 1 < ND) { if (DM_DUO_YFULL || k + 1 < D) DM_XD_YLOAD(k + 1) }
-        if (DM_DUO_YFULL || k < D) {
+        if (k + 1 < ND) { if (YFULL || k + 1 < D) DM_XD_YLOAD(k + 1) }
+        if (YFULL || k < D) {
             const R4 r0 = rr[k & 1][0], r1 = rr[k & 1][1];
             Real val = r0[0] * xd.x + r0[1] * xd.y + r0[2] * xd.z + r0[3] * dd.x + r1[0] * dd.y + r1[1] * dd.z;
-            if (DM_DUO_YFULL) DM_OPAQUE_V(val);
+            if (YFULL) DM_OPAQUE_V(val);
             const bool on = (((k < 32) ? ch_lo : ch_hi) >> (k & 31)) & 1u, ng = (((k < 32) ? ng_lo : ng_hi) >> (k & 31)) & 1u;
             const Real raw = on ? (ng ? -val : val) : (Real)0;
             cvec += raw * r1[2];
@@ -306,38 +270,13 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
             Real acc = raw - (acc2[0] + acc2[1]);
             if (k & 1) acc -= lr[k & 1][k >> 1][0] * y2[k >> 1][0];
             yk = acc * lr[k & 1][k >> 1][k & 1];
-            if (DM_DUO_YFULL) DM_OPAQUE_V(yk);
-        }
-        y2[k >> 1][k & 1] = yk;
-        DM_SCHED_FENCE();
-    }
-#undef DM_XD_YLOAD
-#else
-#pragma unroll
-    for (int k = 0; k < ND; ++k) {
-        Real yk = 0;
-        if (k < D) {
-            const R4 r0 = *reinterpret_cast<const R4*>(&sc.dofrec[k][0]), r1 = *reinterpret_cast<const R4*>(&sc.dofrec[k][4]);
-            const Real val = r0[0] * xd.x + r0[1] * xd.y + r0[2] * xd.z + r0[3] * dd.x + r1[0] * dd.y + r1[1] * dd.z;
-            const bool on = (((k < 32) ? ch_lo : ch_hi) >> (k & 31)) & 1u, ng = (((k < 32) ? ng_lo : ng_hi) >> (k & 31)) & 1u;
-            const Real raw = on ? (ng ? -val : val) : (Real)0;
-            cvec += raw * r1[2];
-            R2 acc2 = {(Real)0, (Real)0}, acc3 = acc2;
-            const R2* lrow = reinterpret_cast<const R2*>(&sc.Lt[L::lrow(k)]);
-#pragma unroll
-            for (int p = 0; p < (k >> 1); ++p) { if (p & 1) acc3 += lrow[p] * y2[p]; else acc2 += lrow[p] * y2[p]; }
-            acc2 += acc3;
-            Real acc = raw - (acc2[0] + acc2[1]);
-            if (k & 1) acc -= sc.Lt[L::lrow(k) + k - 1] * y2[k >> 1][0];
-            yk = acc * sc.Lt[L::lrow(k) + k];
+            if (YFULL) DM_OPAQUE_V(yk);
         }
         y2[k >> 1][k & 1] = yk;
         DM_SCHED_FENCE();      // (one dof at a time: unfenced, the scheduler hoists the factor rows of many dofs -- up to 34 registers each -- and spills kernel-long values)
     }
-#endif
-#if DM_PRIO_Y
+#undef DM_XD_YLOAD
     dm_setprio<0>();
-#endif
     const bool is_fric = row >= RNc && row < Rc;
     Real lam = 0;
     if (wave_ballot(row < RNc && (brow - cvec) > 0) != 0) {
@@ -352,11 +291,12 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
         // 32 + j both hold column j of block (X, Y), i.e. (symmetry) the entries of the row held by lane 32 Y + j against the rows of half X.
         RowFile<Real, XR> arow;
         // Y leaves for the pair's overflow block until the sweep is over (coalesced: [dof][lane]); its registers then carry the MFMA operands
-        // (the lane's base address is formed HERE, opaque to the optimizer: hoisted out of the 20-update loop the 13 row addresses beyond the 12-bit offset range were 26 kernel-long
-        // VGPRs of this rare path -- spilled in the prologue once the main path needed the registers: 17 MB of scratch stores per 4096-env launch)
-        { Real* ys = (DM_XD_YSUNI ? dm_uniform_ptr(ystash) : ystash) + (DM_XD_YSLANE ? wl * (2 * NP2) : wl); if (DM_XD_YSOPQ) DM_OPAQUE_V(ys);        // DM_XD_YSLANE: [lane][dof] -- every entry within the 12-bit offset range of ONE address
+        // (Hoisted out of the 20-update loop, the 13 row addresses beyond the 12-bit offset range are 26 kernel-long VGPRs of this rare path, spilled in the prologue: 17 MB of
+        // scratch stores per 4096-env launch.  Forming the address here, opaque to the optimizer, or a [lane][dof] layout with one address for all entries removes them -- and makes
+        // the allocator reload 12-15 other values INSIDE the update loop (dynamics, factor, collision): rejected, no scratch access on the hot path; tests/test_build_resources.py.)
+        { Real* ys = ystash + wl;
 #pragma unroll
-          for (int p = 0; p < NP2; ++p) { ys[DM_XD_YSLANE ? 2 * p : (2 * p) * kWave] = y2[p][0]; ys[DM_XD_YSLANE ? 2 * p + 1 : (2 * p + 1) * kWave] = y2[p][1]; } }
+          for (int p = 0; p < NP2; ++p) { ys[(2 * p) * kWave] = y2[p][0]; ys[(2 * p + 1) * kWave] = y2[p][1]; } }
         xd_gram_operands<NP2>(y2);
         DM_SCHED_FENCE();
         xd_gram_block<NP2, 0, 0>(y2, [&](auto rc, Real g) { constexpr int r = decltype(rc)::value; arow.set(r, g); if (XR - 32 > 31 - r) arow.set(32 + (31 - r), g); });       // half-0 lanes against half 0 (provisionally every lane's; the borrowed rows of a heavy half 1)
@@ -372,9 +312,7 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
         Real lo = 0, hi = is_fric ? (Real)0 : ((row < NL) ? lim_max_impulse : (Real)1e30);
         const uint32_t fmask = (1u << (NL + ncA)) | (1u << (NL + ncB));
         const int xsrc = H ? 0 : HW;                        // borrowed lanes sit in the half that is not H
-#if DM_PRIO
         dm_setprio<3>();
-#endif
         // (a variant with scalar-unit lane masks and one v_readlane on the visits past the light character's rows issued two VALU fewer per visit and measured 3 % slower
         // in the closed loop: profiles/r06_ab_xd_sweep.json)
         for (int it = 0; it < solver_iters; ++it) {
@@ -397,17 +335,13 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
                 }
             });
         }
-#if DM_PRIO
-        dm_setprio<DM_PRIO_BACK>();
-#endif
+        dm_setprio<kPrioChain>();
         if (row >= Rc) lam = 0;
-        { const Real* ys = (DM_XD_YSUNI ? dm_uniform_ptr(ystash) : ystash) + (DM_XD_YSLANE ? wl * (2 * NP2) : wl); if (DM_XD_YSOPQ) DM_OPAQUE_V(ys);
+        { const Real* ys = ystash + wl;
 #pragma unroll
-          for (int p = 0; p < NP2; ++p) { y2[p][0] = ys[DM_XD_YSLANE ? 2 * p : (2 * p) * kWave]; y2[p][1] = ys[DM_XD_YSLANE ? 2 * p + 1 : (2 * p + 1) * kWave]; } }
+          for (int p = 0; p < NP2; ++p) { y2[p][0] = ys[(2 * p) * kWave]; y2[p][1] = ys[(2 * p + 1) * kWave]; } }
     } else {
-#if DM_PRIO_BACK
-        dm_setprio<DM_PRIO_BACK>();
-#endif
+        dm_setprio<kPrioChain>();
     }
     // Y lambda per dof and character: the rows in their character's own half, then the borrowed lanes' rows (reduced in the half they sit in, handed across once)
     {
@@ -430,21 +364,10 @@ DM_DEV void duo_rows_xd(Lds<Real, ClsBiped>* rec, int wl, Real h, int nc, int R,
     }
 }
 
-#ifndef DM_DUO_YPMAX
-#define DM_DUO_YPMAX 7
-#endif
-#ifndef DM_DUO_WIDE_FALLBACK
-#define DM_DUO_WIDE_FALLBACK 0
-#endif
-// the fallback class of a pair that leaves the two-per-wave routine: the biped class's GRAM64 variant; for biped + free body the one-per-wave class itself
-template <typename CC> struct DuoFallback {
-#if DM_DUO_WIDE_FALLBACK
-    typedef ClsBipedWide type;
-#else
-    typedef ClsBipedFb type;
-#endif
-};
-template <> struct DuoFallback<ClsBipedObj> { typedef ClsBipedObj type; };
+// the fallback class of a pair that leaves the two-per-wave routine: the biped class's GRAM64 variant, with the y loop of the kernel it serves (YFULL); for biped + free body
+// the one-per-wave class itself
+template <typename CC, bool YFULL> struct DuoFallback { typedef ClsBipedFb<YFULL> type; };
+template <bool YFULL> struct DuoFallback<ClsBipedObj, YFULL> { typedef ClsBipedObj type; };
 // CC: ClsBiped, or (round 6) ClsBipedObj -- biped + one free rigid sphere per character (dribble_amp's ball): three more register pairs of y per row lane, the ball's
 // contacts in the half's own slots, its velocity change by six half-wave sums, its integration by lane 0 of the half
 template <typename Real, bool TAPS, typename CC = ClsBiped>
@@ -452,11 +375,14 @@ struct DuoSim {
     typedef CC C;
     typedef Lds<Real, C> L;
     typedef EnvSim<Real, C, TAPS, 32> Base;
-    // Fallback class for a pair with a heavily contacted character.  DM_DUO_WIDE_FALLBACK = 1 selects ClsBipedWide (all 64 rows of A
-    // in VGPRs, 64-row Gram on the matrix core): +8..13 % closed-loop throughput under an untrained policy, but its 64-register row
-    // file pushes 10 kernel-long-lived values of the two-per-wave kernel into scratch (40 B / lane, +7.5 MB of HBM traffic per launch),
-    // so the default keeps the narrow class (rows 32..63 in the HBM / L2 overflow block, requested two rows ahead): no scratch at all.
-    typedef typename DuoFallback<CC>::type FallbackCls;
+    // The y = L^-1 J^T loops of this kernel (substep_post, duo_rows_xd, the 64-lane fallback class) run without per-dof `k < D` tests: every launch has D == ND (dm_host.cpp
+    // checks it).  Except the profiling / tap instantiation, which keeps the loops of rounds 3-5 WITH the tests: without them the fp32 kernel spills 321 VGPRs instead of 56
+    // (the taps' own live values) and its phase shares say nothing about the production kernel any more; its fp64 parity build runs the same loops.
+    static constexpr bool YFULL = !TAPS;
+    // Fallback class for a pair with a heavily contacted character: the narrow class (rows 32..63 in the HBM / L2 overflow block, requested two rows ahead), no scratch at all.
+    // (A class with all 64 rows of A in VGPRs and the 64-row Gram on the matrix core: +8..13 % closed-loop throughput under an untrained policy, but its 64-register row file
+    // pushes 10 kernel-long-lived values of the two-per-wave kernel into scratch -- 40 B / lane, +7.5 MB of HBM traffic per launch: rejected, profiles/r05_ab_fallback_rowfile.json.)
+    typedef typename DuoFallback<CC, YFULL>::type FallbackCls;
     typedef EnvSim<Real, FallbackCls, TAPS, kWave> Single;
     typedef Lds<Real, FallbackCls> WideRec;
     static_assert(sizeof(WideRec) == sizeof(L), "the wide class must share the LDS record layout");
@@ -472,19 +398,11 @@ struct DuoSim {
     int pair_code[PP];
     DM_DEV DuoSim(const ModelDev<Real>& m_, L* rec_, int wl_) : m(m_), rec(rec_), wl(wl_), half(wl_ >> 5), hl(wl_ & 31), b(m_, rec_[wl_ >> 5], wl_ & 31), s(rec_[wl_ >> 5]) {}
     DM_DEV void sync() const { __syncthreads(); }
-    // the priority of the phases between the dependent chains.  DM_PRIO_LATE > 0: a wave that has left the 32-row path in this launch (borrowed lanes or the 64-lane routine) is one
-    // the launch will wait for -- a one-round launch lasts as long as its slowest wave -- and keeps the raised level in the throughput phases too
-#ifndef DM_PRIO_LATE
-#define DM_PRIO_LATE 2      // same-box A/B, closed-loop spinkick: 1: -0.9 %, 2: -1.6 %, 3: -1.4 % step time; open loop +-0; the chain phases at 3 too: no further gain and +1.1 % open loop (profiles/r06_ab_lane_borrowing.json)
-#endif
+    // the priority of the phases between the dependent chains.  A wave that has left the 32-row path in this launch (borrowed lanes or the 64-lane routine) is one
+    // the launch will wait for -- a one-round launch lasts as long as its slowest wave -- and keeps a raised level (PRIO_LATE) in the throughput phases too
+    static constexpr int PRIO_LATE = 2;      // same-box A/B, closed-loop spinkick: 1: -0.9 %, 2: -1.6 %, 3: -1.4 % step time; open loop +-0; the chain phases at 3 too: no further gain and +1.1 % open loop (profiles/r06_ab_lane_borrowing.json)
     int late = 0;
-    DM_DEV void prio_low() const {
-#if DM_PRIO_LATE
-        if (late) dm_setprio<DM_PRIO_LATE>(); else dm_setprio<0>();
-#else
-        dm_setprio<0>();
-#endif
-    }
+    DM_DEV void prio_low() const { if (late) dm_setprio<PRIO_LATE>(); else dm_setprio<0>(); }
     DM_DEV Real& Lx(int r, int c) const { return s.Lt[L::lrow(r) + c]; }
     static DM_DEV v3 zero3() { return mk3((Real)0, (Real)0, (Real)0); }
 
@@ -864,9 +782,7 @@ _Pragma("unroll") \
         sync();
         b.integrate(h);
         sync();
-#if DM_PRIO_BACK
         prio_low();
-#endif
     }
 
     // ------------------------------------------------------------------ rigid-body substep, constraint part
@@ -939,25 +855,17 @@ _Pragma("unroll") \
         int nc = V2 ? half_bcast(nact, 0, half) : nact;          // (uniform per character by construction; under V2 the broadcast tells the compiler)
         // ---- self collision: lane = link pair (three passes of 32); active pairs take the slots the ground left, in pair order
         const int npair_passes = (m.NPAIR + HW - 1) / HW;
-#if DM_PAIRPREF
         // (round 6, second pass) the operands of pass q + 1 are requested before pass q is evaluated, by every lane (an idle lane reads pair 0 / 0): under the lanes'
         // `code >= 0` branch the reads of a pass went out one dependent round trip at a time
         typename Base::PairIn pin[2];
         pin[0] = b.pair_load(pair_code[0] >= 0 ? (pair_code[0] & 0xff) : 0, pair_code[0] >= 0 ? (pair_code[0] >> 8) : 0);
-#endif
 #pragma unroll
         for (int q = 0; q < PP; ++q) {
-#if DM_PAIRPREF
             if (q + 1 < PP) { const int cn = pair_code[q + 1 < PP ? q + 1 : 0]; pin[(q + 1) & 1] = b.pair_load(cn >= 0 ? (cn & 0xff) : 0, cn >= 0 ? (cn >> 8) : 0); }
-#endif
             if (q < npair_passes) {
                 const int code = pair_code[q];
                 v3 x = zero3(), n = zero3(); Real dsc = 0; bool act = false;
-#if DM_PAIRPREF
                 act = b.pair_eval(pin[q & 1], x, n, dsc) && code >= 0;
-#else
-                if (code >= 0) act = b.self_pair(code & 0xff, code >> 8, x, n, dsc);
-#endif
                 const uint64_t mk64 = wave_ballot(act);
                 if (mk64 != 0) {
                     const uint32_t mk = (uint32_t)(mk64 >> (half * 32));
@@ -1031,17 +939,16 @@ _Pragma("unroll") \
         // y := L^-1 J^T, software-pipelined: the factor row and the dof record of step k+1 are requested (LDS broadcasts) before
         // the dependent accumulation chain of step k runs, so their latency hides behind it (two register buffers, static parity)
         R2 y2[NP2X]; Real cvec = 0;
-#if DM_DUO_YFULL
+        dm_setprio<kPrioChain>();
+        if constexpr (YFULL) {
         // (round 6, second pass) No per-dof `k < D` tests: every launch of this kernel has D == ND (dm_host.cpp checks it; the 31 row lanes per character assume
         // it).  As wave-uniform branches around the requests they made the compiler wait for everything in flight (lgkmcnt(0)) at every dof -- the requests of
         // dof k + 1 included, i.e. the pipelining was undone -- and cost two v_readlane of a spilled mask pair per dof.  The look-ahead set holds the dof record
         // and the first YP pairs of row k + 1; the pairs beyond are requested at the top of their own step and consumed last, behind the chain over the first
         // YP (both sets whole: 68 registers, which the kernel does not have -- kernel-long values went to scratch with reloads inside the update loop).
-        constexpr int YP = DM_DUO_YPMAX;
+        // (YP = 5 / 7 / 9 and a scheduling fence behind the requests of every dof: profiles/r06_ab_lds_lookahead.json.)
+        constexpr int YP = 7;
         R2 lr[2][YP], ltl[NP2 > YP ? NP2 - YP : 1]; R4 rr[2][2];
-#if DM_PRIO_Y
-        dm_setprio<DM_PRIO_Y>();
-#endif
         auto yhead = [&](auto kc) {
             constexpr int k = decltype(kc)::value;
             rr[k & 1][0] = *reinterpret_cast<const R4*>(&s.dofrec[k][0]); rr[k & 1][1] = *reinterpret_cast<const R4*>(&s.dofrec[k][4]);
@@ -1054,7 +961,6 @@ _Pragma("unroll") \
             const R2* lrow_ = reinterpret_cast<const R2*>(&s.Lt[L::lrow(k)]);
             static_for<YP, (k >> 1) + 1>([&](auto pc) { constexpr int p = decltype(pc)::value; ltl[p - YP] = lrow_[p]; });      // the row's tail, if any
             if constexpr (k + 1 < ND) yhead(std::integral_constant<int, (k + 1 < ND ? k + 1 : 0)>{});
-            if (DM_DUO_YFULL >= 2) DM_SCHED_FENCE();
             const R4 r0 = rr[k & 1][0], r1 = rr[k & 1][1];
             Real val = r0[0] * xd.x + r0[1] * xd.y + r0[2] * xd.z + r0[3] * dd.x + r1[0] * dd.y + r1[1] * dd.z;
             DM_OPAQUE_V(val);        // (evaluated where it stands, by every lane: see EnvSim::substep_post's tree loop)
@@ -1075,11 +981,8 @@ _Pragma("unroll") \
             y2[k >> 1][k & 1] = yk;
             DM_SCHED_FENCE();       // (one dof per scheduling region)
         });
-#else
+        } else {
         R2 lr[2][NP2]; R4 rr[2][2];
-#if DM_PRIO_Y
-        dm_setprio<DM_PRIO_Y>();
-#endif
 #define DM_DUO_YLOAD(k)                                                                                       \
         {                                                                                                     \
             rr[(k) & 1][0] = *reinterpret_cast<const R4*>(&s.dofrec[(k)][0]);                                  \
@@ -1109,10 +1012,8 @@ _Pragma("unroll") \
             y2[k >> 1][k & 1] = yk;
         }
 #undef DM_DUO_YLOAD
-#endif
-#if DM_PRIO_Y
+        }
         prio_low();
-#endif
         if constexpr (C::OBJ) {
             // the free body's block of the mass matrix is diagonal: its rows of Y = M^-1/2 J^T are a scaling; J v* gains its share
             cvec += dot(jbl, bvs) + dot(jba, bws);
@@ -1169,9 +1070,7 @@ _Pragma("unroll") \
             // phases, and a pair with more rows than the median (16) -- the waves a one-round launch waits for -- outranks a lighter one.
             // The priority is per wave and lasts until it is set back after the sweep.  (Keeping it through all phases, thresholds 10..24,
             // or 3 for every wave measured the same or less; a never-raised control build measured +-0.)
-#if DM_PRIO
-            if (Rv > DM_PRIO_HI) dm_setprio<3>(); else if (Rv > DM_PRIO_LO) dm_setprio<DM_PRIO_MID>(); else dm_setprio<DM_PRIO_BASE>();
-#endif
+            if (Rv > kPrioSweepHi) dm_setprio<3>(); else if (Rv > kPrioSweepLo) dm_setprio<kPrioSweepMid>(); else dm_setprio<kPrioSweepBase>();
             for (int it = 0; it < m.solver_iters; ++it) {
                 uint32_t one = 1u;
                 DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one);
@@ -1180,15 +1079,9 @@ _Pragma("unroll") \
             }
 #undef DM_DUO_PGS_BLK
 #undef DM_DUO_PGS_ROW
-#if DM_PRIO
-            dm_setprio<DM_PRIO_BACK>();
-#endif
+            dm_setprio<kPrioChain>();
             if (hl >= R) lam = 0;
-        } else { b.mark(10);
-#if DM_PRIO_BACK
-            dm_setprio<DM_PRIO_BACK>();
-#endif
-        }
+        } else { b.mark(10); dm_setprio<kPrioChain>(); }
         b.mark(11);
         if constexpr (C::OBJ) {
             // delta v of the free body = M^-1/2 (Y_b lambda): six sums over the half; then semi-implicit Euler with the exponential map, by lane 0 of the half
@@ -1238,13 +1131,9 @@ _Pragma("unroll") \
                 if (hl < m.J) { v3 da = b.gravity_a0() - b.spd_a0(); st3(s.aj[hl], ld3(s.aj[hl]) + da); }
                 sync();
             } else if (!(kin_done && ph == 0)) {
-#if DM_PRIO_KIN
-                dm_setprio<DM_PRIO_KIN>();
-#endif
+                dm_setprio<kPrioChain>();
                 b.kinematics(s.pose, s.vel, ph == 0 ? b.spd_a0() : b.gravity_a0());      // (ph 0: EnvSim::kin_pre ran it)
-#if DM_PRIO_KIN
                 prio_low();
-#endif
             }
             b.mark(ph == 0 ? 1 : 5);
             dynamics(ph == 0 ? 0 : 1, ph == 0 ? rdt : (Real)0);
@@ -1255,13 +1144,9 @@ _Pragma("unroll") \
                 sync();
             } else { for (int k = hl; k < D; k += HW) { Real r = s.tau[k] - s.dofrec[k][7]; if (PERT && pert) r += b.pert_gen_force(k); s.rhs[k] = r; } sync(); }
             DM_OPAQUE_V(hl); DM_OPAQUE_V(b.l);
-#if DM_PRIO_CHOL
-            dm_setprio<DM_PRIO_CHOL>();
-#endif
+            dm_setprio<kPrioChain>();
             chol_solve(s.rhs);
-#if DM_PRIO_CHOL
             prio_low();
-#endif
             DM_OPAQUE_V(hl); DM_OPAQUE_V(b.l); DM_OPAQUE_V(b.li);
             if (ph == 0) {
                 b.mark(3);
@@ -1271,18 +1156,16 @@ _Pragma("unroll") \
             } else {
                 bool rows_done = substep_post<V2>(h, V2 ? manif_pair + (size_t)half * m.J * MF_STRIDE : nullptr);
                 if (!rows_done) {
-#if DM_PRIO_LATE
                     if (!PERT) late = 1;          // (plain instantiation only: in the AMP / v2 kernels the flag's scalar register cost 1 % of the open-loop rate of every AMP scene)
-#endif
-                    // more than 32 rows somewhere in the pair (the contact slots are stored, FLG_NROWS says how many).  One such character, at most DM_XD_ROWS rows, and at most 64
+                    // more than 32 rows somewhere in the pair (the contact slots are stored, FLG_NROWS says how many).  One such character, at most kXdRows rows, and at most 64
                     // rows together: the pair stays in this instruction stream on borrowed lanes (round 6)
                     const int R_ = s.flg[FLG_NROWS], nc_ = (R_ - m.NL) / 3;
                     const int Ra_ = lane_bcast(R_, 0), Rb_ = lane_bcast(R_, 32);
-                    if constexpr (DM_DUO_XD && !C::OBJ) {      // (the borrowed-lane routine knows no free body: such a pair of biped + ball characters takes the 64-lane routine)
-                        if (aovf_pair && Ra_ + Rb_ <= 2 * HW && Ra_ <= DM_XD_ROWS && Rb_ <= DM_XD_ROWS) {
+                    if constexpr (!C::OBJ) {      // (the borrowed-lane routine knows no free body: such a pair of biped + ball characters takes the 64-lane routine)
+                        if (aovf_pair && Ra_ + Rb_ <= 2 * HW && Ra_ <= kXdRows && Rb_ <= kXdRows) {
                             b.mark(8);
                             DM_REGION_MARK(13);             // (s_nop 13 / s_nop 14 bracket the borrowed-lane region in the disassembly: tests/test_build_resources.py holds every scratch access of the update loop to it)
-                            duo_rows_xd<Real, V2>(rec, wl, h, nc_, R_, Ra_, Rb_, D, m.NL, m.erp, m.friction, m.lim_max_impulse, m.solver_iters, aovf_pair);
+                            duo_rows_xd<Real, V2, YFULL>(rec, wl, h, nc_, R_, Ra_, Rb_, D, m.NL, m.erp, m.friction, m.lim_max_impulse, m.solver_iters, aovf_pair);
                             load_cands();                   // (the candidate tables come back from L2 instead of living -- spilled in every wave's prologue -- across the region)
                             DM_REGION_MARK(14);
                             b.mark(11);                     // (profiling build: rows + Gram + sweep of such a substep count as "sub.PGS")

@@ -2,6 +2,16 @@
 //     hipcc ... -DDM_TU_F64=<0|1> -DDM_TU_ID=<family> -c dm_kernels.cpp -o k_<prec>_<family>.o
 // (deepmimic_amd/csrc/Makefile); the emulator build (tests/emu) compiles it once with -DDM_TU_ALL.
 // The kernels themselves live in dm_device.h / dm_device_duo.h; this file only holds their launchers (dm_launch.h).
+// Loop variants and tuning constants are properties of the kernel classes and constants in the headers (dm_types.h: PIPE, ClsBipedFb<YFULL>; DuoSim::YFULL; kPrio*, kXdRows, ...):
+// a -D that changed the body of shared inline code would give one template instantiation different bodies in different objects.  The retired knobs fail the build.
+#if defined(DM_YPREF) || defined(DM_LCPREF) || defined(DM_ELPREF) || defined(DM_TFPREF) || defined(DM_STPREF) || defined(DM_PAIRPREF) || defined(DM_DRPREF) || \
+    defined(DM_YPREF_DENSE_FENCE) || defined(DM_DUO_YFULL) || defined(DM_DUO_YPMAX) || defined(DM_DUO_XD) || defined(DM_DUO_WIDE_FALLBACK) || defined(DM_XD_ROWS) || \
+    defined(DM_XD_YSOPQ) || defined(DM_XD_YSUNI) || defined(DM_XD_YSLANE) || defined(DM_XCD_MAP) || defined(DM_FB_RREG) || defined(DM_FB_PRIO) || defined(DM_DOG_RREG) || \
+    defined(DM_LT_WAVES) || defined(DM_BT_WAVES) || defined(DM_OBJ_WAVES) || defined(DM_PRIO) || defined(DM_PRIO_CHOL) || defined(DM_PRIO_Y) || defined(DM_PRIO_BACK) || \
+    defined(DM_PRIO_KIN) || defined(DM_PRIO_ONE_CHOL) || defined(DM_PRIO_ONE_Y) || defined(DM_PRIO_ONE_BACK) || defined(DM_PRIO_ONE_KIN) || defined(DM_PRIO_BASE) || \
+    defined(DM_PRIO_MID) || defined(DM_PRIO_LO) || defined(DM_PRIO_HI) || defined(DM_PRIO_LATE)
+#error "retired -D knob: edit the constant or the class property in dm_types.h / dm_device.h / dm_device_duo.h instead (one body per template instantiation)"
+#endif
 #include "dm_launch.h"
 #include "dm_device_duo.h"
 

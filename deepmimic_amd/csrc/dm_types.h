@@ -31,27 +31,20 @@ struct ClsBiped {      // humanoid3d: 15 links, 34 dof, 43 pose dims, <= 64 grou
     static constexpr bool PGS_MASKSEL = false;      // sweep: lane r takes its new lambda by v_cmp + v_cndmask (MASKSEL classes: a select on a constant SGPR lane mask)
     static constexpr bool GRAM64 = false;   // 64-row Gram matrix by the readlane loop (128-VGPR budget of the one-per-wave kernel)
     static constexpr int PFD = 2;           // look-ahead of the sweep into the overflow block of A, rows
-    static constexpr bool FULLD = false;    // every character stepped through this class has exactly ND dofs (the fallback class of the two-per-wave kernel: dm_host.cpp checks D == ND before a duo launch)
+    static constexpr bool FULLD = false;    // every character stepped through this class has exactly ND dofs (ClsBipedFb<true>, the fallback class of the two-per-wave kernel: dm_host.cpp checks D == ND before a duo launch)
     static constexpr int PRIO_FLOOR = 0;    // lowest wave priority inside substep_post (s_setprio; the fallback class of the two-per-wave kernel raises it)
 };
-// the same character class with all 64 rows of A in VGPRs: the instantiation the two-per-wave kernel falls back to for a pair with a
-// heavily contacted character (256-VGPR budget there; identical LDS record layout)
-struct ClsBipedWide : ClsBiped { static constexpr int RREG = 64, RREG_PLAIN = 64; };
-// the fallback class of the two-per-wave kernel by default: the narrow row file (rows 32..63 of A in the HBM / L2 overflow block), but
-// the Gram matrix of a character with more than 32 rows still comes off the matrix core (64 accumulators live for the Gram only)
-#ifndef DM_FB_RREG
-#define DM_FB_RREG 32
-#endif
-// DM_FB_PRIO: a pair on the fallback is a wave the launch will wait for (one round of waves lasts as long as its slowest): it runs the two 64-lane passes above its SIMD mate throughout
-// DM_DUO_YFULL: the y = L^-1 J^T loops of the two-per-wave kernel (DuoSim::substep_post, duo_rows_xd, the 64-lane fallback class) without the per-dof `k < D` tests
-// (every duo launch has D == ND)
-#ifndef DM_DUO_YFULL
-#define DM_DUO_YFULL 1
-#endif
-#ifndef DM_FB_PRIO
-#define DM_FB_PRIO 0
-#endif
-struct ClsBipedFb : ClsBiped { static constexpr int RREG = DM_FB_RREG, RREG_PLAIN = DM_FB_RREG; static constexpr bool GRAM64 = true; static constexpr int PRIO_FLOOR = DM_FB_PRIO; static constexpr bool FULLD = DM_DUO_YFULL != 0; };   // (a look-ahead of 6 rows instead of 2 measured no gain)
+// the fallback class of the two-per-wave kernel, for a pair with a heavily contacted character (256-VGPR budget there; identical LDS record layout): the narrow row file (rows
+// 32..63 of A in the HBM / L2 overflow block), but the Gram matrix of a character with more than 32 rows still comes off the matrix core (64 accumulators live for the Gram only).
+// (40 / 48 / all 64 rows in VGPRs measured +0.2 ... +0.9 % slower, 5-8 spilled VGPRs: profiles/r05_ab_fallback_rowfile.json.)
+// YFULL: the y = L^-1 J^T loop without the per-dof `k < D` tests, as in the kernel that falls back to it (DuoSim::YFULL; every duo launch has D == ND).
+template <bool YFULL>
+struct ClsBipedFb : ClsBiped {
+    static constexpr int RREG = 32, RREG_PLAIN = 32;
+    static constexpr bool GRAM64 = true;      // (a look-ahead of 6 rows instead of 2 measured no gain)
+    static constexpr int PRIO_FLOOR = 0;      // (> 0: a pair on the fallback is a wave the launch will wait for -- one round of waves lasts as long as its slowest -- and would run the two 64-lane passes above its SIMD mate throughout)
+    static constexpr bool FULLD = YFULL;
+};
 // the biped class plus one free rigid sphere in the world (`--scene dribble_amp`: the ball, scenes/SceneDribbleAMP.cpp:398-420); one
 // character per wavefront, 2 waves / SIMD (the ball's Jacobian columns ride in six more VGPRs per row lane)
 struct ClsBipedObj : ClsBiped { static constexpr bool OBJ = true; static constexpr bool PGS_MASKSEL = true; };     // (same-box A/B of the mask select: -3.6 %; ClsBiped at 128 VGPRs: +2.8 %, SGPR pressure)
@@ -131,15 +124,15 @@ struct TopoHumanoid3d {
 };
 // the biped class on humanoid3d's compiled topology (one character per wavefront: `wave_packing 1`; the two-per-wave kernel keeps the dense
 // factor -- its 31 row lanes per character have no room for the root-translation columns, which an L^T L elimination finishes LAST)
-struct ClsBipedTree : ClsBiped { static constexpr bool TREE = true; typedef TopoHumanoid3d Topo; };
+// PIPE: the tree loops with the LDS look-ahead of round 6 (tree_load_col, tree_elim, tree_fwd, the y = L^-T J^T loop of EnvSim::substep_post: the next step's records requested
+// into a second register set before the current step's arithmetic).  Not here: the one-per-wave humanoid runs at 4 waves / SIMD = 128 VGPRs and already spills (208 / 395 VGPRs,
+// plain / AMP); the second register set, built for the dog at 256 VGPRs, adds 35 more.  This class keeps the loops of rounds 3-5.
+struct ClsBipedTree : ClsBiped { static constexpr bool TREE = true; static constexpr bool PIPE = false; typedef TopoHumanoid3d Topo; };
 // the large class on dog3d's compiled topology
 // rows of A in VGPRs for the plain imitate instantiation of the compiled dog3d class.  25.6 % of the dog's substeps have more than 32 rows, 1.8 % more
 // than 48, none more than 56 (profiles/r03_rows_hist.txt); 48 / 56 / 64 all compile to 0 scratch at 2 waves / SIMD (239 / 247 / 256 VGPRs) and measure
 // +3.3 / +3.7 / +3.4 % over 32 on one box with bit-identical outputs (profiles/r04_ab_dog_rreg.json).  The AMP / v2 instantiations keep 32 (48 spills there).
-#ifndef DM_DOG_RREG
-#define DM_DOG_RREG 56
-#endif
-struct ClsLargeTree : ClsLarge { static constexpr int RREG_PLAIN = DM_DOG_RREG; static constexpr bool TREE = true; typedef TopoDog3d Topo; static constexpr bool GRAM64 = true; static constexpr bool BROAD = true; static constexpr bool PGS_MASKSEL = true; };   // (more than 32 rows: Gram on the matrix core too)
+struct ClsLargeTree : ClsLarge { static constexpr int RREG_PLAIN = 56; static constexpr bool TREE = true; static constexpr bool PIPE = true; typedef TopoDog3d Topo; static constexpr bool GRAM64 = true; static constexpr bool BROAD = true; static constexpr bool PGS_MASKSEL = true; };   // (more than 32 rows: Gram on the matrix core too)
 
 // link_info word: parent+1 [0:4] | jtype [5:7] | depth [8:11] | pose_off [12:18] | dof_off [19:25] | arot_ident 26 | brot_ident 27 | is_ee 28 | fall 29
 #define DM_LI_PARENT(i) (((i) & 31) - 1)

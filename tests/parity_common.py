@@ -199,14 +199,26 @@ def rollout_compare(name, precision, lib_path, steps, t0=0.0, open_loop_on_devic
     return np.array(dr), np.array(ds), flags_ok
 
 
-def batch_rollout_compare(name, precision, lib_path, steps, t0s, wave_packing=0, lifts=None, stats=None):
+def batch_rollout_compare(name, precision, lib_path, steps, t0s, wave_packing=0, lifts=None, stats=None, step=None):
     """Free-running open-loop rollout of len(t0s) envs in one batch (no debug taps armed, so the production step kernel of
     the requested wave packing runs); every env is compared with its own oracle.  Returns per-env max |reward diff|, max
-    |state diff| and whether every terminate / valid flag agreed."""
+    |state diff| and whether every terminate / valid flag agreed.
+
+    step: callable(env) -> the outputs of one open-loop control step; default `env.step(None, DT, 20, open_loop=True)`, which neither
+    ends an episode early nor resets.  A `step` given here is taken to run with auto_reset and end_early on and to report what the env
+    holds AFTER it (dm_probe 3 + query(), the only route to the tap instantiation of the two-per-wave kernel): the oracle then stops
+    at the update at which its episode is over and mirrors the device's reset with the same counter-based draw
+    (auto_reset_rollout_compare), so every step of every env stays a comparison -- of the first observation of the new episode where
+    one began.  stats["steps"]: per control step the counters below and the mask of the envs that were reset in it."""
+    from deepmimic_amd import streams
     t = model.load_asset(name)
     n = len(t0s)
-    env = BatchEnv(t, n, precision=precision, lib_path=lib_path, wave_packing=wave_packing)
+    seed = 0
+    env = BatchEnv(t, n, precision=precision, lib_path=lib_path, wave_packing=wave_packing, seed=seed)
     env.reset(kin_times=np.array(t0s, dtype=np.float64), max_times=np.inf)
+    if step is not None:
+        ep = env.get_state()["flags"][:, 2].astype(np.int64)        # episode counter the NEXT reset will draw with
+        tmin, tmax = float(t.cfg.time_lim_min), float(t.cfg.time_lim_max)
     oracles = []
     for e, t0 in enumerate(t0s):
         o = Oracle(t); o.reset(t0); oracles.append(o)
@@ -218,18 +230,25 @@ def batch_rollout_compare(name, precision, lib_path, steps, t0s, wave_packing=0,
             p, v = o.sim_state(); p[1] += lifts[e]; o.set_sim_state(p, v)
         env.set_state(pose=pose)
     dr, ds, ok = np.zeros(n), np.zeros(n), True
+    per_step = []
     for k in range(steps):
-        out = env.step(None, DT, 20, open_loop=True)
+        out = env.step(None, DT, 20, open_loop=True) if step is None else step(env)
+        reset = np.zeros(n, dtype=bool)
         for e, o in enumerate(oracles):
             kp, _, _ = o.kin_state()
             o.set_action(o.pose_to_action(kp))
-            for u in range(20):
-                o.update(DT)
+            o.control_step(20, DT, end_early=step is not None)
+            if step is not None and (o.is_episode_end() or not o.check_valid_episode()):
+                mt = tmin + (tmax - tmin) * streams.reset_rand01(seed, e, int(ep[e]), 1) if tmax > tmin else tmax
+                o.reset(o.duration * streams.reset_rand01(seed, e, int(ep[e]), 0), mt)
+                ep[e] += 1; reset[e] = True
             dr[e] = max(dr[e], abs(float(out["reward"][e]) - o.calc_reward()))
             ds[e] = max(ds[e], np.abs(out["state"][e] - o.record_state()).max())
             ok &= int(out["terminate"][e]) == o.check_terminate() and int(out["valid"][e]) == int(o.check_valid_episode())
+        if stats is not None:
+            per_step.append(dict(fallback=env.debug("fallback"), borrowed=env.debug("borrowed"), reset=reset))
     if stats is not None:          # per env: substeps on the 64-lane fallback | on borrowed lanes (two-per-wave kernel)
-        stats["fallback"] = env.debug("fallback"); stats["borrowed"] = env.debug("borrowed")
+        stats["fallback"] = per_step[-1]["fallback"]; stats["borrowed"] = per_step[-1]["borrowed"]; stats["steps"] = per_step
     return dr, ds, ok
 
 

@@ -1,20 +1,20 @@
 """Every kernel family of libdm_hip.so against the oracle, with the family that ran reported by the library.
 
 libdm_hip.so is one object per (precision, kernel family): DM_FAMILY_<id> of deepmimic_amd/csrc/dm_kernels.cpp, KIDS of its Makefile, each with
-code generation flags of its own (NOLICM_IDS, SCHED_IDS) and some with other source (NOPIPE_IDS: the tree classes' loops without the LDS look-ahead;
-tapflag: family 2's y = L^-1 J^T loops with their per-dof tests).  dm_get_debug "family" names the family of the last step launch (dm_host.cpp
-step_family), so each row of FAMILIES below asserts that its configuration ran the object it claims before it compares that object with the oracle.
+code generation flags of its own (NOLICM_IDS, SCHED_IDS) and all from one source: which loops a kernel runs is a property of its class and template
+arguments (ClsBipedTree::PIPE = false: the tree loops without the LDS look-ahead; DuoSim::YFULL = false in the tap instantiation, family 2: the
+y = L^-1 J^T loops with their per-dof tests), so the emulator library runs, per class and per kernel, the loops of the GPU objects.  dm_get_debug
+"family" names the family of the last step launch (dm_host.cpp step_family), so each row of FAMILIES below asserts that its configuration ran the
+object it claims before it compares that object with the oracle.
 
 * ledger (CPU): FAMILIES covers every step family of the Makefile and dm_kernels.cpp, FAMILY11 every class of the reset / query / probe family;
 * dispatch (CPU, emulator): each row's configuration reports its id, and so do the documented one-per-wavefront fallbacks;
-* loop variants (CPU, emulator): tests/emu builds the whole library with NOPIPE_IDS' flags and with tapflag's, which the default emulator build
-  never compiles; the tree rows, the dense class and the two-per-wave tap family run there against the oracle;
+* build rules (CPU): no compile rule of either Makefile passes a -D that could fork a template between objects, no header keeps an overridable knob;
+* loop variants (CPU, emulator): the tree rows, the dense class and the two-per-wave tap family -- through both of its beyond-32-rows paths -- against the oracle;
 * parity (GPU): each row x {f32, f64} on the HIP objects, sampled envs re-synchronised from the device before every control step.
 """
-import fcntl
 import os
 import re
-import subprocess
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -59,7 +59,7 @@ DENSE, BTREE = (("DM_TREE", "0"),), (("DM_TREE_BIPED", "1"),)
 FAMILIES = {
     0: Row(HUM, 10, f32_wc=(6.0e-06, 3.0e-03), note="two-per-wave plain"),
     1: Row(HUM, 10, rot_fail=True, f32_wc=(6.0e-06, 3.0e-03), note="two-per-wave AMP instantiation"),
-    2: Row(HUM, 10, kind="probe3", f32_wc=(9.3e-06, 3.5e-03), note="two-per-wave taps (dm_probe 3), DM_DUO_YFULL=0 on the GPU"),
+    2: Row(HUM, 10, kind="probe3", f32_wc=(9.3e-06, 3.5e-03), note="two-per-wave taps (dm_probe 3): y loops with their per-dof tests"),
     3: Row(HUM, 9, f32_wc=(9.9e-06, 2.4e-03), note="ClsBiped plain: odd N falls back to one per wave"),
     4: Row(HUM, 9, rot_fail=True, f32_wc=(9.9e-06, 2.4e-03), note="ClsBiped AMP instantiation"),
     5: Row(HUM, 9, taps=True, f32_wc=(9.8e-06, 2.4e-03), note="ClsBiped taps"),
@@ -71,13 +71,13 @@ FAMILIES = {
     12: Row(DOG, 9, f32_wc=(2.9e-05, 2.6e-03), note="ClsLargeTree plain"),
     13: Row(DOG, 9, rot_fail=True, f32_wc=(2.9e-05, 2.6e-03), note="ClsLargeTree AMP instantiation"),
     14: Row(DOG, 9, taps=True, f32_wc=(2.9e-05, 2.6e-03), note="ClsLargeTree taps"),
-    15: Row(HUM, 9, env=BTREE, f32_wc=(7.6e-06, 4.2e-03), note="ClsBipedTree plain (NOPIPE loops on the GPU)"),
-    16: Row(HUM, 9, env=BTREE, rot_fail=True, f32_wc=(7.6e-06, 4.2e-03), note="ClsBipedTree AMP instantiation (NOPIPE)"),
-    17: Row(HUM, 9, env=BTREE, taps=True, f32_wc=(7.6e-06, 4.2e-03), note="ClsBipedTree taps (NOPIPE)"),
+    15: Row(HUM, 9, env=BTREE, f32_wc=(7.6e-06, 4.2e-03), note="ClsBipedTree plain (tree loops without the look-ahead)"),
+    16: Row(HUM, 9, env=BTREE, rot_fail=True, f32_wc=(7.6e-06, 4.2e-03), note="ClsBipedTree AMP instantiation (no look-ahead)"),
+    17: Row(HUM, 9, env=BTREE, taps=True, f32_wc=(7.6e-06, 4.2e-03), note="ClsBipedTree taps (no look-ahead)"),
     18: Row(HUM, 9, physics=2, f32_wc=(7.0e-06, 2.5e-03), note="ClsBiped DM-physics v2"),
     19: Row(DOG, 9, env=DENSE, physics=2, f32_wc=(4.8e-05, 5.2e-02), note="ClsLarge DM-physics v2"),
     20: Row(DOG, 9, physics=2, f32_wc=(7.5e-06, 3.5e-03), note="ClsLargeTree DM-physics v2"),
-    21: Row(HUM, 9, env=BTREE, physics=2, f32_wc=(4.6e-06, 2.7e-03), note="ClsBipedTree DM-physics v2 (NOPIPE)"),
+    21: Row(HUM, 9, env=BTREE, physics=2, f32_wc=(4.6e-06, 2.7e-03), note="ClsBipedTree DM-physics v2 (no look-ahead)"),
     22: Row(HUM, 10, physics=2, f32_wc=(5.8e-06, 4.1e-03), note="two-per-wave DM-physics v2"),
     23: Row(DRIBBLE, 9, kind="goal", pack=1, physics=2, note="ClsBipedObj DM-physics v2"),
     24: Row(DRIBBLE, 10, kind="goal", pack=2, note="two-per-wave biped + free body"),
@@ -236,20 +236,36 @@ def test_ledger_covers_every_family():
     assert expert == {c for c, what in FAMILY11.items() if "expert" in what}
 
 
-def test_variant_flags_match_product_makefile():
-    """the emulator's loop-variant builds compile exactly the -D flags the product Makefile gives NOPIPE_IDS and family 2 (tapflag)"""
-    prod = open(os.path.join(CSRC, "Makefile")).read()
-    m = re.search(r"\$\(filter \$\(1\),\$\(NOPIPE_IDS\)\),([^,)]*)", prod)
-    assert m, "licmflag no longer names NOPIPE_IDS"
-    nopipe = sorted(m.group(1).split())
-    m = re.search(r"^tapflag\s*=\s*\$\(if \$\(filter \$\(1\),(\d+)\),([^,)]*),", prod, re.M)
-    assert m, "tapflag changed shape"
-    assert m.group(1) == "2"
-    yfull = sorted(m.group(2).split())
-    assert nopipe and all(f.startswith("-D") for f in nopipe) and yfull == ["-DDM_DUO_YFULL=0"]
-    assert sorted(_makefile_var(os.path.join(EMU, "Makefile"), "NOPIPE_FLAGS")) == nopipe
-    assert sorted(_makefile_var(os.path.join(EMU, "Makefile"), "YFULL0_FLAGS")) == yfull
-    assert sorted(int(i) for i in _makefile_var(os.path.join(CSRC, "Makefile"), "NOPIPE_IDS")) == [15, 16, 17, 21]
+def _recipe_lines(path):
+    """the recipe lines (commands) of a Makefile, continuation lines joined"""
+    txt = open(path).read().replace("\\\n", " ")
+    return [l for l in txt.split("\n") if l.startswith("\t")]
+
+
+def test_no_rule_defines_a_source_variant():
+    """One template instantiation has one body in every object of the GPU library and of the emulator library: no compile rule of either Makefile passes
+    a -D other than the translation unit's own (precision, family) and the emulator switch, nor a variable that could smuggle one in per family; no
+    header under deepmimic_amd/csrc keeps an `#ifndef DM_X / #define DM_X` default for a -D to override (DM_HD, the host / device qualifier, apart)."""
+    allowed = {"DM_EMU", "DM_TU_F64", "DM_TU_ID"}
+    for mk in (os.path.join(CSRC, "Makefile"), os.path.join(EMU, "Makefile")):
+        txt = open(mk).read()
+        recipes = _recipe_lines(mk)
+        assert any("dm_kernels.cpp" in l for l in recipes), mk
+        # every variable and function a recipe expands is looked through too (HIPFLAGS, CXXFLAGS, licmflag, ...)
+        names = set(re.findall(r"\$\((?:call )?(\w+)", "\n".join(recipes)))
+        defs = [m.group(2) for m in re.finditer(r"^(\w+)\s*[?:+]?=(.*)$", txt, re.M) if m.group(1) in names]
+        for text in recipes + defs:
+            for d in re.findall(r"(?<![\w-])-D\s*(\w+)", text):
+                assert d in allowed, "%s passes -D%s: make it a class property or a constant (dm_types.h)" % (os.path.relpath(mk, ROOT), d)
+    for f in sorted(os.listdir(CSRC)):
+        if not f.endswith((".h", ".cpp")):
+            continue
+        src = open(os.path.join(CSRC, f)).read()
+        knobs = [n for n in re.findall(r"^\s*#\s*ifndef\s+(DM_\w+)", src, re.M) if n != "DM_HD" and re.search(r"^\s*#\s*define\s+%s\b" % n, src, re.M)]
+        assert not knobs, "%s keeps overridable knobs %s" % (f, knobs)
+    for var in ("NOLICM_IDS", "SCHED_IDS"):
+        ids = {int(i) for i in _makefile_var(os.path.join(CSRC, "Makefile"), var)}
+        assert ids <= {int(k) for k in _makefile_var(os.path.join(CSRC, "Makefile"), "KIDS")}, var
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- dispatch (CPU)
@@ -330,24 +346,6 @@ def test_dispatch_fallbacks(emu_lib, monkeypatch, case, want):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- loop variants (CPU)
-def _build_variant(target, lib):
-    """tests/emu `make <target>` under a lock on its Makefile: pytest-xdist workers share the build directory"""
-    with open(os.path.join(EMU, "Makefile")) as lk:
-        fcntl.flock(lk, fcntl.LOCK_EX)
-        subprocess.check_call(["make", "-s", "-C", EMU, target], stderr=subprocess.DEVNULL)
-    return os.path.join(EMU, lib)
-
-
-@pytest.fixture(scope="module")
-def emu_nopipe(oracle_built):
-    return _build_variant("nopipe", "libdm_emu_nopipe.so")
-
-
-@pytest.fixture(scope="module")
-def emu_yfull0(oracle_built):
-    return _build_variant("yfull0", "libdm_emu_yfull0.so")
-
-
 def _emu_row(fid, lib, monkeypatch, steps=3):
     row = FAMILIES[fid]
     m = run_row(fid, 64, lib, monkeypatch, n=(2 if row.n % 2 == 0 else 3), steps=steps)
@@ -365,22 +363,45 @@ def test_dense_large_class_emulator(emu_lib, monkeypatch, fid):
 
 
 @pytest.mark.parametrize("fid", [15, 16, 17, 21, 12, 13, 14, 20])
-def test_tree_rows_on_nopipe_loops(emu_nopipe, monkeypatch, fid):
-    """the tree classes with the look-ahead switched off (NOPIPE_IDS' flags): the loops the GPU objects of families 15, 16, 17, 21 run"""
-    _emu_row(fid, emu_nopipe, monkeypatch)
+def test_tree_rows_on_their_own_loops(emu_lib, monkeypatch, fid):
+    """the tree classes, each on the loops its GPU objects run: ClsBipedTree (15, 16, 17, 21) without the LDS look-ahead, ClsLargeTree (12, 13, 14, 20)
+    with it.  (The two other combinations -- the dog without the look-ahead, the humanoid with it -- are in no library any more.)"""
+    _emu_row(fid, emu_lib, monkeypatch)
     if fid == 17:
         monkeypatch.setenv("DM_TREE_BIPED", "1")
-        pc.check_dynamics(HUM, 64, emu_nopipe, rtol=1e-11)
-        pc.check_substep(HUM, 64, emu_nopipe, tol_vel=1e-8, tol_pose=1e-10, lift=-0.03)
+        pc.check_dynamics(HUM, 64, emu_lib, rtol=1e-11)
+        pc.check_substep(HUM, 64, emu_lib, tol_vel=1e-8, tol_pose=1e-10, lift=-0.03)
 
 
-def test_duo_on_yfull0_loops(emu_yfull0, monkeypatch):
-    """DM_DUO_YFULL=0 (family 2's y loops on the GPU): the profiled two-per-wave control step and an A2 rollout of the two-per-wave kernel"""
-    _emu_row(2, emu_yfull0, monkeypatch)
-    dr, ds, ok, _ = pc.action_rollout_compare(HUM, 64, emu_yfull0, 2, "A2", [0.0, 0.37], wave_packing=2)
+def test_duo_tap_family_on_its_own_loops(emu_lib, monkeypatch):
+    """family 2, the tap instantiation of the two-per-wave kernel (DuoSim::YFULL = false: y loops with their per-dof tests): the profiled control step, and the
+    heavy-contact rollout stepped by dm_probe 3 + query() -- the only route to that instantiation -- through the borrowed-lane path and the 64-lane fallback.
+    The A2 rollout runs family 0 on family 0's own loops.
+    dm_probe 3 steps with auto_reset and end_early on, the oracles mirror the resets (parity_common.batch_rollout_compare).  Under it the lifts -0.08 / -0.3 end the
+    lifted characters' episodes inside the first control step (a fall contact): both paths run, but what is compared of those two envs in that step is the
+    first observation of their next episode.  So a second set, found on the emulator: -0.07 on envs 0, 1 and 3 puts pair 0 (two heavy characters, more than 64
+    rows together) on the 64-lane fallback and pair 1 (env 3 beyond 32 rows beside a light partner) on borrowed lanes in the first control step, and no episode ends:
+    all four envs are compared with their oracles through and after those substeps."""
+    _emu_row(2, emu_lib, monkeypatch)
+    dr, ds, ok, _ = pc.action_rollout_compare(HUM, 64, emu_lib, 2, "A2", [0.0, 0.37], wave_packing=2)
     assert ok and dr.max() < 1e-6 and ds.max() < 1e-5, (dr, ds)
-    dr, ds, ok = pc.batch_rollout_compare(HUM, 64, emu_yfull0, steps=2, t0s=[0.0, 0.4, 0.2, 0.6], wave_packing=2, lifts=[-0.08, 0.0, 0.0, -0.3])
-    assert dr.max() < 1e-6 and ds.max() < 1e-4, (dr, ds)       # (heavy contact: the pairs through the borrowed-lane path and the 64-lane fallback)
+    for lifts, live in (([-0.08, 0.0, 0.0, -0.3], False), ([-0.07, -0.07, 0.0, -0.07], True)):
+        fam, st = [], {}
+
+        def probe3(env):
+            env.probe(3, pc.DT)
+            fam.append(_family(env))
+            return env.query()
+        dr, ds, ok = pc.batch_rollout_compare(HUM, 64, emu_lib, steps=2, t0s=[0.0, 0.4, 0.2, 0.6], wave_packing=2, lifts=lifts, stats=st, step=probe3)
+        first = st["steps"][0]
+        print("lifts %s: per step borrowed %s fallback %s resets %s, reward diff %s state diff %s" % (
+            lifts, [x["borrowed"].tolist() for x in st["steps"]], [x["fallback"].tolist() for x in st["steps"]], [x["reset"].tolist() for x in st["steps"]], dr, ds))
+        assert fam == [2, 2], fam
+        assert first["borrowed"].max() > 0 and first["fallback"].max() > 0, st["steps"]         # both beyond-32-rows paths, on these loops
+        if live:
+            assert not any(x["reset"].any() for x in st["steps"]), st["steps"]
+            assert (first["fallback"][:2] > 0).all() and (first["borrowed"][2:] > 0).all(), st["steps"]
+        assert ok and dr.max() < 1e-6 and ds.max() < 1e-4, (dr, ds)       # (heavy contact: the pairs through the borrowed-lane path and the 64-lane fallback)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- parity (GPU)

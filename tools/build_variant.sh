@@ -1,6 +1,8 @@
 #!/bin/bash
 # build one kernel family with extra compiler flags and link it with the default objects into a variant library (for same-box A/B):
 #   tools/build_variant.sh <tag> <family id> <extra hipcc flags...>   ->  deepmimic_amd/csrc/libdm_hip_<tag>.so
+# The extra flags are code-generation options (-mllvm ...).  A SOURCE variant is made by editing the constant or class property in dm_types.h / dm_device*.h
+# and building the whole library: a -D that changes shared inline code would fork a template between objects, and dm_kernels.cpp refuses the retired knob names.
 set -e
 cd "$(dirname "$0")/../deepmimic_amd/csrc"
 TAG=$1; ID=$2; shift 2
