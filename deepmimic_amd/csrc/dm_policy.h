@@ -28,6 +28,7 @@ struct PolicyDev {
     const uint16_t* wfs;              // k_policy_fused: the fragments of layers 1 and 2 in the order each of its four waves consumes them (null: widths it is not compiled for)
 };
 
+struct GateDev;
 struct PolicyIO {
     const float* states;   // M x S fp32 (RecordState of every env)
     uint16_t* s16;         // M x K1 bf16: normalised, clipped, zero-padded observations (written by k_policy_prep)
@@ -45,6 +46,24 @@ struct PolicyIO {
     float exp_rate; int32_t* exp_flags;
     unsigned long long* prof;   // measurement only (DM_POLICY_PROBE=2): per workgroup 8 timestamps (s_memtime of wave 0 at the phase boundaries)
     int probe;             // measurement only (DM_POLICY_PROBE): 1 = k_policy_fused re-reads block 0 of its weight stream forever (the stream served by the vector L1: what the L2 path costs)
+    // gated actor (GateDev below), appended so that no member above moves: what k_policy_gate leaves for the GATED epilogues of layers 1 and 2, fp32 row-major
+    const float *gsig0, *gbeta0;   // M x H1: sigma_0 = 2 sigmoid(.), beta_0
+    const float *gsig1, *gbeta1;   // M x H2
+    const GateDev* gate;           // device copy of the context's GateDev: k_policy_fused<.., true> reads the gate's first layers through it
+};
+
+// The gate of learning/nets/fc_2layers_gated_1024units.py: a small net on the NORMALISED GOAL (the last G input columns, input_tfs[-1]) that scales and
+// shifts the pre-activations of both hidden layers,
+//   c = relu(Wc xg + bc)  (G -> GC);   e_i = relu(We_i c + be_i)  (GC -> GH);   beta_i = Wb_i e_i + bb_i,  sigma_i = 2 sigmoid(Ws_i e_i + bs_i)  (GH -> H_i)
+//   h_i = relu(sigma_i * (W_i h_(i-1) + b_i) + beta_i)                                                     i = 0, 1  (layers 1 and 2)
+// Rounding points (mirrored by deepmimic_amd/policy.py reference_forward(bf16=True)): xg, c, e_i are bf16 where they become MFMA operands (xg IS the goal block
+// of the bf16 observations the main net reads); sigma, beta, acc + b and the gated pre-activation fmaf(sigma, acc + b, beta) stay fp32 (one rounding, written as
+// fmaf so that device and emulator agree); h1, h2 are bf16 as in the plain actor, whose products, accumulation order and rounding points the main layers keep.
+// Packed weights as pack_weights lays them out (dm_policy_host.h); KG = G rounded up to 32, GC and GH multiples of 32.
+struct GateDev {
+    int G, KG, GC, GH;
+    const uint16_t *wcp, *wep[2], *wbp[2], *wsp[2];     // gate_common/0/dense; gate{i}/0/dense, gate{i}/dense (beta), gate{i}/dense_1 (sigma pre-activation)
+    const float *bc, *be[2], *bb[2], *bs[2];
 };
 
 static inline uint16_t f32_to_bf16_host(float f) { uint32_t u; memcpy(&u, &f, 4); if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0; u += 0x7fffu + ((u >> 16) & 1u); return (uint16_t)(u >> 16); }
@@ -148,12 +167,100 @@ __global__ void __launch_bounds__(64) k_policy_prep(PolicyDev p, PolicyIO io) {
     }
 }
 
+// sigma = 2 sigmoid(z) in fp32.  EXACTLY 1 at z = 0 (expf(-0) = 1, 2 / 2), exactly 2 from z = +128 on (expf(-z) <= 2^-184 is 0 in fp32, and far below half
+// an ulp of 1 from z = 17 on: 2 / 1) and exactly 0 from z = -128 down (expf(-z) >= 2^184 overflows to +inf, 2 / inf); any 2 / (1 + exp(-z)) on v_exp_f32 is.
+DMP_DEV float gate_sigma(float z) { return 2.0f / (1.0f + expf(-z)); }
+
+struct alignas(16) f32x4_rec { float x, y, z, w; };
+
+// one 16-feature x 16-row tile of a gate layer, products transposed as in k_policy_fused (weight fragment = A operand, activations = B operand from LDS in
+// [k-step][batch tile][lane] order): the lane holds features 16 ft + 4 (l >> 4) + r of batch row l & 15; k-steps ascending from a zero accumulator
+DMP_DEV f32x4 gate_tile(const uint16_t* wp, int KS, int ft, const bf16x8* in, int bt, int l) {
+    f32x4 acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = 0.0f;
+    // the fragments of four k-steps are requested in one batch (one L2 latency per four, not per one: the gate's time is all latency)
+    for (int k0 = 0; k0 < KS; k0 += 4) {
+        bf16x8 f[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) f[u] = *reinterpret_cast<const bf16x8*>(wp + (((size_t)ft * KS + (k0 + u < KS ? k0 + u : KS - 1)) * 64 + l) * 8);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) if (k0 + u < KS) acc = mfma16(f[u], in[((k0 + u) * 2 + bt) * 64 + l], acc);
+    }
+    return acc;
+}
+// bias + ReLU + bf16 of such a tile into the B-fragment order of the next gate layer (k = 16 ft + 4 g + r): 8 contiguous bytes per lane
+DMP_DEV void gate_store(bf16x8* out, int ft, int bt, int c, int g, const f32x4& acc, const float* bias) {
+    const int f0 = 16 * ft + 4 * g;
+    store4(reinterpret_cast<uint16_t*>(out) + ((size_t)(((ft >> 1) * 2 + bt) * 64 + c + 16 * (2 * (ft & 1) + (g >> 1)))) * 8 + 4 * (g & 1),
+           fmaxf(acc[0] + bias[f0], 0.0f), fmaxf(acc[1] + bias[f0 + 1], 0.0f), fmaxf(acc[2] + bias[f0 + 2], 0.0f), fmaxf(acc[3] + bias[f0 + 3], 0.0f));
+}
+
+// c (into sc) and e_0, e_1 (into se, 4 * 2 * 64 records each) of 32 rows from their goal block sx, all in B-fragment order [k-step][batch tile][lane]; called by
+// every thread of a four-wave workgroup behind the barrier that completed sx, returns behind the barrier that completes se.  Shared by k_policy_gate and
+// k_policy_fused<.., true>, so that both form the same c and e_i bit for bit.
+DMP_DEV void gate_hidden(const GateDev& gd, const bf16x8* sx, bf16x8* sc, bf16x8* se, int w, int l, int c, int g) {
+    for (int u = w; u < gd.GC / 8; u += 4) gate_store(sc, u >> 1, u & 1, c, g, gate_tile(gd.wcp, gd.KG / 32, u >> 1, sx, u & 1, l), gd.bc);
+    __syncthreads();
+    const int ne = gd.GH / 8;                             // units per e_i
+    for (int u = w; u < 2 * ne; u += 4) { const int i = u / ne, v = u % ne; gate_store(se + i * 512, v >> 1, v & 1, c, g, gate_tile(gd.wep[i], gd.GC / 32, v >> 1, sc, v & 1, l), gd.be[i]); }
+    __syncthreads();
+}
+
+// one gated 16-feature tile of k_policy_fused for one batch tile: sigma and beta from two k-steps each (GH = 64) with the gate-projection fragments as A and e_i
+// as B, then relu(fmaf(sigma, acc + b, beta)) -> bf16 -> 8 bytes of the next layer's B fragment.  fbs / fbb: the lane's four scale / bias-projection biases, fp32
+// bits carried in a 16-byte slot of the weight stream
+DMP_DEV void gated_tile_store(uint16_t* dst, const bf16x8& fs0, const bf16x8& fs1, const bf16x8& fb0, const bf16x8& fb1, const bf16x8& fbs, const bf16x8& fbb,
+                              const bf16x8& e0, const bf16x8& e1, const f32x4& acc, const float* mb) {
+    f32x4 z;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) z[r] = 0.0f;
+    const f32x4 as = mfma16(fs1, e1, mfma16(fs0, e0, z)), ab = mfma16(fb1, e1, mfma16(fb0, e0, z));
+    float bs[4], bb[4];
+    __builtin_memcpy(bs, &fbs, 16); __builtin_memcpy(bb, &fbb, 16);
+    store4(dst, fmaxf(fmaf(gate_sigma(as[0] + bs[0]), acc[0] + mb[0], ab[0] + bb[0]), 0.0f), fmaxf(fmaf(gate_sigma(as[1] + bs[1]), acc[1] + mb[1], ab[1] + bb[1]), 0.0f),
+           fmaxf(fmaf(gate_sigma(as[2] + bs[2]), acc[2] + mb[2], ab[2] + bb[2]), 0.0f), fmaxf(fmaf(gate_sigma(as[3] + bs[3]), acc[3] + mb[3], ab[3] + bb[3]), 0.0f));
+}
+
+// The gate of the per-layer route: a workgroup of four wavefronts takes 32 batch rows from the goal block of the bf16 observations (k_policy_prep ran before:
+// normalised, clipped, NaN already -s_clip) through c, e_0, e_1 in LDS to sigma_i / beta_i [M x H_i] fp32 in the scratch buffers of PolicyIO.  The units of
+// work of a stage (feature tile x batch tile) are dealt round-robin to the waves; every count is a multiple of 4 (GC, GH multiples of 32, H_i of 64), so all
+// waves make the same number of trips (the emulator's mfma16 is a workgroup-wide exchange).  Limits (checked at create): G <= 128, GC <= 256, GH <= 128.
+__global__ void __launch_bounds__(256) k_policy_gate(PolicyDev p, PolicyIO io, GateDev gd) {
+    constexpr int R = 32;
+    __shared__ bf16x8 sx[4 * 2 * 64], sc[8 * 2 * 64], se[2][4 * 2 * 64];
+    const int t = threadIdx.x, w = t >> 6, l = t & 63, c = l & 15, g = l >> 4;
+    const int row0 = (int)blockIdx.x * R;
+    {
+        uint16_t* const sxh = reinterpret_cast<uint16_t*>(sx);
+        const int m = t & 31, row = row0 + m < io.M ? row0 + m : io.M - 1;
+        const uint16_t* const src = io.s16 + (size_t)row * p.K1 + (p.S - gd.G);
+        for (int k = t >> 5; k < gd.KG; k += 8)
+            sxh[((size_t)((k >> 5) * 2 + (m >> 4)) * 64 + (m & 15) + 16 * ((k & 31) >> 3)) * 8 + (k & 7)] = k < gd.G ? src[k] : (uint16_t)0;
+    }
+    __syncthreads();
+    gate_hidden(gd, sx, sc, se[0], w, l, c, g);
+    for (int i = 0; i < 2; ++i) {
+        const int H = i ? p.H2 : p.H1;
+        float* const sig = const_cast<float*>(i ? io.gsig1 : io.gsig0); float* const beta = const_cast<float*>(i ? io.gbeta1 : io.gbeta0);
+        for (int u = w; u < H / 8; u += 4) {
+            const int ft = u >> 1, bt = u & 1, f0 = 16 * ft + 4 * g, row = row0 + 16 * bt + c;
+            const f32x4 ab = gate_tile(gd.wbp[i], gd.GH / 32, ft, se[i], bt, l), as = gate_tile(gd.wsp[i], gd.GH / 32, ft, se[i], bt, l);
+            f32x4_rec vb, vs;
+            vb.x = ab[0] + gd.bb[i][f0]; vb.y = ab[1] + gd.bb[i][f0 + 1]; vb.z = ab[2] + gd.bb[i][f0 + 2]; vb.w = ab[3] + gd.bb[i][f0 + 3];
+            vs.x = gate_sigma(as[0] + gd.bs[i][f0]); vs.y = gate_sigma(as[1] + gd.bs[i][f0 + 1]); vs.z = gate_sigma(as[2] + gd.bs[i][f0 + 2]); vs.w = gate_sigma(as[3] + gd.bs[i][f0 + 3]);
+            if (row < io.M) { *reinterpret_cast<f32x4_rec*>(beta + (size_t)row * H + f0) = vb; *reinterpret_cast<f32x4_rec*>(sig + (size_t)row * H + f0) = vs; }
+        }
+    }
+}
+
 // MODE 0: layer 1 (bf16 normalised observations; ReLU; bf16 out)             K = K1, N = H1
 // MODE 1: layer 2 (bf16 in; ReLU; bf16 out)                                  K = H1, N = H2
 // MODE 2: layer 3 (bf16 in; Gaussian head + un-normalise; fp32 actions)      K = H2, N = N3
 // The k loop is software-pipelined by hand: the A / B fragments of step ks + 1 are requested before the MFMAs of step ks issue
 // (two register sets), so one wave keeps its matrix core busy while the next 16-byte-per-lane reads are in flight.
-template <int MODE, int MT, int NT>
+// GATED (MODE 0 / 1): the epilogue reads sigma / beta of its elements from the scratch k_policy_gate filled: relu(fmaf(sigma, acc + b, beta)).
+template <int MODE, int MT, int NT, bool GATED = false>
 __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
     const int l = threadIdx.x, c = l & 15, g = l >> 4;
     const int K = (MODE == 0) ? p.K1 : (MODE == 1 ? p.H1 : p.H2);
@@ -227,6 +334,7 @@ __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
     if (MODE != 2) {
         const float* bias = (MODE == 0) ? p.b1 : p.b2;
         uint16_t* out = (MODE == 0) ? io.h1 : io.h2;
+        const float* const gsig = (MODE == 0) ? io.gsig0 : io.gsig1; const float* const gbeta = (MODE == 0) ? io.gbeta0 : io.gbeta1;
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int col = (nt0 + j) * 16 + c; const float bc = bias[col];
@@ -235,7 +343,8 @@ __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const int row = row0 + 16 * i + 4 * g + r;
-                    if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(acc[i][j][r] + bc, 0.0f));
+                    if (GATED) { if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(fmaf(gsig[(size_t)row * N + col], acc[i][j][r] + bc, gbeta[(size_t)row * N + col]), 0.0f)); }
+                    else if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(acc[i][j][r] + bc, 0.0f));
                 }
         }
     } else {
@@ -289,7 +398,8 @@ __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
 // BM = 64 halves the tile height (each wave 32 x 64) for batches too small to fill the chip with 128 x 128 tiles.
 // (Folding k_policy_prep into MODE 0 -- fp32 observations normalised on the way from the register stage to LDS -- was measured slower:
 // 44.9 / 98.8 us against 41.2 / 83.4 us at 4096 / 16384 rows; eight scalar loads per chunk cost more than the 4 us kernel they replace.)
-template <int MODE, int BM>
+// GATED: as in k_policy_layer.
+template <int MODE, int BM, bool GATED = false>
 __global__ void __launch_bounds__(256) k_policy_gemm(PolicyDev p, PolicyIO io) {
     constexpr int BN = 128, MT = BM / 32, AF = BM / 16;      // MT: row fragments per wave, AF: row fragments per workgroup
     __shared__ bf16x8 sA[2][AF][64];
@@ -354,6 +464,7 @@ __global__ void __launch_bounds__(256) k_policy_gemm(PolicyDev p, PolicyIO io) {
 #undef DMP_LSTORE
     const float* bias = (MODE == 0) ? p.b1 : p.b2;
     uint16_t* out = (MODE == 0) ? io.h1 : io.h2;
+    const float* const gsig = (MODE == 0) ? io.gsig0 : io.gsig1; const float* const gbeta = (MODE == 0) ? io.gbeta0 : io.gbeta1;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
         const int col = (nt0 + 4 * wc + j) * 16 + c; const float bc = bias[col];
@@ -362,7 +473,8 @@ __global__ void __launch_bounds__(256) k_policy_gemm(PolicyDev p, PolicyIO io) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = row0 + 16 * MT * wr + 16 * i + 4 * g + r;
-                if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(acc[i][j][r] + bc, 0.0f));
+                if (GATED) { if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(fmaf(gsig[(size_t)row * N + col], acc[i][j][r] + bc, gbeta[(size_t)row * N + col]), 0.0f)); }
+                else if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(acc[i][j][r] + bc, 0.0f));
             }
     }
 }
@@ -386,9 +498,16 @@ __global__ void __launch_bounds__(256) k_policy_gemm(PolicyDev p, PolicyIO io) {
 // three-deep register ring (block t + 2 is requested before block t is multiplied), the whole schedule unrolled at compile time so that the
 // ring slots are plain registers.  KS1 = K1 / 32 (8: humanoid, 12: dog3d); H1 = 1024, H2 = 512 (learning/nets/fc_2layers_1024units.py);
 // other widths take the per-layer kernels above.
-template <int KS1, int N3T>
+//
+// GATED (dm_policy_create_gated, GC <= 256, GH = 64): behind the observations a prologue takes the tile's goal rows through c, e_0, e_1 (gate_hidden; sx and sc live in the
+// chunk buffers, which are still empty, e_0 / e_1 in 8 KB of their own).  The gate projections ride the weight stream: behind the layer-1 blocks of every chunk 3 blocks =
+// 4 feature tiles x {sigma k-steps 0 1, beta k-steps 0 1, scale biases, bias-projection biases}, behind the last chunk 6 blocks for the 8 layer-2 tiles; a tile's sigma and
+// beta are formed in the epilogue that already holds its accumulators (gated_tile_store), 8 MFMAs per feature tile.  Block t + 2 is still requested when block t is entered,
+// and a block is entered once the block before it is used up (a tile's six slots may straddle two blocks).  The plain instantiations are untouched by the switch.
+template <int KS1, int N3T, bool GATED = false>
 __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO io) {
-    constexpr int R = 32, NQ = 4, NB1 = KS1 / 2, NB2 = 8, NBQ = NB1 + NB2, NBLK = NQ * NBQ;
+    constexpr int NGB1 = GATED ? 3 : 0, NGB2 = GATED ? 6 : 0;
+    constexpr int R = 32, NQ = 4, NB1 = KS1 / 2, NB2 = 8, NBQ = NB1 + NGB1 + NB2, NBLK = NQ * NBQ + NGB2;
     constexpr int LDS_S16 = KS1 * 2 * 64, LDS_H1C = 8 * 2 * 64, LDS_H2 = 16 * 2 * 64;            // in 16-byte records
     constexpr int LDS_TOTAL = (LDS_S16 + 2 * LDS_H1C > LDS_H2) ? LDS_S16 + 2 * LDS_H1C : LDS_H2;
     __shared__ bf16x8 lds[LDS_TOTAL];
@@ -465,6 +584,36 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
         }
     }
     __syncthreads();
+    bf16x8* se = nullptr;
+    if constexpr (GATED) {
+        __shared__ bf16x8 se_buf[2 * 4 * 2 * 64];
+        se = se_buf;
+        const GateDev gd = *io.gate;
+        bf16x8* const sx = h1c + LDS_H1C;          // goal block re-based to k = 0 (<= 512 records); c goes to h1c[0] (<= 1024 records)
+        {
+            const uint16_t* const s16h = reinterpret_cast<const uint16_t*>(s16); uint16_t* const sxh = reinterpret_cast<uint16_t*>(sx);
+            const int m = t & 31;
+            for (int k = t >> 5; k < gd.KG; k += 8) {
+                const int kc = p.S - gd.G + k;
+                sxh[((size_t)((k >> 5) * 2 + (m >> 4)) * 64 + (m & 15) + 16 * ((k & 31) >> 3)) * 8 + (k & 7)] =
+                    k < gd.G ? s16h[((size_t)((kc >> 5) * 2 + (m >> 4)) * 64 + (m & 15) + 16 * ((kc & 31) >> 3)) * 8 + (kc & 7)] : (uint16_t)0;
+            }
+        }
+        __syncthreads();
+        gate_hidden(gd, sx, h1c, se, w, l, c, g);
+    }
+#define DMF_GF(X_, i_) ring[((X_) + (i_) / 8) % 3][(i_) % 8]
+    /* gated tile tl_ (six slots from 6 tl_ on behind block X_) for both batch tiles; before it the blocks whose predecessor is used up are entered */
+#define DMF_GATED_TILE(X_, tl_, E_, ACC_, MB_, DST0_, DST1_)                                                                                          \
+    {                                                                                                                                                 \
+        if ((tl_) % 4 == 0) DMF_LOAD(((X_) + 3 * ((tl_) / 4) + 2) % 3, (X_) + 3 * ((tl_) / 4) + 2)                                                    \
+        if ((tl_) % 4 == 2) DMF_LOAD(((X_) + 3 * ((tl_) / 4) + 3) % 3, (X_) + 3 * ((tl_) / 4) + 3)                                                    \
+        if ((tl_) % 4 == 3) DMF_LOAD(((X_) + 3 * ((tl_) / 4) + 4) % 3, (X_) + 3 * ((tl_) / 4) + 4)                                                    \
+        gated_tile_store(DST0_, DMF_GF(X_, 6 * (tl_)), DMF_GF(X_, 6 * (tl_) + 1), DMF_GF(X_, 6 * (tl_) + 2), DMF_GF(X_, 6 * (tl_) + 3), DMF_GF(X_, 6 * (tl_) + 4),   \
+                         DMF_GF(X_, 6 * (tl_) + 5), (E_)[(0 * 2 + 0) * 64 + l], (E_)[(1 * 2 + 0) * 64 + l], ACC_[0], MB_);                            \
+        gated_tile_store(DST1_, DMF_GF(X_, 6 * (tl_)), DMF_GF(X_, 6 * (tl_) + 1), DMF_GF(X_, 6 * (tl_) + 2), DMF_GF(X_, 6 * (tl_) + 3), DMF_GF(X_, 6 * (tl_) + 4),   \
+                         DMF_GF(X_, 6 * (tl_) + 5), (E_)[(0 * 2 + 1) * 64 + l], (E_)[(1 * 2 + 1) * 64 + l], ACC_[1], MB_);                            \
+    }
 
     DMF_STAMP(1)
     f32x4 acc2[8][2];
@@ -497,7 +646,15 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
             }
         }
         // bias + ReLU + bf16 -> this chunk's buffer, already in the B-fragment order of layer 2 (local k = 64 w + 16 j + 4 g + r)
-        {
+        if constexpr (GATED) {
+            uint16_t* const dst = reinterpret_cast<uint16_t*>(h1c + (q & 1) * LDS_H1C);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int f0 = 256 * q + 64 * w + 16 * j + 4 * g;
+                const int ksl = 2 * w + (j >> 1), ll = c + 16 * (2 * (j & 1) + (g >> 1));
+                DMF_GATED_TILE(q * NBQ + NB1, j, se, acc1[j], sbias + f0, dst + ((size_t)((ksl * 2 + 0) * 64 + ll)) * 8 + 4 * (g & 1), dst + ((size_t)((ksl * 2 + 1) * 64 + ll)) * 8 + 4 * (g & 1))
+            }
+        } else {
             uint16_t* const dst = reinterpret_cast<uint16_t*>(h1c + (q & 1) * LDS_H1C);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
@@ -517,7 +674,7 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
             const bf16x8* const src = h1c + (q & 1) * LDS_H1C;
 #pragma unroll
             for (int ksl = 0; ksl < NB2; ++ksl) {
-                const int blk = q * NBQ + NB1 + ksl;
+                const int blk = q * NBQ + NB1 + NGB1 + ksl;
                 DMF_LOAD((blk + 2) % 3, blk + 2)
                 const bf16x8 x0 = src[(ksl * 2 + 0) * 64 + l], x1 = src[(ksl * 2 + 1) * 64 + l];
 #pragma unroll
@@ -525,11 +682,24 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
             }
         }
     }
-#undef DMF_LOAD
     DMF_STAMP(3)
-    // the first action tile's 16 weight fragments of layer 3 are requested now (the ring is dead): they arrive during the epilogue and the barrier
     constexpr int KS3 = 16;
     bf16x8 wf[KS3];
+    float hc_ls[NT3W][4], hc_b3[NT3W][4], hc_as[NT3W][4], hc_am[NT3W][4];
+    if constexpr (GATED) {
+        // layer-2 epilogue, gated: the ring is still at work (6 blocks of gate projections), so layer 3's first fragments are requested behind it
+        uint16_t* const dst = reinterpret_cast<uint16_t*>(h2);
+#pragma unroll
+        for (int n = 0; n < 8; ++n) {
+            const int f0 = 128 * w + 16 * n + 4 * g;
+            const int ks = 4 * w + (n >> 1), ll = c + 16 * (2 * (n & 1) + (g >> 1));
+            DMF_GATED_TILE(NQ * NBQ, n, se + 512, acc2[n], sbias + 1024 + f0, dst + ((size_t)((ks * 2 + 0) * 64 + ll)) * 8 + 4 * (g & 1), dst + ((size_t)((ks * 2 + 1) * 64 + ll)) * 8 + 4 * (g & 1))
+        }
+    }
+#undef DMF_GATED_TILE
+#undef DMF_GF
+#undef DMF_LOAD
+    // the first action tile's 16 weight fragments of layer 3 are requested now (the ring is dead): they arrive during the epilogue and the barrier
     {
         const int ntc0 = (w >> 1) < N3T ? (w >> 1) : N3T - 1;
         DMP_SCHED_FENCE();
@@ -538,7 +708,6 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
         DMP_SCHED_FENCE();
     }
     // ... and so are the head's per-column constants of every tile this wave owns (branch-free, clamped: one latency for all of them)
-    float hc_ls[NT3W][4], hc_b3[NT3W][4], hc_as[NT3W][4], hc_am[NT3W][4];
 #pragma unroll
     for (int it = 0; it < NT3W; ++it)
 #pragma unroll
@@ -549,7 +718,7 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
     DMP_SCHED_FENCE();
     // layer-2 epilogue -> h2 (B-fragment order of layer 3: k = 128 w + 16 n + 4 g + r).  Every wave is past the barrier of the last chunk, so s16 and
     // h1c[0], which h2 overlays, are dead; h1c[1] (still being read by slower waves) lies behind them.
-    {
+    if constexpr (!GATED) {
         uint16_t* const dst = reinterpret_cast<uint16_t*>(h2);
 #pragma unroll
         for (int n = 0; n < 8; ++n) {

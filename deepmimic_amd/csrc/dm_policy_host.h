@@ -6,8 +6,11 @@ struct dm_policy {
     dmp::PolicyDev pd; int device_id = 0; int cap = 0;
     int last_path = DM_POLICY_PATH_NONE, last_rows = 0;      // dm_policy_info: the kernels of the last dm_policy_forward(_ex)
     uint16_t *h1 = nullptr, *h2 = nullptr, *s16 = nullptr;
+    bool gated = false; dmp::GateDev gd; const dmp::GateDev* gd_dev = nullptr;   // dm_policy_create_gated: the gate's packed weights (gd_dev: the copy the fused kernel reads)
+    float* gbuf[4] = {nullptr, nullptr, nullptr, nullptr};   // sigma_0, beta_0 [cap x H1], sigma_1, beta_1 [cap x H2] fp32, grown with h1 / h2
     std::vector<void*> allocs;
-    ~dm_policy() { for (void* p : allocs) rt_free(p); if (h1) rt_free(h1); if (h2) rt_free(h2); if (s16) rt_free(s16); }
+    void free_gbuf() { for (float*& b : gbuf) { if (b) rt_free(b); b = nullptr; } }
+    ~dm_policy() { for (void* p : allocs) rt_free(p); if (h1) rt_free(h1); if (h2) rt_free(h2); if (s16) rt_free(s16); free_gbuf(); }
     void* up(const void* host, size_t bytes) { void* d = nullptr; if (rt_malloc(&d, bytes)) return nullptr; allocs.push_back(d); if (rt_h2d(d, host, bytes, 0)) return nullptr; return d; }
 };
 
@@ -43,6 +46,67 @@ static std::vector<uint16_t> pack_fused_stream(const std::vector<uint16_t>& w1p,
     return out;
 }
 
+// the gated twin: the same blocks, plus behind the layer-1 blocks of every chunk 3 blocks and behind the last chunk 6 blocks of gate projections -- per feature tile
+// (16 q + 4 w + j, then 8 w + n) six 1 KB slots in consumption order: sigma fragments of k-steps 0 and 1, beta fragments of k-steps 0 and 1 (pack_weights with K = GH = 64),
+// then the lane's four scale biases and four bias-projection biases as fp32 bits (lane l: features 16 ft + 4 (l >> 4) + r)
+static std::vector<uint16_t> pack_fused_stream_gated(const std::vector<uint16_t>& w1p, const std::vector<uint16_t>& w2p, int K1, const std::vector<uint16_t> (&wbp)[2],
+                                                     const std::vector<uint16_t> (&wsp)[2], const float* const (&bb)[2], const float* const (&bs)[2]) {
+    const int KS1 = K1 / 32, NB1 = KS1 / 2, NBQ = NB1 + 3 + 8, NBLK = 4 * NBQ + 6, KS2 = 1024 / 32;
+    std::vector<uint16_t> out((size_t)4 * NBLK * 8 * 512, 0);
+    auto gate_tile = [&](size_t slot0, int layer, int ft) {          // six slots from slot index slot0 on
+        for (int ks = 0; ks < 2; ++ks) {
+            std::copy(wsp[layer].begin() + ((size_t)ft * 2 + ks) * 512, wsp[layer].begin() + ((size_t)ft * 2 + ks + 1) * 512, out.begin() + (slot0 + ks) * 512);
+            std::copy(wbp[layer].begin() + ((size_t)ft * 2 + ks) * 512, wbp[layer].begin() + ((size_t)ft * 2 + ks + 1) * 512, out.begin() + (slot0 + 2 + ks) * 512);
+        }
+        for (int l = 0; l < 64; ++l) {
+            memcpy(&out[(slot0 + 4) * 512 + (size_t)l * 8], bs[layer] + 16 * ft + 4 * (l >> 4), 16);
+            memcpy(&out[(slot0 + 5) * 512 + (size_t)l * 8], bb[layer] + 16 * ft + 4 * (l >> 4), 16);
+        }
+    };
+    for (int w = 0; w < 4; ++w) {
+        for (int q = 0; q < 4; ++q) {
+            for (int b1 = 0; b1 < NB1; ++b1) for (int kk = 0; kk < 2; ++kk) for (int j = 0; j < 4; ++j) {
+                const size_t dst = (((size_t)w * NBLK + q * NBQ + b1) * 8 + kk * 4 + j) * 512;
+                const size_t src = ((size_t)(16 * q + 4 * w + j) * KS1 + 2 * b1 + kk) * 512;
+                std::copy(w1p.begin() + src, w1p.begin() + src + 512, out.begin() + dst);
+            }
+            for (int j = 0; j < 4; ++j) gate_tile(((size_t)w * NBLK + q * NBQ + NB1) * 8 + 6 * j, 0, 16 * q + 4 * w + j);
+            for (int ksl = 0; ksl < 8; ++ksl) for (int n = 0; n < 8; ++n) {
+                const size_t dst = (((size_t)w * NBLK + q * NBQ + NB1 + 3 + ksl) * 8 + n) * 512;
+                const size_t src = ((size_t)(8 * w + n) * KS2 + 8 * q + ksl) * 512;
+                std::copy(w2p.begin() + src, w2p.begin() + src + 512, out.begin() + dst);
+            }
+        }
+        for (int n = 0; n < 8; ++n) gate_tile(((size_t)w * NBLK + 4 * NBQ) * 8 + 6 * n, 1, 8 * w + n);
+    }
+    return out;
+}
+
+// the launches of a path id, plain or GATED: one copy of the kernel choice for both
+template <bool GATED>
+static void launch_fused(int path, unsigned grid, rt_stream stream, const dmp::PolicyDev& d, const dmp::PolicyIO& io) {
+    switch (path) {
+    case DM_POLICY_PATH_FUSED_8_2: RT_LAUNCH4((dmp::k_policy_fused<8, 2, GATED>), grid, stream, d, io); break;
+    case DM_POLICY_PATH_FUSED_8_4: RT_LAUNCH4((dmp::k_policy_fused<8, 4, GATED>), grid, stream, d, io); break;
+    case DM_POLICY_PATH_FUSED_12_2: RT_LAUNCH4((dmp::k_policy_fused<12, 2, GATED>), grid, stream, d, io); break;
+    default: RT_LAUNCH4((dmp::k_policy_fused<12, 4, GATED>), grid, stream, d, io); break;
+    }
+}
+// layers 1 and 2; tiles sized so that every launch has at least ~1 wave per SIMD at 4096 rows: 64 x 64 (layer 1), 32 x 64 (layer 2)
+template <bool GATED>
+static void launch_layers(int path, int n, rt_stream stream, const dmp::PolicyDev& d, const dmp::PolicyIO& io) {
+    switch (DM_POLICY_PATH_LAYER1(path)) {
+    case DM_POLICY_LAYER_TILE128: RT_LAUNCH4((dmp::k_policy_gemm<0, 128, GATED>), ((n + 127) / 128) * (d.H1 / 128), stream, d, io); break;
+    case DM_POLICY_LAYER_TILE64: RT_LAUNCH4((dmp::k_policy_gemm<0, 64, GATED>), ((n + 63) / 64) * (d.H1 / 128), stream, d, io); break;
+    default: RT_LAUNCH((dmp::k_policy_layer<0, 4, 4, GATED>), ((n + 63) / 64) * (d.H1 / 64), stream, d, io); break;
+    }
+    switch (DM_POLICY_PATH_LAYER2(path)) {
+    case DM_POLICY_LAYER_TILE128: RT_LAUNCH4((dmp::k_policy_gemm<1, 128, GATED>), ((n + 127) / 128) * (d.H2 / 128), stream, d, io); break;
+    case DM_POLICY_LAYER_TILE64: RT_LAUNCH4((dmp::k_policy_gemm<1, 64, GATED>), ((n + 63) / 64) * (d.H2 / 128), stream, d, io); break;
+    default: RT_LAUNCH((dmp::k_policy_layer<1, 2, 4, GATED>), ((n + 31) / 32) * (d.H2 / 64), stream, d, io); break;
+    }
+}
+
 // The ONE place that decides which kernels a forward call runs (ids: include/dm_hip.h dm_policy_path): dm_policy_forward_ex launches from the id
 // this returns and dm_policy_info reports it, so the report cannot drift from the launch.
 // One launch for the whole actor (k_policy_fused) where it is compiled for the widths; DM_POLICY_LAYERED=1 keeps the per-layer kernels (A/B, tests).
@@ -67,14 +131,26 @@ int dm_policy_info(dm_policy* p, int32_t* out) {
     if (!p || !out) return fail("null argument");
     for (int i = 0; i < 8; ++i) out[i] = 0;
     out[0] = p->pd.K1; out[1] = p->pd.N3; out[2] = p->pd.wfs ? 1 : 0; out[3] = p->last_path; out[4] = p->last_rows;
+    out[5] = p->gated ? 1 : 0; out[6] = p->gated ? p->gd.G : 0; out[7] = (p->gated && p->pd.wfs) ? 1 : 0;
     return 0;
 }
 
-int dm_policy_create(int device_id, const dm_policy_params* pp, dm_policy** out) {
+}  // extern "C"
+
+// gp == nullptr: the plain actor.  With a gate the fused stream is the gated one (pack_fused_stream_gated; gate_hidden = 64 only, else the per-layer kernels)
+static int policy_create(int device_id, const dm_policy_params* pp, const dm_policy_gate_params* gp, dm_policy** out) {
     if (!pp || !out) return fail("null argument");
     if (pp->state_dim < 1 || pp->action_dim < 1 || pp->hidden1 < 64 || pp->hidden2 < 64) return fail("dm_policy_create: bad layer widths");
     if (pp->hidden1 % 64 || pp->hidden2 % 64) return fail("dm_policy_create: hidden widths must be multiples of 64 (reference: 1024, 512)");
     if (!pp->w1 || !pp->b1 || !pp->w2 || !pp->b2 || !pp->w3 || !pp->b3) return fail("dm_policy_create: null weights");
+    if (gp) {
+        if (gp->goal_dim < 1 || gp->goal_dim >= pp->state_dim) return fail("dm_policy_create_gated: goal_dim must be in [1, state_dim): the gate reads the last goal_dim input columns");
+        if (gp->goal_dim > 128) return fail("dm_policy_create_gated: goal_dim above 128 is not compiled (k_policy_gate holds the goal block in LDS)");
+        if (gp->gate_common < 32 || gp->gate_common % 32 || gp->gate_common > 256 || gp->gate_hidden < 32 || gp->gate_hidden % 32 || gp->gate_hidden > 128)
+            return fail("dm_policy_create_gated: gate widths must be multiples of 32, gate_common <= 256 and gate_hidden <= 128 (reference: 128, 64)");
+        if (!gp->gc_w || !gp->gc_b || !gp->g0_w || !gp->g0_b || !gp->g0_bias_w || !gp->g0_bias_b || !gp->g0_scale_w || !gp->g0_scale_b ||
+            !gp->g1_w || !gp->g1_b || !gp->g1_bias_w || !gp->g1_bias_b || !gp->g1_scale_w || !gp->g1_scale_b) return fail("dm_policy_create_gated: null gate weights");
+    }
 #ifndef DM_EMU
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
@@ -91,9 +167,12 @@ int dm_policy_create(int device_id, const dm_policy_params* pp, dm_policy** out)
     for (int i = 0; i < d.S; ++i) { if (pp->s_mean) sm[i] = pp->s_mean[i]; if (pp->s_std) si[i] = 1.0f / pp->s_std[i]; }
     // one-launch actor: compiled for the reference's widths (1024, 512), K1 = 256 / 384 and up to 64 action slots; a K1 of 320 is padded up to 384
     d.wfs = nullptr;
-    if (d.H1 == 1024 && d.H2 == 512 && d.K1 <= 384 && d.N3 <= 64) {
+    const bool fusable = d.H1 == 1024 && d.H2 == 512 && d.K1 <= 384 && d.N3 <= 64 && (!gp || gp->gate_hidden == 64);
+    if (fusable) {
         if (d.K1 == 320) { d.K1 = 384; w1 = pack_weights(pp->w1, d.S, d.H1, d.K1, d.H1); }
         if (d.K1 < 256) { d.K1 = 256; w1 = pack_weights(pp->w1, d.S, d.H1, d.K1, d.H1); }
+    }
+    if (fusable && !gp) {
         std::vector<uint16_t> fs = pack_fused_stream(w1, w2, d.K1);
         d.wfs = (const uint16_t*)p->up(fs.data(), fs.size() * 2);
         if (!d.wfs) { delete p; return fail("device allocation failed"); }
@@ -105,8 +184,44 @@ int dm_policy_create(int device_id, const dm_policy_params* pp, dm_policy** out)
     d.logstd = (const float*)p->up(ls.data(), sizeof(float) * d.A);
     d.s_clip = (pp->s_clip > 0) ? (float)pp->s_clip : std::numeric_limits<float>::infinity();
     if (!d.w1p || !d.w2p || !d.w3p || !d.b1 || !d.b2 || !d.b3 || !d.s_mean || !d.s_inv_std || !d.a_mean || !d.a_std || !d.logstd) { delete p; return fail("device allocation failed"); }
+    if (gp) {
+        dmp::GateDev& q = p->gd; memset(&q, 0, sizeof(q));
+        q.G = gp->goal_dim; q.KG = (q.G + 31) / 32 * 32; q.GC = gp->gate_common; q.GH = gp->gate_hidden;
+        const float* ew[2] = {gp->g0_w, gp->g1_w}; const float* eb[2] = {gp->g0_b, gp->g1_b};
+        const float* bw[2] = {gp->g0_bias_w, gp->g1_bias_w}; const float* bb[2] = {gp->g0_bias_b, gp->g1_bias_b};
+        const float* sw[2] = {gp->g0_scale_w, gp->g1_scale_w}; const float* sb[2] = {gp->g0_scale_b, gp->g1_scale_b};
+        std::vector<uint16_t> last;
+        auto upw = [&](const float* W, int K, int N, int Kp) { last = pack_weights(W, K, N, Kp, N); return (const uint16_t*)p->up(last.data(), last.size() * 2); };
+        std::vector<uint16_t> hwb[2], hws[2];
+        q.wcp = upw(gp->gc_w, q.G, q.GC, q.KG); q.bc = (const float*)p->up(gp->gc_b, sizeof(float) * q.GC);
+        bool ok = q.wcp && q.bc;
+        for (int i = 0; i < 2; ++i) {
+            const int H = i ? d.H2 : d.H1;
+            q.wep[i] = upw(ew[i], q.GC, q.GH, q.GC); q.be[i] = (const float*)p->up(eb[i], sizeof(float) * q.GH);
+            q.wbp[i] = upw(bw[i], q.GH, H, q.GH); hwb[i] = last; q.bb[i] = (const float*)p->up(bb[i], sizeof(float) * H);
+            q.wsp[i] = upw(sw[i], q.GH, H, q.GH); hws[i] = last; q.bs[i] = (const float*)p->up(sb[i], sizeof(float) * H);
+            ok = ok && q.wep[i] && q.be[i] && q.wbp[i] && q.bb[i] && q.wsp[i] && q.bs[i];
+        }
+        if (ok && fusable) {
+            std::vector<uint16_t> fs = pack_fused_stream_gated(w1, w2, d.K1, hwb, hws, bb, sb);
+            d.wfs = (const uint16_t*)p->up(fs.data(), fs.size() * 2);
+            ok = d.wfs != nullptr;
+        }
+        if (ok) { p->gd_dev = (const dmp::GateDev*)p->up(&q, sizeof(q)); ok = p->gd_dev != nullptr; }
+        if (!ok) { delete p; return fail("device allocation failed"); }
+        p->gated = true;
+    }
     *out = p;
     return 0;
+}
+
+extern "C" {
+
+int dm_policy_create(int device_id, const dm_policy_params* pp, dm_policy** out) { return policy_create(device_id, pp, nullptr, out); }
+
+int dm_policy_create_gated(int device_id, const dm_policy_params* pp, const dm_policy_gate_params* gp, dm_policy** out) {
+    if (!gp) return fail("null argument");
+    return policy_create(device_id, pp, gp, out);
 }
 
 int dm_policy_destroy(dm_policy* p) { if (!p) return 0; DevGuard guard(p->device_id); delete p; return 0; }
@@ -123,6 +238,7 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
                          int32_t* exp_flags_dev, double exp_rate, int sample, uint64_t seed, uint32_t step, int env_id_offset, void* hip_stream) {
     if (!p || !states_dev || !actions_dev) return fail("null argument");
     if (goal_dim < 0 || goal_dim >= p->pd.S || (goal_dim > 0 && !goals_dev)) return fail("dm_policy_forward_ex: goal_dim must be in [0, state_dim) with a goal block when positive (state_dim counts the goal columns)");
+    if (p->gated && goal_dim != 0 && goal_dim != p->gd.G) return fail("dm_policy_forward_ex: a gated actor takes its goal as a block of the gate's goal_dim columns, or goal_dim = 0 with the goal in the last columns of states_dev");
     if (!(exp_rate >= 0.0 && exp_rate <= 1.0)) return fail("dm_policy_forward_ex: exp_rate must be in [0, 1]");
     if (n <= 0) return 0;
     DevGuard guard(p->device_id);
@@ -130,8 +246,14 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
     if (n > p->cap) {                       // hidden activations: n x (H1 + H2) bf16, grown on demand
         rt_sync(stream);
         if (p->h1) rt_free(p->h1); if (p->h2) rt_free(p->h2); if (p->s16) rt_free(p->s16); p->h1 = p->h2 = p->s16 = nullptr; p->cap = 0;
+        p->free_gbuf();
         void *a = nullptr, *b = nullptr, *c = nullptr;
-        if (rt_malloc(&a, (size_t)n * p->pd.H1 * 2) || rt_malloc(&b, (size_t)n * p->pd.H2 * 2) || rt_malloc(&c, (size_t)n * p->pd.K1 * 2)) { if (a) rt_free(a); if (b) rt_free(b); return fail("device allocation failed"); }
+        if (rt_malloc(&a, (size_t)n * p->pd.H1 * 2) || rt_malloc(&b, (size_t)n * p->pd.H2 * 2) || rt_malloc(&c, (size_t)n * p->pd.K1 * 2)) { if (a) rt_free(a); if (b) rt_free(b); if (c) rt_free(c); return fail("device allocation failed"); }
+        if (p->gated) for (int i = 0; i < 4; ++i) {
+            void* g = nullptr;
+            if (rt_malloc(&g, (size_t)n * (i < 2 ? p->pd.H1 : p->pd.H2) * sizeof(float))) { p->free_gbuf(); rt_free(a); rt_free(b); rt_free(c); return fail("device allocation failed"); }
+            p->gbuf[i] = (float*)g;
+        }
         p->h1 = (uint16_t*)a; p->h2 = (uint16_t*)b; p->s16 = (uint16_t*)c; p->cap = n;
     }
     dmp::PolicyIO io; memset(&io, 0, sizeof(io));
@@ -139,6 +261,7 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
     io.seed_lo = (uint32_t)seed; io.seed_hi = (uint32_t)(seed >> 32); io.step = step; io.env_off = env_id_offset;
     if (const char* pr = getenv("DM_POLICY_PROBE")) io.probe = atoi(pr);
     io.goals = goal_dim ? goals_dev : nullptr; io.G = goal_dim; io.exp_rate = (float)exp_rate; io.exp_flags = exp_flags_dev;
+    io.gsig0 = p->gbuf[0]; io.gbeta0 = p->gbuf[1]; io.gsig1 = p->gbuf[2]; io.gbeta1 = p->gbuf[3]; io.gate = p->gd_dev;
     const dmp::PolicyDev& d = p->pd;
     const int path = policy_path(d);
     p->last_path = path; p->last_rows = n;
@@ -148,12 +271,7 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
         static unsigned long long* prof_buf = nullptr; static int prof_calls = 0;
         if (io.probe == 2) { if (!prof_buf && hipMalloc((void**)&prof_buf, (size_t)8192 * 8 * 8) != hipSuccess) prof_buf = nullptr; io.prof = grid <= 8192 ? prof_buf : nullptr; }
 #endif
-        switch (path) {
-        case DM_POLICY_PATH_FUSED_8_2: RT_LAUNCH4((dmp::k_policy_fused<8, 2>), grid, stream, d, io); break;
-        case DM_POLICY_PATH_FUSED_8_4: RT_LAUNCH4((dmp::k_policy_fused<8, 4>), grid, stream, d, io); break;
-        case DM_POLICY_PATH_FUSED_12_2: RT_LAUNCH4((dmp::k_policy_fused<12, 2>), grid, stream, d, io); break;
-        default: RT_LAUNCH4((dmp::k_policy_fused<12, 4>), grid, stream, d, io); break;
-        }
+        if (p->gated) launch_fused<true>(path, grid, stream, d, io); else launch_fused<false>(path, grid, stream, d, io);
 #ifndef DM_EMU
         hipError_t le0 = hipGetLastError(); if (le0 != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le0));
         if (io.prof && ++prof_calls == 100) {          // DM_POLICY_PROBE=2: phase times of the 100th launch (100 MHz constant clock -> ns), mean over the workgroups
@@ -169,16 +287,11 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
     }
     // tiles sized so that every launch has at least ~1 wave per SIMD at 4096 rows: 64 x 64 (layer 1), 32 x 64 (layer 2), 16 x 32 (layer 3)
     RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
-    switch (DM_POLICY_PATH_LAYER1(path)) {
-    case DM_POLICY_LAYER_TILE128: RT_LAUNCH4((dmp::k_policy_gemm<0, 128>), ((n + 127) / 128) * (d.H1 / 128), stream, d, io); break;
-    case DM_POLICY_LAYER_TILE64: RT_LAUNCH4((dmp::k_policy_gemm<0, 64>), ((n + 63) / 64) * (d.H1 / 128), stream, d, io); break;
-    default: RT_LAUNCH((dmp::k_policy_layer<0, 4, 4>), ((n + 63) / 64) * (d.H1 / 64), stream, d, io); break;
-    }
-    switch (DM_POLICY_PATH_LAYER2(path)) {
-    case DM_POLICY_LAYER_TILE128: RT_LAUNCH4((dmp::k_policy_gemm<1, 128>), ((n + 127) / 128) * (d.H2 / 128), stream, d, io); break;
-    case DM_POLICY_LAYER_TILE64: RT_LAUNCH4((dmp::k_policy_gemm<1, 64>), ((n + 63) / 64) * (d.H2 / 128), stream, d, io); break;
-    default: RT_LAUNCH((dmp::k_policy_layer<1, 2, 4>), ((n + 31) / 32) * (d.H2 / 64), stream, d, io); break;
-    }
+    if (p->gated) {
+        // the launch is (path id, gated): the same kernel choice per layer, its GATED instantiation, behind k_policy_gate (32 rows per workgroup)
+        RT_LAUNCH4(dmp::k_policy_gate, (n + 31) / 32, stream, d, io, p->gd);
+        launch_layers<true>(path, n, stream, d, io);
+    } else launch_layers<false>(path, n, stream, d, io);
     RT_LAUNCH((dmp::k_policy_layer<2, 1, 2>), (n + 15) / 16, stream, d, io);   // one workgroup per 16 rows owns all N3 columns (logp is a row sum)
 #ifndef DM_EMU
     hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));

@@ -3,6 +3,9 @@
 The actor of the reference's PPO / PG agents (learning/pg_agent.py:141-188, learning/nets/fc_2layers_1024units.py,
 learning/normalizer.py) evaluated by hand-written MFMA kernels (deepmimic_amd/csrc/dm_policy.h) on device buffers, so a
 rollout loop `states -> actions -> BatchEnv.step_device` never touches the host.  No CPU fallback.
+
+The gated actor of the AMP task policies (learning/nets/fc_2layers_gated_1024units.py) is the same class: a weights dict that carries the gate arrays
+(GATE_KEYS + "goal_dim") builds a gated context (dm_policy_create_gated).
 """
 import ctypes as C
 from typing import Optional
@@ -18,13 +21,29 @@ class _PolicyParams(C.Structure):
                [("s_clip", C.c_double)]
 
 
+class _GateParams(C.Structure):
+    _fields_ = [("goal_dim", C.c_int), ("gate_common", C.c_int), ("gate_hidden", C.c_int)] + \
+               [(k, C.POINTER(C.c_float)) for k in ("gc_w", "gc_b", "g0_w", "g0_b", "g0_bias_w", "g0_bias_b", "g0_scale_w", "g0_scale_b",
+                                                    "g1_w", "g1_b", "g1_bias_w", "g1_bias_b", "g1_scale_w", "g1_scale_b")]
+
+
+# the gate of a weights dict (tf.layers.dense layout): gc_* = actor/gate_common/0/dense [G, GC]; g{i}_w / _b = actor/gate{i}/0/dense [GC, GH];
+# g{i}_bias_* = actor/gate{i}/dense, g{i}_scale_* = actor/gate{i}/dense_1, [GH, H1] for i = 0 and [GH, H2] for i = 1; plus the integer "goal_dim"
+GATE_KEYS = tuple(k for k, _ in _GateParams._fields_[3:])
+
+
+def is_gated(weights: dict) -> bool:
+    return any(weights.get(k) is not None for k in GATE_KEYS)
+
+
 def _fp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
 
 
 class Policy:
     """weights: dict with w1 [S,H1], b1 [H1], w2 [H1,H2], b2 [H2], w3 [H2,A], b3 [A] (tf.layers.dense layout) and optional
-    s_mean, s_std, a_mean, a_std, logstd."""
+    s_mean, s_std, a_mean, a_std, logstd.  With the arrays of GATE_KEYS and "goal_dim" (the last goal_dim of the S input columns are the goal) the
+    context is the gated actor: same calls, the goal either as forward_device_ex's block or inside the state rows."""
 
     def __init__(self, weights: dict, device_id: int = 0, s_clip: float = 0.0, lib_path: Optional[str] = None):
         self.lib = load_library(lib_path)
@@ -39,16 +58,36 @@ class Policy:
         pp = _PolicyParams(self.S, self.H1, self.H2, self.A, *[_fp(w[k]) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "s_mean", "s_std", "a_mean", "a_std", "logstd")],
                            float(s_clip))
         self.h = C.c_void_p()
-        if self.lib.dm_policy_create(int(device_id), C.byref(pp), C.byref(self.h)) != 0:
+        self.gated = is_gated(weights)
+        if self.gated:
+            missing = [k for k in GATE_KEYS + ("goal_dim",) if weights.get(k) is None]
+            if missing:
+                raise ValueError("gated actor: no %s in the weights" % ", ".join(missing))
+            gw = {k: np.ascontiguousarray(weights[k], dtype=np.float32) for k in GATE_KEYS}
+            G = int(weights["goal_dim"]); GC = gw["gc_w"].shape[1]; GH = gw["g0_w"].shape[1]
+            want = dict(gc_w=(G, GC), gc_b=(GC,))
+            for i, H in ((0, self.H1), (1, self.H2)):
+                want.update({"g%d_w" % i: (GC, GH), "g%d_b" % i: (GH,), "g%d_bias_w" % i: (GH, H), "g%d_bias_b" % i: (H,), "g%d_scale_w" % i: (GH, H), "g%d_scale_b" % i: (H,)})
+            bad = [k for k in GATE_KEYS if gw[k].shape != want[k]]
+            if bad:
+                raise ValueError("inconsistent gate shapes: %s is %s, not %s" % (bad[0], gw[bad[0]].shape, want[bad[0]]))
+            if not hasattr(self.lib, "dm_policy_create_gated"):
+                raise RuntimeError("libdm_hip: this library has no dm_policy_create_gated (rebuild it)")
+            gp = _GateParams(G, GC, GH, *[_fp(gw[k]) for k in GATE_KEYS])
+            rc = self.lib.dm_policy_create_gated(int(device_id), C.byref(pp), C.byref(gp), C.byref(self.h))
+        else:
+            rc = self.lib.dm_policy_create(int(device_id), C.byref(pp), C.byref(self.h))
+        if rc != 0:
             raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
 
     @classmethod
     def from_checkpoint(cls, prefix: str, state_dim: Optional[int] = None, **kw):
         """the actor of a reference checkpoint (`--model_files <prefix>`: learning/rl_world.py:67-85, learning/tf_agent.py:36-48; read without TensorFlow by
         deepmimic_amd/tf_checkpoint.py) with its state / action normalisers.  An agent with a goal takes [state, goal] rows (forward_device_ex's goal block);
-        its g_norm rides behind s_norm."""
+        its g_norm rides behind s_norm.  The index decides the mapper: a checkpoint with actor/gate* variables (the AMP task policies) gives the gated actor."""
         from . import tf_checkpoint
-        w = tf_checkpoint.actor_weights(prefix, state_dim=state_dim)
+        gated = tf_checkpoint.is_gated_checkpoint(prefix)
+        w = (tf_checkpoint.gated_actor_weights if gated else tf_checkpoint.actor_weights)(prefix, state_dim=state_dim)
         if "g_mean" in w:
             w["s_mean"] = np.concatenate([w["s_mean"], w["g_mean"]]); w["s_std"] = np.concatenate([w["s_std"], w["g_std"]])
         return cls(w, **kw)
@@ -92,12 +131,14 @@ class Policy:
 
     def info(self) -> dict:
         """dm_policy_info (include/dm_hip.h): the padded widths K1 / N3, whether the one-launch actor's weight stream exists, and the
-        dm_policy_path id and row count of the last forward call (path -1 before any)"""
+        dm_policy_path id and row count of the last forward call (path -1 before any); gated / goal_dim: a gated context and the goal columns its
+        gate reads (the launch is then (path, gated)); gated_fused: the fused stream it holds is the gated one (k_policy_fused<.., true>)"""
         out = (C.c_int32 * 8)()
         self.lib.dm_policy_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         if self.lib.dm_policy_info(self.h, out) != 0:
             raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
-        return dict(K1=int(out[0]), N3=int(out[1]), fused=bool(out[2]), path=int(out[3]), rows=int(out[4]))
+        return dict(K1=int(out[0]), N3=int(out[1]), fused=bool(out[2]), path=int(out[3]), rows=int(out[4]), gated=bool(out[5]), goal_dim=int(out[6]),
+                    gated_fused=bool(out[7]))
 
     def close(self):
         if getattr(self, "h", None):
@@ -113,7 +154,8 @@ class Policy:
 
 def reference_forward(weights: dict, states, s_clip=np.inf, bf16=False):
     """Plain numpy statement of the same actor (fp32; bf16=True rounds operands to bfloat16 at the points the kernels do).
-    Returns the mode action and the normalised mean."""
+    Returns the mode action and the normalised mean.  With the gate arrays (GATE_KEYS, "goal_dim") it is the gated actor: the gate reads the normalised,
+    clipped goal columns; xg, c, e_i are rounded where the kernels round them, sigma, beta and the gated pre-activation are fp32."""
     def r(x):
         if not bf16:
             return x.astype(np.float32)
@@ -125,20 +167,45 @@ def reference_forward(weights: dict, states, s_clip=np.inf, bf16=False):
     sm = weights.get("s_mean"); ss = weights.get("s_std")
     x = (s - (0 if sm is None else sm.astype(np.float32))) * (np.float32(1) / (np.float32(1) if ss is None else ss.astype(np.float32)))
     x = np.clip(x, -s_clip, s_clip)
-    h = np.maximum(r(x).astype(np.float64) @ r(weights["w1"]).astype(np.float64) + weights["b1"], 0).astype(np.float32)
-    h = np.maximum(r(h).astype(np.float64) @ r(weights["w2"]).astype(np.float64) + weights["b2"], 0).astype(np.float32)
+    if is_gated(weights):
+        f32 = np.float32
+        dense = lambda v, k: (r(v).astype(np.float64) @ r(weights[k + "_w"]).astype(np.float64) + weights[k + "_b"]).astype(f32)
+        c = np.maximum(dense(x[:, S - int(weights["goal_dim"]):], "gc"), 0)
+        h = x
+        for i, (wk, bk) in enumerate((("w1", "b1"), ("w2", "b2"))):
+            e = np.maximum(dense(c, "g%d" % i), 0)
+            beta = dense(e, "g%d_bias" % i)
+            with np.errstate(over="ignore"):
+                sigma = (f32(2) / (f32(1) + np.exp(-dense(e, "g%d_scale" % i)))).astype(f32)
+            pre = (r(h).astype(np.float64) @ r(weights[wk]).astype(np.float64) + weights[bk]).astype(f32)
+            h = np.maximum((sigma.astype(np.float64) * pre + beta).astype(f32), 0)
+    else:
+        h = np.maximum(r(x).astype(np.float64) @ r(weights["w1"]).astype(np.float64) + weights["b1"], 0).astype(np.float32)
+        h = np.maximum(r(h).astype(np.float64) @ r(weights["w2"]).astype(np.float64) + weights["b2"], 0).astype(np.float32)
     m = (r(h).astype(np.float64) @ r(weights["w3"]).astype(np.float64) + weights["b3"]).astype(np.float32)
     am = weights.get("a_mean"); as_ = weights.get("a_std")
     a = m * (1 if as_ is None else as_) + (0 if am is None else am)
     return a.astype(np.float32), m
 
 
-def random_weights(S, A, H1=1024, H2=512, seed=0, init_output_scale=0.01, noise=0.05):
+def random_weights(S, A, H1=1024, H2=512, seed=0, init_output_scale=0.01, noise=0.05, gated_goal_dim=0, gate_common=128, gate_hidden=64):
     """Random-init weights of the reference architecture: Xavier-uniform hidden layers (learning/tf_util.py:27-39), uniform
-    (+-init_output_scale) output layer, logstd = log(noise) (pg_agent.py:147-158)."""
+    (+-init_output_scale) output layer, logstd = log(noise) (pg_agent.py:147-158).  gated_goal_dim = G > 0 adds the gate of
+    fc_2layers_gated_1024units.py on the last G of the S columns: Xavier kernels, zero biases (drawn after the plain layers, which stay what they are)."""
     rng = np.random.default_rng(seed)
     def xav(i, o):
         lim = np.sqrt(6.0 / (i + o)); return rng.uniform(-lim, lim, size=(i, o)).astype(np.float32)
+    w = _plain_random_weights(rng, xav, S, A, H1, H2, init_output_scale, noise)
+    if gated_goal_dim:
+        G, GC, GH = int(gated_goal_dim), gate_common, gate_hidden
+        w.update(goal_dim=G, gc_w=xav(G, GC), gc_b=np.zeros(GC, np.float32))
+        for i, H in ((0, H1), (1, H2)):
+            w.update({"g%d_w" % i: xav(GC, GH), "g%d_b" % i: np.zeros(GH, np.float32), "g%d_bias_w" % i: xav(GH, H), "g%d_bias_b" % i: np.zeros(H, np.float32),
+                      "g%d_scale_w" % i: xav(GH, H), "g%d_scale_b" % i: np.zeros(H, np.float32)})
+    return w
+
+
+def _plain_random_weights(rng, xav, S, A, H1, H2, init_output_scale, noise):
     return dict(w1=xav(S, H1), b1=np.zeros(H1, np.float32), w2=xav(H1, H2), b2=np.zeros(H2, np.float32),
                 w3=rng.uniform(-init_output_scale, init_output_scale, size=(H2, A)).astype(np.float32), b3=np.zeros(A, np.float32),
                 logstd=np.full(A, np.log(noise), np.float32))

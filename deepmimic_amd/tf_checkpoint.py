@@ -11,8 +11,8 @@ Variables of an agent (learning/pg_agent.py:141-188, learning/nets/fc_2layers_10
     agent/main/actor/0/dense/{kernel,bias}  [S + G, 1024]      agent/main/actor/1/dense/{kernel,bias}  [1024, 512]
     agent/main/actor/dist_gauss_diag/mean/{kernel,bias}  [512, A]      agent/main/actor/dist_gauss_diag/logstd/bias  [A]
     agent/resource/{s_norm,g_norm,a_norm}/{mean,std}
-The AMP task policies use the gated net (learning/nets/fc_2layers_gated_1024units.py: `gate0`, `gate1`, `gate_common` variables); the device actor is the
-plain two-layer net, so those are refused with the list of what was found."""
+The AMP task policies use the gated net (learning/nets/fc_2layers_gated_1024units.py: `gate0`, `gate1`, `gate_common` variables): `gated_actor_weights`
+reads those for the gated device actor; `actor_weights`, which returns the plain net's dict, refuses them and says so."""
 import os
 import struct
 from typing import Dict, Optional
@@ -197,15 +197,57 @@ def actor_weights(prefix: str, scope: str = "agent", state_dim: Optional[int] = 
     a = scope + "/main/actor/"
     gated = sorted(n for n in idx if n.startswith(a + "gate"))
     if gated:
-        raise NotImplementedError("%s holds a gated actor (learning/nets/fc_2layers_gated_1024units.py: %s, ...); the device actor is the plain fc_2layers_1024units net" % (prefix, gated[0]))
+        raise NotImplementedError("%s holds a gated actor (learning/nets/fc_2layers_gated_1024units.py: %s, ...); actor_weights returns the plain fc_2layers_1024units "
+                                  "net's dict: read it with gated_actor_weights (Policy.from_checkpoint picks the mapper by itself)" % (prefix, gated[0]))
+    return _actor_weights(idx, prefix, scope, state_dim, verify_below, {})
+
+
+# key of the weights dict of deepmimic_amd.policy (GATE_KEYS) -> variable under <scope>/main/actor/, as tf.layers.dense names them in the shipped gated
+# checkpoints (data/policies/humanoid3d_amp/*.ckpt.index: the first dense of a scope is `dense`, the second `dense_1`; tests/test_tf_checkpoint_gated.py
+# holds this table to every shipped index)
+GATE_VARIABLES = {"gc": "gate_common/0/dense", "g0": "gate0/0/dense", "g0_bias": "gate0/dense", "g0_scale": "gate0/dense_1",
+                  "g1": "gate1/0/dense", "g1_bias": "gate1/dense", "g1_scale": "gate1/dense_1"}
+
+
+def is_gated_checkpoint(prefix: str, scope: str = "agent") -> bool:
+    return any(n.startswith(scope + "/main/actor/gate") for n in read_index(prefix + ".index"))
+
+
+def gated_actor_weights(prefix: str, scope: str = "agent", state_dim: Optional[int] = None, verify_below: int = 1 << 16) -> dict:
+    """The gated actor of an AMP task checkpoint ("ActorNet": "fc_2layers_gated_1024units") as the weights dict of `deepmimic_amd.policy.Policy`: what
+    actor_weights returns plus the gate arrays (policy.GATE_KEYS) and goal_dim, the width of g_norm -- the gate's input is the normalised goal."""
+    idx = read_index(prefix + ".index")
+    a = scope + "/main/actor/"
+    extra = {}
+    for key, var in GATE_VARIABLES.items():
+        extra[key + "_w"] = a + var + "/kernel"; extra[key + "_b"] = a + var + "/bias"
+    missing = [n for n in extra.values() if n not in idx]
+    if missing:
+        raise ValueError("%s: no %s (not a gated actor; plain ones are read by actor_weights)" % (prefix, missing[0]))
+    w = _actor_weights(idx, prefix, scope, state_dim, verify_below, extra)
+    G = w["g_mean"].size if "g_mean" in w else 0
+    if G < 1 or w["gc_w"].shape[0] != G:
+        raise ValueError("%s: the gate takes %d inputs, g_norm has %d" % (prefix, w["gc_w"].shape[0], G))
+    GC, GH = w["gc_w"].shape[1], w["g0_w"].shape[1]
+    for i, H in ((0, w["w1"].shape[1]), (1, w["w2"].shape[1])):
+        if w["g%d_w" % i].shape != (GC, GH) or w["g%d_bias_w" % i].shape != (GH, H) or w["g%d_scale_w" % i].shape != (GH, H):
+            raise ValueError("%s: gate %d shapes %s %s %s do not chain from %d to %d" % (prefix, i, w["g%d_w" % i].shape, w["g%d_bias_w" % i].shape, w["g%d_scale_w" % i].shape, GC, H))
+    w["goal_dim"] = G
+    return w
+
+
+def _actor_weights(idx, prefix, scope, state_dim, verify_below, extra) -> dict:
+    a = scope + "/main/actor/"
     need = [a + "0/dense/kernel", a + "0/dense/bias", a + "1/dense/kernel", a + "1/dense/bias", a + "dist_gauss_diag/mean/kernel", a + "dist_gauss_diag/mean/bias",
             a + "dist_gauss_diag/logstd/bias"]
     missing = [n for n in need if n not in idx]
     if missing:
         raise ValueError("%s: no %s (not a pg / ppo agent checkpoint of scope %r)" % (prefix, missing[0], scope))
     norms = [scope + "/resource/%s/%s" % (g, k) for g in ("s_norm", "g_norm", "a_norm") for k in ("mean", "std")]
-    t = read_tensors(prefix, names=set(need + [n for n in norms if n in idx]), verify_below=verify_below)
+    t = read_tensors(prefix, names=set(need + list(extra.values()) + [n for n in norms if n in idx]), verify_below=verify_below)
     w = dict(w1=t[need[0]], b1=t[need[1]], w2=t[need[2]], b2=t[need[3]], w3=t[need[4]], b3=t[need[5]], logstd=t[need[6]])
+    for k, n in extra.items():
+        w[k] = t[n]
     for g, key in (("s_norm", "s"), ("g_norm", "g"), ("a_norm", "a")):
         for k in ("mean", "std"):
             n = scope + "/resource/%s/%s" % (g, k)

@@ -423,8 +423,30 @@ enum dm_policy_path {
 };
 /* out[0] = K1 and out[1] = N3, the padded input / action widths the context really uses; out[2] = 1 if it holds a fused weight stream;
  * out[3] = dm_policy_path of the LAST dm_policy_forward(_ex) on this context (DM_POLICY_PATH_NONE before any; the environment switches
- * DM_POLICY_LAYERED / DM_POLICY_ONE_WAVE / DM_POLICY_TILE are read per call); out[4] = its row count; out[5..7] = 0 (reserved) */
+ * DM_POLICY_LAYERED / DM_POLICY_ONE_WAVE / DM_POLICY_TILE are read per call); out[4] = its row count; out[5] = 1 for a gated context
+ * (dm_policy_create_gated), out[6] = its goal_dim, out[7] = 1 if the fused stream it holds is the gated one */
 int dm_policy_info(dm_policy* policy, int32_t* out);
+
+/* The gated actor of the AMP task policies (learning/nets/fc_2layers_gated_1024units.py, "ActorNet": "fc_2layers_gated_1024units"): a small net on the
+ * NORMALISED GOAL, the last goal_dim input columns, scales and shifts the pre-activations of both hidden layers --
+ *   c = relu(Wc xg + bc);  e_i = relu(We_i c + be_i);  beta_i = Wb_i e_i + bb_i;  sigma_i = 2 sigmoid(Ws_i e_i + bs_i);  h_i = relu(sigma_i * (W_i h + b_i) + beta_i)
+ * -- head, noise, exploration coin and logp as in the plain actor.  Arrays in tf.layers.dense layout like dm_policy_params: gc_* = actor/gate_common/0/dense
+ * [goal_dim x gate_common]; g{i}_w / _b = actor/gate{i}/0/dense [gate_common x gate_hidden]; g{i}_bias_* = actor/gate{i}/dense and g{i}_scale_* =
+ * actor/gate{i}/dense_1, [gate_hidden x hidden1] for i = 0 and [gate_hidden x hidden2] for i = 1.  Refused at create: goal_dim outside [1, min(state_dim - 1, 128)],
+ * gate widths that are no multiples of 32, gate_common > 256, gate_hidden > 128 (reference: 128, 64).
+ * The result is an ordinary dm_policy: dm_policy_forward(_ex), dm_policy_bind_obs_normalizer (g_norm bound at column state_dim - goal_dim feeds the gate with no
+ * further call), dm_policy_info and dm_policy_destroy work on it.  dm_policy_forward_ex takes goal_dim equal to the gate's with a goal block, or goal_dim = 0
+ * with the goal in the last columns of states_dev; any other goal_dim fails.  Which kernels run is (dm_policy_path id, gated): the id says which kernel serves
+ * each layer, out[5] of dm_policy_info that its GATED instantiation ran: k_policy_fused<.., true> in one launch at 1024 / 512, K1 256 / 384, N3 32 / 64 with
+ * gate_hidden = 64 (out[2] = out[7] = 1), else -- and under DM_POLICY_LAYERED -- k_policy_gate and the GATED per-layer kernels.  Rounding points:
+ * deepmimic_amd/csrc/dm_policy.h GateDev. */
+typedef struct {
+    int goal_dim, gate_common, gate_hidden;
+    const float *gc_w, *gc_b;
+    const float *g0_w, *g0_b, *g0_bias_w, *g0_bias_b, *g0_scale_w, *g0_scale_b;
+    const float *g1_w, *g1_b, *g1_bias_w, *g1_bias_b, *g1_scale_w, *g1_scale_b;
+} dm_policy_gate_params;
+int dm_policy_create_gated(int device_id, const dm_policy_params* params, const dm_policy_gate_params* gate, dm_policy** out);
 
 /* ---- Running observation statistics on the device: the Normalizer of the reference's learner (learning/normalizer.py:6-152; the
  * s_norm / g_norm / amp_obs_norm of learning/rl_agent.py:466-483, amp_agent.py:290-291) for records that stay in HBM.

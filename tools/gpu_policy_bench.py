@@ -1,6 +1,10 @@
 #!/usr/bin/env python
 """Time the on-device policy (dm_policy.h) alone and inside the closed 30 Hz loop (policy -> control step), 4096 humanoids.
-Prints one JSON object; run on the GPU box."""
+Prints one JSON object; run on the GPU box.
+
+--gated: instead, the actor alone at the humanoid task shape (197 + 3 goal columns, 36 actions) for ROWS (default 2048,4096,16384) rows: the plain actor in
+one launch (k_policy_fused), the plain actor on the per-layer kernels (DM_POLICY_LAYERED=1), the gated actor in one launch (k_policy_fused<.., true>) and on
+the per-layer route (k_policy_gate + GATED per-layer kernels), all in this one process, interleaved, median of 5 blocks of 200 calls each."""
 import json
 import os
 import sys
@@ -13,6 +17,43 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from deepmimic_amd import model                      # noqa: E402
 from deepmimic_amd.core import BatchEnv              # noqa: E402
 from deepmimic_amd.policy import Policy, random_weights   # noqa: E402
+
+
+
+def gated_bench():
+    S, G, A = 197, 3, 36
+    wg = random_weights(S + G, A, seed=0, gated_goal_dim=G)
+    wp = {k: v for k, v in wg.items() if not k.startswith("g")}
+    out = {"shape": [S, G, A], "rows": {}}
+    stream = torch.cuda.Stream(); torch.cuda.set_stream(stream); sh = stream.cuda_stream
+    for rows in [int(r) for r in os.environ.get("ROWS", "2048,4096,16384").split(",")]:
+        st = torch.randn((rows, S), device="cuda"); gl = torch.randn((rows, G), device="cuda"); ac = torch.zeros((rows, A), device="cuda")
+        cases = {"plain_fused": (Policy(wp), None), "plain_layered": (Policy(wp), "1"), "gated_fused": (Policy(wg), None), "gated_layered": (Policy(wg), "1")}
+        times = {k: [] for k in cases}; paths = {}
+        for block in range(6):                       # block 0 warms up
+            for name, (pol, layered) in cases.items():
+                if layered: os.environ["DM_POLICY_LAYERED"] = layered
+                else: os.environ.pop("DM_POLICY_LAYERED", None)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(stream)
+                for k in range(200):
+                    pol.forward_device_ex(st.data_ptr(), rows, ac.data_ptr(), goals_ptr=gl.data_ptr(), goal_dim=G, sample=True, seed=1, step=k, stream=sh)
+                e1.record(stream); torch.cuda.synchronize()
+                if block: times[name].append(1e3 * e0.elapsed_time(e1) / 200)
+                paths[name] = [pol.info()["path"], int(pol.info()["gated"])]
+        os.environ.pop("DM_POLICY_LAYERED", None)
+        med = {k: float(np.median(v)) for k, v in times.items()}
+        out["rows"][str(rows)] = {"us_per_call_median_of_5": med, "us_per_call_min_max": {k: [min(v), max(v)] for k, v in times.items()}, "path_gated": paths,
+                                  "gated_fused_over_plain_fused": med["gated_fused"] / med["plain_fused"], "gated_layered_over_gated_fused": med["gated_layered"] / med["gated_fused"],
+                                  "gated_layered_over_plain_layered": med["gated_layered"] / med["plain_layered"]}
+        for pol, _ in cases.values():
+            pol.close()
+    print(json.dumps(out))
+
+
+if "--gated" in sys.argv:
+    gated_bench()
+    sys.exit(0)
 
 n = int(os.environ.get("ENVS", "4096")); iters = 200
 t = model.load_asset("humanoid3d_walk")
