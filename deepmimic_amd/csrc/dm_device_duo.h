@@ -643,9 +643,22 @@ _Pragma("unroll") \
     // (x, xr) := L^-T (x, xr): rows 3..33 per lane with column reads from LDS, rows 0..2 by three half-wave sums
     DM_DEV void back_substitute(Real& x, Real (&xr)[3], Real dinv, Real dinv0) {
         const int own = hl + 3; const bool valid = own < m.D;
+        // Column `own` of L below the diagonal, c[k] = L[k][own] for k > own and 0 above.  Every lane reads all 30 words without a test, off ONE base register
+        // with the row offsets as immediates, and the lanes on or above the diagonal are zeroed by a select on a constant lane mask (lanes hl < k - 3 of either half;
+        // every launch has D == ND, so those are valid row lanes).  A word past the end of a short packed row is a word of a later row of the same Lt.  The form
+        // `(valid && k > own) ? Lt[...] : 0` compiled to a basic block per element (compare, exec save, address, read, exec restore): 2/3 of this routine's instructions.
+        const Real* colp = &s.Lt[valid ? own : 3];
+        uint64_t z = 0; DM_OPAQUE_S(z);
         Real c[ND];
+        c[3] = 0;
 #pragma unroll
-        for (int k = 0; k < ND; ++k) c[k] = (valid && k > own) ? s.Lt[L::lrow(k) + own] : (Real)0;
+        for (int k = ND - 1; k >= 4; --k) c[k] = colp[L::lrow(k)];      // in the order of their use
+        DM_SCHED_FENCE();                                // all requests before the first select, or every select waits for its own read (lgkmcnt(0) 15 times)
+        static_for<0, ND - 4>([&](auto jc) {
+            constexpr int k = ND - 1 - decltype(jc)::value;
+            constexpr uint64_t below = (1ull << (k - 3)) - 1ull;
+            c[k] = lane_sel<(below << 32) | below>(c[k], (Real)0, wl, z);
+        });
 #define DM_DUO_BWD(k) { const Real xk = half_bcast_c<(k) - 3>(x * dinv, half); x -= c[k] * xk; }      /* c[k] = 0 for k <= own */
         static_assert(ND == 34, "the expansion below covers rows 33..3");
         DM_DUO_BWD(33) DM_DUO_BWD(32) DM_DUO_BWD(31) DM_DUO_BWD(30) DM_DUO_BWD(29) DM_DUO_BWD(28) DM_DUO_BWD(27) DM_DUO_BWD(26)
