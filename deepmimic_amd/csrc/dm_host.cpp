@@ -295,20 +295,49 @@ static int build_host_model(const dm_scene_tables& t, int max_contacts, HostMode
     return 0;
 }
 
-// ---------------------------------------------------------------- kernel family of a step launch
-// The object a step-kernel launch runs: DM_FAMILY_<id> of dm_kernels.cpp (KIDS of the Makefiles), from the class (CtxT::cls numbering), the
-// variant (SV_PLAIN / SV_AMP / SV_TAPS / SV_V2) and the wave packing; -1 for a combination no family instantiates.  Reported by dm_get_debug "family".
-template <typename C> struct ClsId;
-template <> struct ClsId<ClsBiped> { static constexpr int v = 0; };
-template <> struct ClsId<ClsLarge> { static constexpr int v = 1; };
-template <> struct ClsId<ClsBipedObj> { static constexpr int v = 2; };
-template <> struct ClsId<ClsLargeTree> { static constexpr int v = 3; };
-template <> struct ClsId<ClsBipedTree> { static constexpr int v = 4; };
-static int step_family(int cls, int variant, bool duo) {
-    static const int one[5][4] = {{3, 4, 5, 18}, {6, 7, 8, 19}, {-1, 9, 10, 23}, {12, 13, 14, 20}, {15, 16, 17, 21}};      // [class][variant], one character per wavefront
-    static const int two[5][4] = {{0, 1, 2, 22}, {-1, -1, -1, -1}, {-1, 24, -1, -1}, {-1, -1, -1, -1}, {-1, -1, -1, -1}};  // two characters per wavefront
-    if (cls < 0 || cls > 4 || variant < 0 || variant > 3) return -1;
-    return duo ? two[cls][variant] : one[cls][variant];
+// ---------------------------------------------------------------- launch tables, built from dm_families.h
+// step[class][variant][packing - 1]: the family id (reported by dm_get_debug "family") and the launcher of every row of DM_STEP_FAMILIES, a null launcher
+// for a combination no family instantiates; reset / query / probe per class of the reset / query / probe family, expert through the base class.
+template <typename Real>
+struct LaunchTable {
+    struct Step { int family; decltype(&launch_step_family<Real, 0>) launch; } step[kNumCls][SV_COUNT][2];
+    decltype(&launch_reset<Real, ClsBiped>) reset[kNumCls];
+    decltype(&launch_query<Real, ClsBiped>) query[kNumCls];
+    decltype(&launch_probe<Real, ClsBiped>) probe[kNumCls];
+    decltype(&launch_amp_expert<Real, ClsBiped>) expert[kNumCls];
+    int base[kNumCls];
+    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, base{} {
+#define DM_ROW(id, pack, Cls, V) if (!step[k##Cls][V][pack - 1].launch) step[k##Cls][V][pack - 1] = {id, &launch_step_family<Real, id>};      // (of two rows for one combination the first is dispatched)
+        DM_STEP_FAMILIES(DM_ROW)
+#undef DM_ROW
+#define DM_ROW(Cls) reset[k##Cls] = &launch_reset<Real, Cls>; query[k##Cls] = &launch_query<Real, Cls>; probe[k##Cls] = &launch_probe<Real, Cls>;
+        DM_MISC_CLASSES(DM_ROW)
+#undef DM_ROW
+#define DM_ROW(Cls) expert[k##Cls] = &launch_amp_expert<Real, Cls>;
+        DM_EXPERT_CLASSES(DM_ROW)
+#undef DM_ROW
+#define DM_ROW(Cls, id, Base) base[k##Cls] = k##Base;
+        DM_CLASSES(DM_ROW)
+#undef DM_ROW
+        for (int c = 0; c < kNumCls; ++c) {
+            expert[c] = expert[base[c]];
+            if (!reset[c] || !expert[c]) throw "dm_families.h: a class without reset / query / probe kernels, or whose base class has no AMP expert";      // (fails the build: the table is constexpr)
+        }
+    }
+};
+template <typename Real> static const LaunchTable<Real>& launch_table() { static constexpr LaunchTable<Real> t; return t; }
+
+// the dof tree of the skeleton is the compiled topology T (dm_types.h TopoTables)
+template <typename T> static bool same_topology(const HostModel& h) {
+    if (h.D != T::N) return false;
+    std::vector<int> lam(h.D, -1);      // parent dof of every dof: the joint's previous dof, or the last dof of its nearest ancestor that has any
+    for (int j = 0; j < h.J; ++j) {
+        int a = h.parent[j];
+        while (a >= 0 && h.ndof[a] == 0) a = h.parent[a];
+        for (int k = 0; k < h.ndof[j]; ++k) lam[h.dof_off[j] + k] = (k == 0) ? (a < 0 ? -1 : h.dof_off[a] + h.ndof[a] - 1) : h.dof_off[j] + k - 1;
+    }
+    for (int k = 0; k < h.D; ++k) if (lam[k] != T::PAR[k]) return false;
+    return true;
 }
 
 // ---------------------------------------------------------------- device-side context, typed on the kernel precision
@@ -318,7 +347,7 @@ struct CtxBase {
     std::vector<void*> allocs;
     float *d_actions = nullptr, *d_states = nullptr, *d_rewards = nullptr; int *d_term = nullptr, *d_valid = nullptr, *d_end = nullptr;
     bool duo = false, duo_obj = true, upload_failed = false; int physics = 1;
-    int last_family = -1;                  // step_family() of the last step-kernel launch (step, dm_probe 3 / 4); -1 before any
+    int last_family = -1;                  // family id (dm_families.h) of the last step-kernel launch (step, dm_probe 3 / 4); -1 before any
     int* d_ids = nullptr; const int* step_ids = nullptr; int step_n_ids = 0;      // dm_step_envs: the subset the next step() call runs (device ids), cleared after it
     virtual ~CtxBase() { for (void* p : allocs) rt_free(p); }
     void* dalloc(size_t n) { void* p = nullptr; if (rt_malloc(&p, n) != 0) return nullptr; allocs.push_back(p); return p; }
@@ -348,7 +377,7 @@ struct CtxBase {
 
 template <typename Real>
 struct CtxT : CtxBase {
-    ModelDev<Real> md; EnvState<Real> st; DebugTaps<Real> dbg; int cls = 0; long long* d_prof = nullptr; double* d_tape = nullptr;
+    ModelDev<Real> md; EnvState<Real> st; DebugTaps<Real> dbg; int cls = kClsBiped; long long* d_prof = nullptr; double* d_tape = nullptr;
 
     template <typename T, typename U> const T* up(const std::vector<U>& v) {
         std::vector<T> tmp(v.size()); for (size_t i = 0; i < v.size(); ++i) tmp[i] = (T)v[i];
@@ -408,46 +437,27 @@ struct CtxT : CtxBase {
             md.NL = 2 * h.NL;
             if (max_contacts > (kMaxRows - md.NL) / 3) max_contacts = (kMaxRows - md.NL) / 3;
         }
-        if (h.J <= ClsBiped::NJ && h.D <= ClsBiped::ND && h.P <= ClsBiped::NP && h.NC <= ClsBiped::NCAP && !any_rot) cls = 0;
-        else if (h.J <= ClsLarge::NJ && h.D <= ClsLarge::ND && h.P <= ClsLarge::NP && h.NC <= ClsLarge::NCAP) cls = 1;
+        if (h.J <= ClsBiped::NJ && h.D <= ClsBiped::ND && h.P <= ClsBiped::NP && h.NC <= ClsBiped::NCAP && !any_rot) cls = kClsBiped;
+        else if (h.J <= ClsLarge::NJ && h.D <= ClsLarge::ND && h.P <= ClsLarge::NP && h.NC <= ClsLarge::NCAP) cls = kClsLarge;
         else return fail("character too large for the compiled kernel classes (J<=23, D<=64, P<=83, <=128 contact candidates)");
-        if (c.scene_goal == 5) { if (cls != 0) return fail("dribble_amp is compiled for the biped class only"); cls = 2; }      // biped + one free body
+        if (c.scene_goal == 5) { if (cls != kClsBiped) return fail("dribble_amp is compiled for the biped class only"); cls = kClsBipedObj; }      // biped + one free body
         // a skeleton whose dof tree is one of the compiled topologies runs the branch-sparse, level-scheduled factor (dm_types.h
         // TopoTables); anything else of that size the dense class.  DM_TREE=0 keeps the dense class (A/B runs).
-        if (cls == 1 && h.D == TopoDog3d::N) {
-            std::vector<int> lam(h.D, -1);
-            for (int j = 0; j < h.J; ++j) {
-                int a = h.parent[j];
-                while (a >= 0 && h.ndof[a] == 0) a = h.parent[a];
-                for (int k = 0; k < h.ndof[j]; ++k) lam[h.dof_off[j] + k] = (k == 0) ? (a < 0 ? -1 : h.dof_off[a] + h.ndof[a] - 1) : h.dof_off[j] + k - 1;
-            }
-            bool same = true;
-            for (int k = 0; k < h.D; ++k) if (lam[k] != TopoDog3d::PAR[k]) same = false;
-            const char* tv = getenv("DM_TREE");
-            if (same && !(tv && tv[0] == '0')) cls = 3;
-        }
+        const char* tv = getenv("DM_TREE");
+        if (cls == kClsLarge && !(tv && tv[0] == '0') && same_topology<TopoDog3d>(h)) cls = kClsLargeTree;
         // humanoid3d one character per wavefront (wave_packing 1): the same factor on its compiled topology.  The two-per-wave kernel (the
         // default for this class) keeps the dense factor.
-        if (cls == 0 && (!duo || physics == 2 || (N % 2) != 0) && h.D == TopoHumanoid3d::N) {
-            std::vector<int> lam(h.D, -1);
-            for (int j = 0; j < h.J; ++j) {
-                int a = h.parent[j];
-                while (a >= 0 && h.ndof[a] == 0) a = h.parent[a];
-                for (int k = 0; k < h.ndof[j]; ++k) lam[h.dof_off[j] + k] = (k == 0) ? (a < 0 ? -1 : h.dof_off[a] + h.ndof[a] - 1) : h.dof_off[j] + k - 1;
-            }
-            bool same = true;
-            for (int k = 0; k < h.D; ++k) if (lam[k] != TopoHumanoid3d::PAR[k]) same = false;
-            // opt-in (DM_TREE_BIPED=1): on humanoid3d the sparse factor saves too little (154 of 289 packed FMAs per factorisation) to pay for
-            // the column build and the level bookkeeping inside a 128-VGPR budget -- measured 1.00 M env-steps/s at 4 waves / SIMD, 1.31 M
-            // at 2, against 1.66 M for the dense one-per-wave kernel and 2.06 M two-per-wave (same box, profiles/r03_ab_biped_tree.json)
-            const char* tv = getenv("DM_TREE_BIPED");
-            if (same && tv && tv[0] == '1') cls = 4;
-        }
-        md.mdl_blob = (cls == 0 || cls == 2 || cls == 4) ? build_mdl<ClsBiped>(&md.mdl_words) : build_mdl<ClsLarge>(&md.mdl_words);
+        // opt-in (DM_TREE_BIPED=1): on humanoid3d the sparse factor saves too little (154 of 289 packed FMAs per factorisation) to pay for
+        // the column build and the level bookkeeping inside a 128-VGPR budget -- measured 1.00 M env-steps/s at 4 waves / SIMD, 1.31 M
+        // at 2, against 1.66 M for the dense one-per-wave kernel and 2.06 M two-per-wave (same box, profiles/r03_ab_biped_tree.json)
+        const char* tb = getenv("DM_TREE_BIPED");
+        if (cls == kClsBiped && (!duo || physics == 2 || (N % 2) != 0) && tb && tb[0] == '1' && same_topology<TopoHumanoid3d>(h)) cls = kClsBipedTree;
+        const bool biped_base = launch_table<Real>().base[cls] == kClsBiped;      // the class shares ClsBiped's model tables and capacities, else ClsLarge's
+        md.mdl_blob = biped_base ? build_mdl<ClsBiped>(&md.mdl_words) : build_mdl<ClsLarge>(&md.mdl_words);
         md.act_off = up<int>(h.act_off); md.diffw = up<Real>(h.diffw); md.aabb_he = up<Real>(h.aabb_he);
         md.cand_link = up<int>(h.cand_link); md.cand_loc = up<Real>(h.cand_loc); md.cand_rad = up<Real>(h.cand_rad);
         md.pair_code = up<int>(h.pair_code); md.NPAIR = (int)h.pair_code.size();
-        if (md.NPAIR > ((cls == 0 || cls == 2 || cls == 4) ? ClsBiped::NPAIRCAP : ClsLarge::NPAIRCAP)) return fail("too many self-collision pairs for the compiled kernel classes");
+        if (md.NPAIR > (biped_base ? ClsBiped::NPAIRCAP : ClsLarge::NPAIRCAP)) return fail("too many self-collision pairs for the compiled kernel classes");
         md.frame_time = up<double>(h.frame_time); md.frames = up<Real>(h.frames); md.frame_vel = up<Real>(h.frame_vel);
         md.duration = h.duration; md.loop = h.loop; for (int k = 0; k < 3; ++k) { md.cycle_delta[k] = (Real)h.cycle_delta[k]; md.gravity[k] = (Real)c.gravity[k]; }
         md.num_sim_substeps = c.num_sim_substeps; md.solver_iters = c.solver_iters > 0 ? c.solver_iters : 10; md.max_contacts = max_contacts;
@@ -466,9 +476,9 @@ struct CtxT : CtxBase {
         if (st.clock) rt_memset(st.clock, 0, sizeof(double) * (size_t)N * 6, stream);   // word 5 of a clock row counts the env's substeps on borrowed lanes (two-per-wave kernel, round 6)
         if (st.kin) rt_memset(st.kin, 0, sizeof(Real) * (size_t)N * 8, stream);      // word 7 of a kin row is the env's fallback-substep counter (two-per-wave kernel), never reset by the device
         // overflow rows of the constraint-space matrix (rows RREG..63 of a character with more than RREG rows in a substep)
-        { const int ovf = kMaxRows - ((cls == 0 || cls == 2 || cls == 4) ? ClsBiped::RREG : ClsLarge::RREG); st.aovf = ovf > 0 ? (Real*)dalloc(sizeof(Real) * (size_t)N * ovf * kWave) : nullptr; }
+        { const int ovf = kMaxRows - (biped_base ? ClsBiped::RREG : ClsLarge::RREG); st.aovf = ovf > 0 ? (Real*)dalloc(sizeof(Real) * (size_t)N * ovf * kWave) : nullptr; }
         st.obj = nullptr;
-        if (cls == 2) {
+        if (cls == kClsBipedObj) {
             st.obj = (Real*)dalloc(sizeof(Real) * (size_t)N * OB_WIDTH);
             if (!st.obj) return fail("device allocation failed");
             rt_memset(st.obj, 0, sizeof(Real) * (size_t)N * OB_WIDTH, stream);
@@ -560,31 +570,20 @@ struct CtxT : CtxBase {
         d_prof = (long long*)dalloc(sizeof(long long) * N * 16);
         return dbg.links ? 0 : fail("device allocation failed");
     }
-    // every step-kernel launch goes through these: they record the family it runs (dm_get_debug "family")
-    template <typename C, int V> void run_step(unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
-        last_family = step_family(ClsId<C>::v, V, false); launch_step<Real, C, V>(grid, stream, md, st, io, d);
+    // every step-kernel launch goes through here: the family of (class, variant, packing) is recorded (dm_get_debug "family") and launched
+    int launch_step(int variant, int packing, unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
+        const auto& e = launch_table<Real>().step[cls][variant][packing - 1];
+        if (!e.launch) return fail("no kernel family for class " + std::to_string(cls) + ", variant " + std::to_string(variant) + ", " + std::to_string(packing) + " per wavefront (dm_families.h)");
+        last_family = e.family; e.launch(grid, stream, md, st, io, d);
+        return 0;
     }
-    template <int V> void run_step_duo(unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
-        last_family = step_family(ClsId<ClsBiped>::v, V, true); launch_step_duo<Real, V>(grid, stream, md, st, io, d);
-    }
-    template <typename C, int V> void run_step_duo_c(unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
-        last_family = step_family(ClsId<C>::v, V, true); launch_step_duo_c<Real, C, V>(grid, stream, md, st, io, d);
-    }
-#define DM_DISPATCH(LAUNCH, grid, ...)                                                       \
-    do {                                                                                     \
-        if (cls == 0) LAUNCH<Real, ClsBiped>(grid, stream, __VA_ARGS__);                         \
-        else if (cls == 2) LAUNCH<Real, ClsBipedObj>(grid, stream, __VA_ARGS__);                 \
-        else if (cls == 3) LAUNCH<Real, ClsLargeTree>(grid, stream, __VA_ARGS__);                \
-        else if (cls == 4) LAUNCH<Real, ClsBipedTree>(grid, stream, __VA_ARGS__);                \
-        else LAUNCH<Real, ClsLarge>(grid, stream, __VA_ARGS__);                                  \
-    } while (0)
 
     int reset(const int* ids_dev, int n, const double* kt_dev, const double* mt_dev) override {
         // a bound draw tape serves the whole reset of an env with a goal row; an env without one (single clip, no yaw) has only its perturbation clock on the
         // device -- its clip time and episode limit are the caller's draws (the facade makes them on the host in the reference's order): the counter-based
         // streams must not fill in silently
         if (md.draw_tape && !st.goal && (!kt_dev || !mt_dev)) return fail("a draw tape is bound and the scene has no goal row: dm_reset needs kin_times and max_times (drawn by the caller in the reference's order)");
-        DM_DISPATCH(launch_reset, n, md, st, ids_dev, kt_dev, mt_dev);
+        launch_table<Real>().reset[cls](n, stream, md, st, ids_dev, kt_dev, mt_dev);
         return 0;
     }
     int step(const float* actions_dev, double dt, int n_updates, float* states, float* rewards, int* term, int* valid, int* end, int flags, float* amp) override {
@@ -594,46 +593,20 @@ struct CtxT : CtxBase {
         io.env_ids = step_ids; const int GN = step_ids ? step_n_ids : N;      // workgroups of the one-per-wave launches
         if (md.draw_tape && (flags & DM_AUTO_RESET)) return fail("a draw tape is bound (dm_set_draw_tape): resets go through dm_reset, where the tape serves the reference's draw order");
         io.n_updates = n_updates; io.dt = dt; io.auto_reset = (flags & DM_AUTO_RESET) ? 1 : 0; io.emit = (flags & DM_NO_EMIT) ? 0 : 1; io.open_loop = (flags & DM_OPEN_LOOP) ? 1 : 0; io.end_early = (flags & DM_END_EPISODE_EARLY) ? 1 : 0;
-        // two characters per wavefront: biped class, even batch, no debug taps armed (DM_DUO=0 keeps one character per wave)
-        if (duo && cls == 0 && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape) {      // (31 row lanes per character assume exactly 34 dofs; a bound draw tape is read by the one-per-wave kernels only -- EnvSim::tape() -- so such a batch takes them: ADVICE r5)
-            if (st.manif) run_step_duo<SV_V2>(N / 2, io, dbg);               // DM-physics v2, two characters per wavefront (round 4)
-            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) run_step_duo<SV_AMP>(N / 2, io, dbg);      // (the AMP instantiation also carries the perturbation code)
-            else run_step_duo<SV_PLAIN>(N / 2, io, dbg);
-            return 0;
-        }
-        // biped + free body (dribble_amp), two characters per wavefront (round 6; DM-physics v1 -- v2 and armed taps keep the one-per-wave kernel).  DM_DUO_OBJ=0: one per wave
-        if (duo && duo_obj && cls == 2 && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape && !st.manif) {
-            run_step_duo_c<ClsBipedObj, SV_AMP>(N / 2, io, dbg);
-            return 0;
-        }
-        // production launch: the tap-free instantiation unless a parity test armed the debug taps (dm_probe)
-        if (cls == 2) {
-            if (dbg.H) run_step<ClsBipedObj, SV_TAPS>(GN, io, dbg);
-            else if (st.manif) run_step<ClsBipedObj, SV_V2>(GN, io, dbg);      // round 5: the links' ground contacts through the persistent manifolds, the ball's single-point contacts as under v1
-            else run_step<ClsBipedObj, SV_AMP>(GN, io, dbg);
-        }
-        else if (cls == 4) {
-            if (dbg.H) run_step<ClsBipedTree, SV_TAPS>(GN, io, dbg);
-            else if (st.manif) run_step<ClsBipedTree, SV_V2>(GN, io, dbg);
-            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) run_step<ClsBipedTree, SV_AMP>(GN, io, dbg);
-            else run_step<ClsBipedTree, SV_PLAIN>(GN, io, dbg);
-        }
-        else if (cls == 3) {
-            if (dbg.H) run_step<ClsLargeTree, SV_TAPS>(GN, io, dbg);
-            else if (st.manif) run_step<ClsLargeTree, SV_V2>(GN, io, dbg);
-            else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) run_step<ClsLargeTree, SV_AMP>(GN, io, dbg);
-            else run_step<ClsLargeTree, SV_PLAIN>(GN, io, dbg);
-        }
-        else if (dbg.H) { if (cls == 0) run_step<ClsBiped, SV_TAPS>(GN, io, dbg); else run_step<ClsLarge, SV_TAPS>(GN, io, dbg); }
-        else if (st.manif) { if (cls == 0) run_step<ClsBiped, SV_V2>(GN, io, dbg); else run_step<ClsLarge, SV_V2>(GN, io, dbg); }      // DM-physics v2: its own instantiation (AMP code + manifolds)
-        else if (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) { if (cls == 0) run_step<ClsBiped, SV_AMP>(GN, io, dbg); else run_step<ClsLarge, SV_AMP>(GN, io, dbg); }
-        else { if (cls == 0) run_step<ClsBiped, SV_PLAIN>(GN, io, dbg); else run_step<ClsLarge, SV_PLAIN>(GN, io, dbg); }
-        return 0;
+        // Packing.  Two characters per wavefront: biped class of exactly 34 dofs (31 row lanes per character assume them), even batch, no debug taps armed, the whole
+        // batch, no draw tape (a bound tape is read by the one-per-wave kernels only -- EnvSim::tape() -- so such a batch takes them); DM_DUO=0 keeps one character per wave.
+        // Biped + free body (dribble_amp) only under DM-physics v1 (v2 keeps the one-per-wave kernel); DM_DUO_OBJ=0: one per wave
+        const bool two = (duo && cls == kClsBiped && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape) ||
+                         (duo && duo_obj && cls == kClsBipedObj && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape && !st.manif);
+        // Variant.  The tap instantiation only when a parity test armed the debug taps (dm_probe); DM-physics v2 has its own (AMP code + manifolds); the AMP
+        // instantiation also carries the perturbation code; ClsBipedObj has no plain family
+        int variant = dbg.H ? SV_TAPS : st.manif ? SV_V2 : (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) ? SV_AMP : SV_PLAIN;
+        if (variant == SV_PLAIN && cls == kClsBipedObj) variant = SV_AMP;
+        return two ? launch_step(variant, 2, N / 2, io, dbg) : launch_step(variant, 1, GN, io, dbg);
     }
     int amp_expert(int n, const double* times_dev, const double* gh_dev, float* out_dev) override { return amp_expert_clips(n, nullptr, times_dev, gh_dev, out_dev); }
     int amp_expert_clips(int n, const int* clips_dev, const double* times_dev, const double* gh_dev, float* out_dev) override {
-        if (cls == 0 || cls == 2 || cls == 4) launch_amp_expert<Real, ClsBiped>(n, stream, md, times_dev, gh_dev, out_dev, clips_dev);
-        else launch_amp_expert<Real, ClsLarge>(n, stream, md, times_dev, gh_dev, out_dev, clips_dev);
+        launch_table<Real>().expert[cls](n, stream, md, times_dev, gh_dev, out_dev, clips_dev);      // (the expert of the base class)
         return 0;
     }
     int get_goal(double* out) override {
@@ -785,7 +758,7 @@ struct CtxT : CtxBase {
         StepIO<Real> io; memset(&io, 0, sizeof(io));
         io.amp_obs = amp; io.goals = d_goals;
         io.states = states; io.rewards = rewards; io.terminate = term; io.valid = valid; io.episode_end = end; io.emit = 1;
-        DM_DISPATCH(launch_query, N, md, st, io, dbg);
+        launch_table<Real>().query[cls](N, stream, md, st, io, dbg);
         return 0;
     }
     int probe(int what, double dt) override {
@@ -797,15 +770,9 @@ struct CtxT : CtxBase {
             io.states = d_states; io.rewards = d_rewards; io.terminate = d_term; io.valid = d_valid; io.episode_end = d_end;
             io.n_updates = 20; io.dt = dt; io.auto_reset = 1; io.emit = 1; io.open_loop = (what == 3) ? 1 : 0; io.end_early = 1;
             if (what == 4) io.actions = d_actions;
-            if (duo && cls == 0 && hm.D == ClsBiped::ND && (N % 2) == 0 && !st.manif) run_step_duo<SV_TAPS>(N / 2, io, d2);
-            else if (cls == 0) run_step<ClsBiped, SV_TAPS>(N, io, d2);
-            else if (cls == 2) run_step<ClsBipedObj, SV_TAPS>(N, io, d2);
-            else if (cls == 3) run_step<ClsLargeTree, SV_TAPS>(N, io, d2);
-            else if (cls == 4) run_step<ClsBipedTree, SV_TAPS>(N, io, d2);
-            else run_step<ClsLarge, SV_TAPS>(N, io, d2);
-            return 0;
+            return (duo && cls == kClsBiped && hm.D == ClsBiped::ND && (N % 2) == 0 && !st.manif) ? launch_step(SV_TAPS, 2, N / 2, io, d2) : launch_step(SV_TAPS, 1, N, io, d2);
         }
-        DM_DISPATCH(launch_probe, N, md, st, dbg, what, dt);
+        launch_table<Real>().probe[cls](N, stream, md, st, dbg, what, dt);
         return 0;
     }
     template <typename T> int dl(const T* dev, size_t n, double* out) {
@@ -844,7 +811,7 @@ struct CtxT : CtxBase {
     int get_debug(const char* name, double* out) override {
         const size_t n = N; const HostModel& h = hm; std::string s(name);
         if (s == "tau") return dl(st.tau, n * h.D, out);
-        if (s == "family") {        // N: the kernel family (DM_FAMILY_<id>) of the last step-kernel launch, the same for every env; -1 before any
+        if (s == "family") {        // N: the kernel family (id of dm_families.h) of the last step-kernel launch, the same for every env; -1 before any
             for (size_t e = 0; e < n; ++e) out[e] = (double)last_family;
             return 0;
         }

@@ -1,0 +1,8 @@
+# Included by deepmimic_amd/csrc/Makefile and tests/emu/Makefile (after OBJDIR): the kernel objects, one per precision and family id of dm_families.h --
+# the id of every F( row of DM_STEP_FAMILIES and DM_MISC_FAMILY.  Neither Makefile restates the list.  (${shell }: the pattern's parentheses are unbalanced.)
+FAMILIES_H := $(dir $(lastword $(MAKEFILE_LIST)))dm_families.h
+KIDS := ${shell sed -n -e 's/^ *F(\([0-9][0-9]*\),.*/\1/p' -e 's/^.define DM_MISC_FAMILY \([0-9][0-9]*\).*/\1/p' $(FAMILIES_H)}
+ifeq ($(strip $(KIDS)),)
+$(error no family ids found in $(FAMILIES_H))
+endif
+KOBJS := $(foreach i,$(KIDS),$(OBJDIR)/k_f32_$(i).o $(OBJDIR)/k_f64_$(i).o)

@@ -269,7 +269,7 @@ int dm_set_state(dm_ctx* ctx, const double* pose, const double* vel, const doubl
  * "borrowed" (N doubles): likewise the substeps in which ONE character of the pair had more than 32 rows, the two together
  * at most 64, and the pair stayed on the two-per-wavefront path with the heavy character's rows 32.. on lanes of its
  * partner's half (kept in the pad word of the env's clock row).
- * "family" (N doubles, all equal; needs no dm_probe): the kernel family -- DM_FAMILY_<id> of deepmimic_amd/csrc/dm_kernels.cpp,
+ * "family" (N doubles, all equal; needs no dm_probe): the kernel family -- its id in the table of deepmimic_amd/csrc/dm_families.h,
  * one compiled object per precision -- of the last step-kernel launch of the context (dm_step_*, dm_bench_rollout, the profiled
  * step of dm_probe 3 / 4); -1 before the first. */
 int dm_probe(dm_ctx* ctx, int what, double dt);

@@ -1,13 +1,13 @@
 """Every kernel family of libdm_hip.so against the oracle, with the family that ran reported by the library.
 
-libdm_hip.so is one object per (precision, kernel family): DM_FAMILY_<id> of deepmimic_amd/csrc/dm_kernels.cpp, KIDS of its Makefile, each with
+libdm_hip.so is one object per (precision, kernel family): the table of deepmimic_amd/csrc/dm_families.h, from which both Makefiles take their objects, each with
 code generation flags of its own (NOLICM_IDS, SCHED_IDS) and all from one source: which loops a kernel runs is a property of its class and template
 arguments (ClsBipedTree::PIPE = false: the tree loops without the LDS look-ahead; DuoSim::YFULL = false in the tap instantiation, family 2: the
 y = L^-1 J^T loops with their per-dof tests), so the emulator library runs, per class and per kernel, the loops of the GPU objects.  dm_get_debug
-"family" names the family of the last step launch (dm_host.cpp step_family), so each row of FAMILIES below asserts that its configuration ran the
+"family" names the family of the last step launch (dm_host.cpp launch_step), so each row of FAMILIES below asserts that its configuration ran the
 object it claims before it compares that object with the oracle.
 
-* ledger (CPU): FAMILIES covers every step family of the Makefile and dm_kernels.cpp, FAMILY11 every class of the reset / query / probe family;
+* ledger (CPU): FAMILIES covers every step family of the table and of both Makefiles' objects, FAMILY11 every class of the reset / query / probe family;
 * dispatch (CPU, emulator): each row's configuration reports its id, and so do the documented one-per-wavefront fallbacks;
 * build rules (CPU): no compile rule of either Makefile passes a -D that could fork a template between objects, no header keeps an overridable knob;
 * loop variants (CPU, emulator): the tree rows, the dense class and the two-per-wave tap family -- through both of its beyond-32-rows paths -- against the oracle;
@@ -15,6 +15,7 @@ object it claims before it compares that object with the oracle.
 """
 import os
 import re
+import subprocess
 from dataclasses import dataclass, field
 
 import numpy as np
@@ -83,8 +84,7 @@ FAMILIES = {
     24: Row(DRIBBLE, 10, kind="goal", pack=2, note="two-per-wave biped + free body"),
 }
 PRECISIONS = (32, 64)
-TWO_PER_WAVE = (0, 1, 2, 22, 24)
-# family 11: reset / query / probe of every class (dm_host.cpp DM_DISPATCH) and the AMP expert, which every biped class shares with ClsBiped
+# family 11: reset / query / probe of every class (dm_host.cpp LaunchTable) and the AMP expert, which every biped class shares with ClsBiped
 FAMILY11 = {
     "ClsBiped": ("misc", "expert"), "ClsBipedObj": ("misc",), "ClsLarge": ("misc", "expert"), "ClsLargeTree": ("misc",), "ClsBipedTree": ("misc",),
 }
@@ -208,30 +208,43 @@ def _makefile_var(path, name):
     return m.group(1).split()
 
 
-def _family_defs():
-    src = open(os.path.join(CSRC, "dm_kernels.cpp")).read()
-    return {int(i): body for i, body in re.findall(r"^#define DM_FAMILY_(\d+)\(Real\)(.*)$", src, re.M)}
+def _table():
+    """dm_families.h: ({step family id: (characters per wavefront, class, variant)}, id of the reset / query / probe family, its classes, the expert classes)"""
+    src = open(os.path.join(CSRC, "dm_families.h")).read()
+    rows = re.findall(r"^\s*F\((\d+),\s*([12]),\s*(\w+),\s*(SV_\w+)\)", src, re.M)
+    step = {int(i): (int(pack), cls, v) for i, pack, cls, v in rows}
+    assert len(step) == len(rows), "a family id has two rows"
+    misc = int(re.search(r"^#define DM_MISC_FAMILY (\d+)", src, re.M).group(1))
+    classes = {n: set(re.findall(r"\b%s\((\w+)\)" % x, re.search(r"^#define DM_%s_CLASSES\(%s\)(.*)$" % (n, x), src, re.M).group(1))) for n, x in (("MISC", "M"), ("EXPERT", "E"))}
+    return step, misc, classes["MISC"], classes["EXPERT"]
+
+
+TWO_PER_WAVE = tuple(sorted(i for i, (pack, _, _) in _table()[0].items() if pack == 2))
+
+
+def _built_families(mk_dir):
+    """the family ids a Makefile builds kernel objects for (dry run of a full build): {32: ids, 64: ids}"""
+    out = subprocess.run(["make", "-C", mk_dir, "-n", "-B"], check=True, capture_output=True, text=True).stdout
+    return {prec: {int(i) for i in re.findall(r"-o \S*/k_f%d_(\d+)\.o\b" % prec, out)} for prec in PRECISIONS}
 
 
 def test_ledger_covers_every_family():
-    """a family added to the Makefile or to dm_kernels.cpp fails here until FAMILIES has a row (configuration, oracle check, bounds) for it"""
-    kids = {int(k) for k in _makefile_var(os.path.join(CSRC, "Makefile"), "KIDS")}
-    assert kids == {int(k) for k in _makefile_var(os.path.join(EMU, "Makefile"), "KIDS")}, "tests/emu/Makefile KIDS differ from the product's"
-    defs = _family_defs()
-    assert set(defs) == kids, "DM_FAMILY_<id> of dm_kernels.cpp and KIDS differ: %s" % sorted(set(defs) ^ kids)
-    step = {i for i, body in defs.items() if re.search(r"DM_INST_(DUO|STEP|DUOC)\b", body)}
-    assert step == kids - {11}
+    """a family added to the table (dm_families.h) fails here until FAMILIES has a row (configuration, oracle check, bounds) for it"""
+    step, misc_id, misc, expert = _table()
+    kids = set(step) | {misc_id}
+    for mk_dir in (CSRC, EMU):
+        for prec, ids in _built_families(mk_dir).items():
+            assert ids == kids, "%s builds f%d objects for %s, the table has %s" % (os.path.relpath(mk_dir, ROOT), prec, sorted(ids), sorted(kids))
+    assert misc_id == 11 and misc_id not in step
     for prec in PRECISIONS:
-        missing = sorted(step - set(FAMILIES))
+        missing = sorted(set(step) - set(FAMILIES))
         assert not missing, "step families without a parity row (f%d): %s" % (prec, missing)
-    assert set(FAMILIES) <= step, sorted(set(FAMILIES) - step)
+    assert set(FAMILIES) <= set(step), sorted(set(FAMILIES) - set(step))
     for fid, row in FAMILIES.items():
         assert row.kind in ("sampled", "goal", "probe3") and row.n >= 8
         assert row.n % 2 == (0 if fid in TWO_PER_WAVE else 1), "family %d: pairs need an even N, one-per-wave rows an odd one" % fid
         if row.kind != "goal":
             assert len(row.f32_wc) == 2 and 0 < row.f32_wc[0] <= 1e-4 and 0 < row.f32_wc[1] < 0.3, "family %d needs its measured f32 bounds" % fid
-    misc = set(re.findall(r"DM_INST_MISC\(Real, (\w+)\)", defs[11]))
-    expert = set(re.findall(r"DM_INST_EXPERT\(Real, (\w+)\)", defs[11]))
     assert misc == set(FAMILY11), sorted(misc ^ set(FAMILY11))
     assert expert == {c for c, what in FAMILY11.items() if "expert" in what}
 
@@ -265,7 +278,7 @@ def test_no_rule_defines_a_source_variant():
         assert not knobs, "%s keeps overridable knobs %s" % (f, knobs)
     for var in ("NOLICM_IDS", "SCHED_IDS"):
         ids = {int(i) for i in _makefile_var(os.path.join(CSRC, "Makefile"), var)}
-        assert ids <= {int(k) for k in _makefile_var(os.path.join(CSRC, "Makefile"), "KIDS")}, var
+        assert ids <= _built_families(CSRC)[32], var
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- dispatch (CPU)
