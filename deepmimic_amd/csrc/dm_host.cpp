@@ -341,6 +341,9 @@ template <typename T> static bool same_topology(const HostModel& h) {
 }
 
 // ---------------------------------------------------------------- device-side context, typed on the kernel precision
+// what a control step / a query hands back: N x S states, N rewards / terminate / valid / episode-end flags, N x amp_size AMP observations; any may be null
+struct StepOut { float* states; float* rewards; int* term; int* valid; int* end; float* amp; };
+
 struct CtxBase {
     HostModel hm; int N = 0; int env_off = 0; uint64_t seed = 0; int precision = 32; int max_contacts = 20; int device_id = 0;
     rt_stream own_stream = 0, stream = 0;
@@ -353,16 +356,17 @@ struct CtxBase {
     void* dalloc(size_t n) { void* p = nullptr; if (rt_malloc(&p, n) != 0) return nullptr; allocs.push_back(p); return p; }
     virtual int setup() = 0;
     virtual int reset(const int* ids_dev, int n, const double* kt_dev, const double* mt_dev) = 0;
-    virtual int step(const float* actions_dev, double dt, int n_updates, float* states, float* rewards, int* term, int* valid, int* end, int flags, float* amp = nullptr) = 0;
-    virtual int query(float* states, float* rewards, int* term, int* valid, int* end, float* amp = nullptr) = 0;
-    virtual int amp_expert(int n, const double* times_dev, const double* gh_dev, float* out_dev) = 0;
+    virtual int step(const float* actions_dev, double dt, int n_updates, const StepOut& out_dev, int flags) = 0;
+    virtual int query(const StepOut& out_dev) = 0;
+    // the ctx's own output buffers: the five step outputs, the AMP observations on request
+    StepOut dev_out(bool amp) const { return StepOut{d_states, d_rewards, d_term, d_valid, d_end, amp ? d_amp : nullptr}; }
     int amp_size = 0; float* d_amp = nullptr; uint64_t expert_calls = 0;
     int goal_size = 0; float* d_goals = nullptr;            // RecordGoal of the last emit (goal scenes)
-    virtual int get_goal(double* out) = 0; virtual int set_goal(const double* in) = 0; virtual int get_clips(int* out) = 0; virtual int set_clips(const int* in) = 0;
+    virtual int goal_state(double* out, const double* in) = 0; virtual int clips(int* out, const int* in) = 0; virtual int need_new_action(int* out) = 0;
     virtual int goal_aux(double* out, const double* in) = 0; virtual void set_mode(int test) = 0; virtual int pert_state(double* out, const double* in) = 0;
     virtual int obj_state(double* out, const double* in) = 0;
     virtual int manifolds(double* out, const double* in) = 0;
-    virtual int amp_expert_clips(int n, const int* clips_dev, const double* times_dev, const double* gh_dev, float* out_dev) = 0;
+    virtual int amp_expert_clips(int n, const int* clips_dev /* null: the model's own clip */, const double* times_dev, const double* gh_dev, float* out_dev) = 0;
     virtual int probe(int what, double dt) = 0;
     virtual int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) = 0;
     virtual int set_state(const double* pose, const double* vel, const double* tar, const double* kin, const double* clk, const int* flg) = 0;
@@ -586,77 +590,91 @@ struct CtxT : CtxBase {
         launch_table<Real>().reset[cls](n, stream, md, st, ids_dev, kt_dev, mt_dev);
         return 0;
     }
-    int step(const float* actions_dev, double dt, int n_updates, float* states, float* rewards, int* term, int* valid, int* end, int flags, float* amp) override {
+    // Packing: two characters per wavefront?  One rule for step() and for the profiled step of dm_probe 3 / 4 (for_taps), which differ where marked.
+    bool two_per_wave(bool for_taps) const {
+        // both: the ctx allows it (DM_DUO=0 / wave_packing 1 / an odd env_id_offset keep one character per wave), exactly 34 dofs (31 row lanes per character
+        // assume them), an even batch
+        if (!duo || hm.D != ClsBiped::ND || (N % 2) != 0) return false;
+        // dm_probe: the tap variant has a two-per-wave family for the biped class only (dm_families.h: no (2, ClsBipedObj, SV_TAPS) row), so there is no
+        // free-body arm; and it keeps one character per wave under DM-physics v2 for the biped class too, where step() runs the two-per-wave v2 family
+        // (family 22) -- the tap instantiation carries no manifold code.  The three terms below are not tested: !dbg.H cannot hold (probe() has just armed
+        // the taps) and step_ids is set only inside dm_step_envs, both vacuous; a bound draw tape is NOT vacuous -- see docs/HISTORY.md, behaviour kept.
+        if (for_taps) return cls == kClsBiped && !st.manif;
+        // step(): no debug taps armed (a parity test reads one env per wave), the whole batch (dm_step_envs runs a subset through env_ids, which only the
+        // one-per-wave kernels read), no draw tape (read by the one-per-wave kernels only -- EnvSim::tape())
+        if (dbg.H || step_ids || md.draw_tape) return false;
+        // biped + free body (dribble_amp) only under DM-physics v1 (v2 keeps the one-per-wave kernel); DM_DUO_OBJ=0: one per wave
+        return cls == kClsBiped || (duo_obj && cls == kClsBipedObj && !st.manif);
+    }
+    StepIO<Real> make_io(const StepOut& o) const {
         StepIO<Real> io; memset(&io, 0, sizeof(io));
-        io.amp_obs = amp; io.goals = d_goals;
-        io.actions = actions_dev; io.states = states; io.rewards = rewards; io.terminate = term; io.valid = valid; io.episode_end = end;
+        io.amp_obs = o.amp; io.goals = d_goals;
+        io.states = o.states; io.rewards = o.rewards; io.terminate = o.term; io.valid = o.valid; io.episode_end = o.end;
+        return io;
+    }
+    int step(const float* actions_dev, double dt, int n_updates, const StepOut& out_dev, int flags) override {
+        StepIO<Real> io = make_io(out_dev);
+        io.actions = actions_dev;
         io.env_ids = step_ids; const int GN = step_ids ? step_n_ids : N;      // workgroups of the one-per-wave launches
         if (md.draw_tape && (flags & DM_AUTO_RESET)) return fail("a draw tape is bound (dm_set_draw_tape): resets go through dm_reset, where the tape serves the reference's draw order");
         io.n_updates = n_updates; io.dt = dt; io.auto_reset = (flags & DM_AUTO_RESET) ? 1 : 0; io.emit = (flags & DM_NO_EMIT) ? 0 : 1; io.open_loop = (flags & DM_OPEN_LOOP) ? 1 : 0; io.end_early = (flags & DM_END_EPISODE_EARLY) ? 1 : 0;
-        // Packing.  Two characters per wavefront: biped class of exactly 34 dofs (31 row lanes per character assume them), even batch, no debug taps armed, the whole
-        // batch, no draw tape (a bound tape is read by the one-per-wave kernels only -- EnvSim::tape() -- so such a batch takes them); DM_DUO=0 keeps one character per wave.
-        // Biped + free body (dribble_amp) only under DM-physics v1 (v2 keeps the one-per-wave kernel); DM_DUO_OBJ=0: one per wave
-        const bool two = (duo && cls == kClsBiped && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape) ||
-                         (duo && duo_obj && cls == kClsBipedObj && hm.D == ClsBiped::ND && (N % 2) == 0 && !dbg.H && !step_ids && !md.draw_tape && !st.manif);
         // Variant.  The tap instantiation only when a parity test armed the debug taps (dm_probe); DM-physics v2 has its own (AMP code + manifolds); the AMP
         // instantiation also carries the perturbation code; ClsBipedObj has no plain family
         int variant = dbg.H ? SV_TAPS : st.manif ? SV_V2 : (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) ? SV_AMP : SV_PLAIN;
         if (variant == SV_PLAIN && cls == kClsBipedObj) variant = SV_AMP;
-        return two ? launch_step(variant, 2, N / 2, io, dbg) : launch_step(variant, 1, GN, io, dbg);
+        return two_per_wave(false) ? launch_step(variant, 2, N / 2, io, dbg) : launch_step(variant, 1, GN, io, dbg);
     }
-    int amp_expert(int n, const double* times_dev, const double* gh_dev, float* out_dev) override { return amp_expert_clips(n, nullptr, times_dev, gh_dev, out_dev); }
     int amp_expert_clips(int n, const int* clips_dev, const double* times_dev, const double* gh_dev, float* out_dev) override {
         launch_table<Real>().expert[cls](n, stream, md, times_dev, gh_dev, out_dev, clips_dev);      // (the expert of the base class)
         return 0;
     }
-    int get_goal(double* out) override {
-        if (!st.goal) return fail("no goal state: not a goal scene / multi-clip dataset");
-        std::vector<double> g((size_t)N * GS_WIDTH);
-        if (rt_d2h(g.data(), st.goal, sizeof(double) * g.size(), stream) != 0) return fail("device to host copy failed");
-        for (int e = 0; e < N; ++e) for (int k = 0; k < 12; ++k) out[(size_t)e * 12 + k] = g[(size_t)e * GS_WIDTH + k];
-        return 0;
+    // ---- the one copy between a strided per-row device table and the caller's compact host rows
+    // Row r of the window is device columns [col, col + w) of row r (`stride` elements apart) and host columns [0, w) of a `hw`-wide host row; host columns
+    // w .. hw - 1 read 0 and are ignored on a write.  Elements are converted with a cast.  A write says what happens to the device columns outside the window.
+    enum Pad { KeepPad, ZeroPad };
+    struct Win { size_t n, stride, col, w, hw; };
+    // Always whole-table copies on the ctx stream: a read is one download; a KeepPad write one download and one upload; a ZeroPad write one upload.
+    template <typename H, typename D> int rows(D* dev, const Win& win, H* out, const H* in, Pad pad) {      // (a call with a null side names H: rows<double>(...))
+        std::vector<D> t(win.n * win.stride);      // (zero-filled)
+        if ((out || (in && pad == KeepPad)) && rt_d2h(t.data(), dev, sizeof(D) * t.size(), stream) != 0) return fail("device to host copy failed");
+        if (out) for (size_t r = 0; r < win.n; ++r) for (size_t k = 0; k < win.hw; ++k) out[r * win.hw + k] = (k < win.w) ? (H)t[r * win.stride + win.col + k] : (H)0;
+        if (!in) return 0;
+        if (out && pad == ZeroPad) std::fill(t.begin(), t.end(), (D)0);
+        for (size_t r = 0; r < win.n; ++r) for (size_t k = 0; k < win.w; ++k) t[r * win.stride + win.col + k] = (D)in[r * win.hw + k];
+        return rt_h2d(dev, t.data(), sizeof(D) * t.size(), stream) == 0 ? 0 : fail("host to device copy failed");
     }
-    int set_goal(const double* in) override {
-        if (!st.goal) return fail("no goal state: not a goal scene / multi-clip dataset");
-        std::vector<double> g((size_t)N * GS_WIDTH);
-        if (rt_d2h(g.data(), st.goal, sizeof(double) * g.size(), stream) != 0) return fail("device to host copy failed");
-        for (int e = 0; e < N; ++e) for (int k = 0; k < 12; ++k) g[(size_t)e * GS_WIDTH + k] = in[(size_t)e * 12 + k];
-        return rt_h2d(st.goal, g.data(), sizeof(double) * g.size(), stream) == 0 ? 0 : fail("host to device copy failed");
+    // a whole table of n elements: the full-width window
+    template <typename D, typename H> int dl(D* dev, size_t n, H* out) { return rows<H>(dev, Win{1, n, 0, n, n}, out, nullptr, KeepPad); }
+    template <typename D, typename H> int ul(D* dev, size_t n, const H* in) { return rows<H>(dev, Win{1, n, 0, n, n}, nullptr, in, ZeroPad); }
+
+    int no_goal() const { return fail("no goal state: not a goal scene / multi-clip dataset"); }
+    int goal_state(double* out, const double* in) override {          // N x 12: GS_TX .. GS_DRAWS
+        return st.goal ? rows(st.goal, Win{(size_t)N, GS_WIDTH, 0, 12, 12}, out, in, KeepPad) : no_goal();
     }
     int goal_aux(double* out, const double* in) override {
-        if (!st.goal) return fail("no goal state: not a goal scene / multi-clip dataset");
-        std::vector<double> g((size_t)N * GS_WIDTH);
-        if (rt_d2h(g.data(), st.goal, sizeof(double) * g.size(), stream) != 0) return fail("device to host copy failed");
         // the 7 scene-specific columns GS_AUX0 .. GS_OTIMER_MAX; column 7 of the 8-wide interface row is reserved (reads 0, writes are ignored): the goal row's next
         // slot is the env's own draw key (GS_KSEED, dm_set_env_keys), which a restored aux block must not re-key
         static_assert(GS_AUX0 + 7 == GS_KSEED, "the aux window ends where the draw key starts");
-        if (out) for (int e = 0; e < N; ++e) for (int k = 0; k < 8; ++k) out[(size_t)e * 8 + k] = (k < 7) ? g[(size_t)e * GS_WIDTH + GS_AUX0 + k] : 0.0;
-        if (in) {
-            for (int e = 0; e < N; ++e) for (int k = 0; k < 7; ++k) g[(size_t)e * GS_WIDTH + GS_AUX0 + k] = in[(size_t)e * 8 + k];
-            if (rt_h2d(st.goal, g.data(), sizeof(double) * g.size(), stream) != 0) return fail("host to device copy failed");
-        }
-        return 0;
+        return st.goal ? rows(st.goal, Win{(size_t)N, GS_WIDTH, GS_AUX0, 7, 8}, out, in, KeepPad) : no_goal();
     }
+    int clips(int* out, const int* in) override {                     // N: GS_CLIP, the clip the env was reset to
+        if (!st.goal) { if (in) return no_goal(); for (int e = 0; e < N; ++e) out[e] = 0; return 0; }
+        for (int e = 0; in && e < N; ++e) if (in[e] < 0 || in[e] >= hm.num_clips) return fail("clip id out of range");
+        return rows(st.goal, Win{(size_t)N, GS_WIDTH, GS_CLIP, 1, 1}, out, in, KeepPad);
+    }
+    int need_new_action(int* out) override { return rows<int>(st.flag, Win{(size_t)N, 4, 0, 1, 1}, out, nullptr, KeepPad) ? fail("copy failed") : 0; }      // column 0 of the flag rows
     void set_mode(int test) override { md.mode_test = test ? 1 : 0; }
     int obj_state(double* out, const double* in) override {          // N x 13: pos, rot wxyz, vel, ang vel of the free body
-        if (!st.obj) return fail("no free body: not a dribble_amp scene");
-        std::vector<Real> o((size_t)N * OB_WIDTH);
-        if (rt_d2h(o.data(), st.obj, sizeof(Real) * o.size(), stream) != 0) return fail("device to host copy failed");
-        if (out) for (int e = 0; e < N; ++e) for (int k = 0; k < 13; ++k) out[(size_t)e * 13 + k] = (double)o[(size_t)e * OB_WIDTH + k];
-        if (in) {
-            for (int e = 0; e < N; ++e) for (int k = 0; k < 13; ++k) o[(size_t)e * OB_WIDTH + k] = (Real)in[(size_t)e * 13 + k];
-            if (rt_h2d(st.obj, o.data(), sizeof(Real) * o.size(), stream) != 0) return fail("host to device copy failed");
-        }
-        return 0;
+        return st.obj ? rows(st.obj, Win{(size_t)N, OB_WIDTH, 0, 13, 13}, out, in, KeepPad) : fail("no free body: not a dribble_amp scene");
     }
     // dm_set_env_keys: the listed envs become what env 0 of a fresh one-env context created with seeds[i] would be BEFORE its first reset: draw key (seed, env 0)
     // in the goal / perturbation rows, draw counters and the episode counter back to 0, no manifolds.  The caller resets them next (dm_create does the same).
     int set_env_keys(const int* ids, int n, const uint64_t* seeds) override {
         if (rt_sync(stream) != 0) return fail("stream synchronize failed");
         std::vector<double> g, p; std::vector<int> f((size_t)N * 4);
-        if (st.goal) { g.resize((size_t)N * GS_WIDTH); if (rt_d2h(g.data(), st.goal, sizeof(double) * g.size(), stream) != 0) return fail("device to host copy failed"); }
-        if (st.pert) { p.resize((size_t)N * PT_WIDTH); if (rt_d2h(p.data(), st.pert, sizeof(double) * p.size(), stream) != 0) return fail("device to host copy failed"); }
-        if (rt_d2h(f.data(), st.flag, sizeof(int) * f.size(), stream) != 0) return fail("device to host copy failed");
+        if (st.goal) { g.resize((size_t)N * GS_WIDTH); if (dl(st.goal, g.size(), g.data())) return -1; }
+        if (st.pert) { p.resize((size_t)N * PT_WIDTH); if (dl(st.pert, p.size(), p.data())) return -1; }
+        if (dl(st.flag, f.size(), f.data())) return -1;
         for (int i = 0; i < n; ++i) {
             const int e = ids[i];
             if (e < 0 || e >= N) return fail("dm_set_env_keys: env id out of range");
@@ -665,9 +683,7 @@ struct CtxT : CtxBase {
             if (st.pert) { double* r = &p[(size_t)e * PT_WIDTH]; for (int k = 0; k < PT_WIDTH; ++k) r[k] = 0; r[PT_KSEED] = (double)seeds[i] + 1.0; }
             f[(size_t)e * 4 + 2] = 0;
         }
-        if (st.goal && rt_h2d(st.goal, g.data(), sizeof(double) * g.size(), stream) != 0) return fail("host to device copy failed");
-        if (st.pert && rt_h2d(st.pert, p.data(), sizeof(double) * p.size(), stream) != 0) return fail("host to device copy failed");
-        if (rt_h2d(st.flag, f.data(), sizeof(int) * f.size(), stream) != 0) return fail("host to device copy failed");
+        if ((st.goal && ul(st.goal, g.size(), g.data())) || (st.pert && ul(st.pert, p.size(), p.data())) || ul(st.flag, f.size(), f.data())) return -1;
         if (st.manif) {
             std::vector<Real> mz((size_t)hm.J * MF_STRIDE, (Real)0);
             for (int i = 0; i < n; ++i) if (rt_h2d(st.manif + (size_t)ids[i] * hm.J * MF_STRIDE, mz.data(), sizeof(Real) * mz.size(), stream) != 0) return fail("host to device copy failed");
@@ -725,39 +741,11 @@ struct CtxT : CtxBase {
         if (in && rt_h2d(st.pert, in, bytes, stream) != 0) return fail("host to device copy failed");
         return 0;
     }
-    int manifolds(double* out, const double* in) override {           // N x J x 25: count, 4 x (body-frame point (3), plane point x z, distance)
-        if (!st.manif) return fail("no manifold state: the ctx does not run DM-physics v2");
-        const size_t n = (size_t)N * hm.J;
-        std::vector<Real> buf(n * MF_STRIDE);
-        if (out) {
-            if (rt_d2h(buf.data(), st.manif, sizeof(Real) * buf.size(), stream) != 0) return fail("device to host copy failed");
-            for (size_t i = 0; i < n; ++i) for (int k = 0; k < 25; ++k) out[i * 25 + k] = (double)buf[i * MF_STRIDE + k];
-        }
-        if (in) {
-            std::fill(buf.begin(), buf.end(), (Real)0);
-            for (size_t i = 0; i < n; ++i) for (int k = 0; k < 25; ++k) buf[i * MF_STRIDE + k] = (Real)in[i * 25 + k];
-            if (rt_h2d(st.manif, buf.data(), sizeof(Real) * buf.size(), stream) != 0) return fail("host to device copy failed");
-        }
-        return 0;
+    int manifolds(double* out, const double* in) override {           // N x J x 25: count, 4 x (body-frame point (3), plane point x z, distance); a write zeroes columns 25 .. 31
+        return st.manif ? rows(st.manif, Win{(size_t)N * hm.J, MF_STRIDE, 0, 25, 25}, out, in, ZeroPad) : fail("no manifold state: the ctx does not run DM-physics v2");
     }
-    int set_clips(const int* in) override {
-        if (!st.goal) return fail("no goal state: not a goal scene / multi-clip dataset");
-        std::vector<double> g((size_t)N * GS_WIDTH);
-        if (rt_d2h(g.data(), st.goal, sizeof(double) * g.size(), stream) != 0) return fail("device to host copy failed");
-        for (int e = 0; e < N; ++e) { if (in[e] < 0 || in[e] >= hm.num_clips) return fail("clip id out of range"); g[(size_t)e * GS_WIDTH + GS_CLIP] = (double)in[e]; }
-        return rt_h2d(st.goal, g.data(), sizeof(double) * g.size(), stream) == 0 ? 0 : fail("host to device copy failed");
-    }
-    int get_clips(int* out) override {
-        if (!st.goal) { for (int e = 0; e < N; ++e) out[e] = 0; return 0; }
-        std::vector<double> g((size_t)N * GS_WIDTH);
-        if (rt_d2h(g.data(), st.goal, sizeof(double) * g.size(), stream) != 0) return fail("device to host copy failed");
-        for (int e = 0; e < N; ++e) out[e] = (int)g[(size_t)e * GS_WIDTH + GS_CLIP];
-        return 0;
-    }
-    int query(float* states, float* rewards, int* term, int* valid, int* end, float* amp) override {
-        StepIO<Real> io; memset(&io, 0, sizeof(io));
-        io.amp_obs = amp; io.goals = d_goals;
-        io.states = states; io.rewards = rewards; io.terminate = term; io.valid = valid; io.episode_end = end; io.emit = 1;
+    int query(const StepOut& out_dev) override {
+        StepIO<Real> io = make_io(out_dev); io.emit = 1;
         launch_table<Real>().query[cls](N, stream, md, st, io, dbg);
         return 0;
     }
@@ -766,31 +754,21 @@ struct CtxT : CtxBase {
         if (what == 3 || what == 4) {   // one profiled control step (20 updates; 3: open-loop, 4: the actions of the last dm_step_batch): per-phase cycle counts -> tap "prof"
             rt_memset(d_prof, 0, sizeof(long long) * N * 16, stream);
             DebugTaps<Real> d2; memset(&d2, 0, sizeof(d2)); d2.prof = d_prof;
-            StepIO<Real> io; memset(&io, 0, sizeof(io));
-            io.states = d_states; io.rewards = d_rewards; io.terminate = d_term; io.valid = d_valid; io.episode_end = d_end;
+            StepIO<Real> io = make_io(dev_out(false)); io.goals = nullptr;
             io.n_updates = 20; io.dt = dt; io.auto_reset = 1; io.emit = 1; io.open_loop = (what == 3) ? 1 : 0; io.end_early = 1;
             if (what == 4) io.actions = d_actions;
-            return (duo && cls == kClsBiped && hm.D == ClsBiped::ND && (N % 2) == 0 && !st.manif) ? launch_step(SV_TAPS, 2, N / 2, io, d2) : launch_step(SV_TAPS, 1, N, io, d2);
+            return two_per_wave(true) ? launch_step(SV_TAPS, 2, N / 2, io, d2) : launch_step(SV_TAPS, 1, N, io, d2);
         }
         launch_table<Real>().probe[cls](N, stream, md, st, dbg, what, dt);
         return 0;
-    }
-    template <typename T> int dl(const T* dev, size_t n, double* out) {
-        std::vector<T> tmp(n); if (rt_d2h(tmp.data(), dev, sizeof(T) * n, stream) != 0) return fail("device to host copy failed");
-        for (size_t i = 0; i < n; ++i) out[i] = (double)tmp[i];
-        return 0;
-    }
-    template <typename T> int ul(T* dev, size_t n, const double* in) {
-        std::vector<T> tmp(n); for (size_t i = 0; i < n; ++i) tmp[i] = (T)in[i];
-        return rt_h2d(dev, tmp.data(), sizeof(T) * n, stream) == 0 ? 0 : fail("host to device copy failed");
     }
     int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) override {
         const size_t n = N; const int P = hm.P;
         if (pose && dl(st.pose, n * P, pose)) return -1;
         if (vel && dl(st.vel, n * P, vel)) return -1;
         if (tar && dl(st.tar, n * P, tar)) return -1;
-        if (kin) { std::vector<double> t8(n * 8); if (dl(st.kin, n * 8, t8.data())) return -1; for (size_t e = 0; e < n; ++e) for (int k = 0; k < 7; ++k) kin[e * 7 + k] = t8[e * 8 + k]; }
-        if (clk) { std::vector<double> t6(n * 6); if (rt_d2h(t6.data(), st.clock, sizeof(double) * n * 6, stream)) return fail("copy failed"); for (size_t e = 0; e < n; ++e) for (int k = 0; k < 5; ++k) clk[e * 5 + k] = t6[e * 6 + k]; }
+        if (kin && rows<double>(st.kin, Win{n, 8, 0, 7, 7}, kin, nullptr, KeepPad)) return -1;
+        if (clk && rows<double>(st.clock, Win{n, 6, 0, 5, 5}, clk, nullptr, KeepPad)) return fail("copy failed");
         if (flg && rt_d2h(flg, st.flag, sizeof(int) * n * 4, stream)) return fail("copy failed");
         return 0;
     }
@@ -800,8 +778,9 @@ struct CtxT : CtxBase {
         if (pose && st.manif && rt_memset(st.manif, 0, sizeof(Real) * n * hm.J * MF_STRIDE, stream)) return fail("memset failed");      // a new pose starts with empty manifolds (physics 2)
         if (vel && ul(st.vel, n * P, vel)) return -1;
         if (tar && ul(st.tar, n * P, tar)) return -1;
-        if (kin) { std::vector<double> t8(n * 8, 0); for (size_t e = 0; e < n; ++e) for (int k = 0; k < 7; ++k) t8[e * 8 + k] = kin[e * 7 + k]; if (ul(st.kin, n * 8, t8.data())) return -1; }
-        if (clk) { std::vector<double> t6(n * 6, 0); for (size_t e = 0; e < n; ++e) for (int k = 0; k < 5; ++k) t6[e * 6 + k] = clk[e * 5 + k]; if (rt_h2d(st.clock, t6.data(), sizeof(double) * n * 6, stream)) return fail("copy failed"); }
+        // both writes zero the counter column next to the window (kin column 7: "fallback", clock column 5: "borrowed"): they count since dm_create or the last dm_set_state
+        if (kin && rows<double>(st.kin, Win{n, 8, 0, 7, 7}, nullptr, kin, ZeroPad)) return -1;
+        if (clk && rows<double>(st.clock, Win{n, 6, 0, 5, 5}, nullptr, clk, ZeroPad)) return fail("copy failed");
         if (flg && rt_h2d(st.flag, flg, sizeof(int) * n * 4, stream)) return fail("copy failed");
         return 0;
     }
@@ -816,14 +795,10 @@ struct CtxT : CtxBase {
             return 0;
         }
         if (s == "borrowed") {      // N: substeps the env's pair ran with one character's rows 32.. on lanes borrowed from its partner's half (two-per-wave kernel, DuoSim::substep_rows_xd)
-            std::vector<double> t6(n * 6); if (rt_d2h(t6.data(), st.clock, sizeof(double) * n * 6, stream)) return fail("copy failed");
-            for (size_t e = 0; e < n; ++e) out[e] = t6[e * 6 + 5];
-            return 0;
+            return rows<double>(st.clock, Win{n, 6, 5, 1, 1}, out, nullptr, KeepPad) ? fail("copy failed") : 0;
         }
         if (s == "fallback") {      // N: substeps the env's pair ran on the 64-lane fallback of the two-per-wave kernel since dm_create / the last dm_set_state (0 for the one-per-wave kernels)
-            std::vector<double> t8(n * 8); if (dl(st.kin, n * 8, t8.data())) return -1;
-            for (size_t e = 0; e < n; ++e) out[e] = t8[e * 8 + 7];
-            return 0;
+            return rows<double>(st.kin, Win{n, 8, 7, 1, 1}, out, nullptr, KeepPad);
         }
         if (!dbg.H) return fail("no debug taps recorded yet (call dm_probe first)");
         if (s == "H") return dl(dbg.H, n * h.D * h.D, out);
@@ -841,6 +816,50 @@ struct CtxT : CtxBase {
 };
 
 struct dm_ctx { CtxBase* c; };
+
+// ---------------------------------------------------------------- what the C-ABI functions share
+// null check, the ctx's device current, forward: f(CtxBase*) -> int.  With an argument that must not be null the message is "null argument", else "null ctx".
+template <typename F> static int guarded(const dm_ctx* ctx, F&& f) { if (!ctx) return fail("null ctx"); DevGuard guard(ctx->c->device_id); return f(ctx->c); }
+template <typename F> static int guarded(const dm_ctx* ctx, const void* arg, F&& f) { if (!ctx || !arg) return fail("null argument"); DevGuard guard(ctx->c->device_id); return f(ctx->c); }
+static bool need_amp(const CtxBase* c) { if (!c->amp_size) fail("AMP observations need a `--scene imitate_amp` context (dm_scene_tables.scene_amp)"); return c->amp_size != 0; }
+static bool need_goal(const CtxBase* c) { if (!c->goal_size) fail("RecordGoal needs a goal scene (dm_scene_tables.scene_goal)"); return c->goal_size != 0; }
+
+// A device temporary of one call: allocated, filled from `host` when given, freed with the scope.  `rc` is the call's status: a temporary after a failed one is
+// not made, and the caller launches nothing unless rc is still 0 -- a failed allocation must not reach a kernel as a null pointer ("NULL = all envs" in dm_reset).
+struct DevTmp {
+    void* p = nullptr;
+    DevTmp(int& rc, rt_stream s, size_t bytes, const void* host, bool alloc_only = false) {      // null `host`: no temporary, unless it is an output (alloc_only)
+        if (rc || !(host || alloc_only)) return;
+        if (rt_malloc(&p, bytes) != 0) { if (p) rt_free(p); p = nullptr; rc = fail("device allocation failed"); return; }
+        if (host && rt_h2d(p, host, bytes, s) != 0) rc = fail("copy failed");
+    }
+    ~DevTmp() { if (p) rt_free(p); }
+    DevTmp(const DevTmp&) = delete; DevTmp& operator=(const DevTmp&) = delete;
+};
+
+// ---- the one step / query I/O path
+static int copy_out(CtxBase* c, void* host, const void* dev, size_t bytes) { return (host && rt_d2h(host, dev, bytes, c->stream)) ? fail("copy failed") : 0; }
+// whatever of `h` is non-null, from the ctx's own output buffers
+static int copy_back(CtxBase* c, const StepOut& h) {
+    const size_t N = c->N;
+    return (copy_out(c, h.states, c->d_states, sizeof(float) * N * c->hm.S) || copy_out(c, h.rewards, c->d_rewards, sizeof(float) * N) || copy_out(c, h.term, c->d_term, sizeof(int) * N) ||
+            copy_out(c, h.valid, c->d_valid, sizeof(int) * N) || copy_out(c, h.end, c->d_end, sizeof(int) * N) || copy_out(c, h.amp, c->d_amp, sizeof(float) * N * c->amp_size)) ? -1 : 0;
+}
+// One control step.  Device pointers (DM_DEVICE_PTRS) go to the kernel as they are; host pointers: `act_rows` rows of actions are staged, the kernel writes the
+// ctx's own buffers (all five outputs, AMP observations when asked for) and whatever of `out` is non-null is copied back, whole arrays.
+static int step_io(CtxBase* c, const float* actions, int act_rows, double dt, int n_updates, const StepOut& out, int flags) {
+    if (out.amp && !need_amp(c)) return -1;
+    if (flags & DM_DEVICE_PTRS) return launch_status(c->step(actions, dt, n_updates, out, flags));
+    if (actions && rt_h2d(c->d_actions, actions, sizeof(float) * (size_t)act_rows * c->hm.A, c->stream)) return fail("copy failed");
+    if (launch_status(c->step(actions ? c->d_actions : nullptr, dt, n_updates, c->dev_out(out.amp != nullptr), flags))) return -1;
+    return copy_back(c, out);
+}
+// the query kernel's side of it: with host pointers the kernel emits into `own`, the ctx's buffers for what `out` may ask for
+static int query_io(CtxBase* c, const StepOut& out, const StepOut& own, int flags) {
+    if (flags & DM_DEVICE_PTRS) return launch_status(c->query(out));
+    if (launch_status(c->query(own))) return -1;
+    return copy_back(c, out);
+}
 
 // ---------------------------------------------------------------- C-ABI
 extern "C" {
@@ -954,7 +973,7 @@ int dm_get_stream(const dm_ctx* ctx, void** out_own, void** out_current) {
     if (out_current) *out_current = (void*)ctx->c->stream;
     return 0;
 }
-int dm_synchronize(dm_ctx* ctx) { if (!ctx) return fail("null ctx"); DevGuard guard(ctx->c->device_id); return rt_sync(ctx->c->stream) == 0 ? 0 : fail("stream synchronize failed"); }
+int dm_synchronize(dm_ctx* ctx) { return guarded(ctx, [&](CtxBase* c) { return rt_sync(c->stream) == 0 ? 0 : fail("stream synchronize failed"); }); }
 
 int dm_set_timer_exp(dm_ctx* ctx, double time_lim_exp) {
     if (!ctx) return fail("null ctx");
@@ -977,89 +996,61 @@ int dm_reset(dm_ctx* ctx, const int32_t* env_ids, int n, const double* kin_times
     if (n <= 0) return 0;
     for (int i = 0; env_ids && i < n; ++i) if (env_ids[i] < 0 || env_ids[i] >= c->N) return fail("env id out of range");
     int rc = 0;
-    void* tmp[3] = {nullptr, nullptr, nullptr};
-    auto stage = [&](int k, const void* host, size_t bytes) {      // a failed allocation must not reach the kernel as "NULL = all envs"
-        if (!host || rc) return;
-        if (rt_malloc(&tmp[k], bytes) != 0) { tmp[k] = nullptr; rc = fail("device allocation failed"); return; }
-        if (rt_h2d(tmp[k], host, bytes, c->stream) != 0) rc = fail("copy failed");
-    };
-    stage(0, env_ids, sizeof(int) * n); stage(1, kin_times, sizeof(double) * n); stage(2, max_times, sizeof(double) * n);
-    if (!rc) rc = launch_status(c->reset((const int*)tmp[0], n, (const double*)tmp[1], (const double*)tmp[2]));
+    DevTmp ids(rc, c->stream, sizeof(int) * n, env_ids), kt(rc, c->stream, sizeof(double) * n, kin_times), mt(rc, c->stream, sizeof(double) * n, max_times);
+    if (!rc) rc = launch_status(c->reset((const int*)ids.p, n, (const double*)kt.p, (const double*)mt.p));
     if (rt_sync(c->stream) != 0 && !rc) rc = fail("stream synchronize failed");
-    for (void* p : tmp) if (p) rt_free(p);
     return rc;
 }
 
 int dm_set_action(dm_ctx* ctx, const float* actions, int flags) {
-    if (!ctx || !actions) return fail("null argument");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    const float* adev = actions;
-    if (!(flags & DM_DEVICE_PTRS)) { if (rt_h2d(c->d_actions, actions, sizeof(float) * c->N * c->hm.A, c->stream)) return fail("copy failed"); adev = c->d_actions; }
-    return launch_status(c->step(adev, 0.0, 0, nullptr, nullptr, nullptr, nullptr, nullptr, DM_NO_EMIT));
+    return guarded(ctx, actions, [&](CtxBase* c) {
+        const bool host = !(flags & DM_DEVICE_PTRS);
+        if (host && rt_h2d(c->d_actions, actions, sizeof(float) * c->N * c->hm.A, c->stream)) return fail("copy failed");
+        return launch_status(c->step(host ? c->d_actions : actions, 0.0, 0, StepOut{}, DM_NO_EMIT));
+    });
 }
 
 int dm_update(dm_ctx* ctx, double timestep, int n_updates) {
     if (!ctx) return fail("null ctx");
     if (n_updates < 1 || !(timestep > 0)) return 0;   // cImpPDController::UpdateControlForce ignores non-positive steps
-    DevGuard guard(ctx->c->device_id);
-    return launch_status(ctx->c->step(nullptr, timestep, n_updates, nullptr, nullptr, nullptr, nullptr, nullptr, DM_NO_EMIT));
+    return guarded(ctx, [&](CtxBase* c) { return launch_status(c->step(nullptr, timestep, n_updates, StepOut{}, DM_NO_EMIT)); });
 }
 
-static int copy_out(CtxBase* c, void* host, const void* dev, size_t bytes) { return (host && rt_d2h(host, dev, bytes, c->stream)) ? fail("copy failed") : 0; }
-
 int dm_query(dm_ctx* ctx, float* states, float* rewards, int32_t* terminate, int32_t* valid, int32_t* episode_end, int32_t* need_new_action, int flags) {
-    if (!ctx) return fail("null ctx");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (flags & DM_DEVICE_PTRS) { if (launch_status(c->query(states, rewards, terminate, valid, episode_end))) return -1; }
-    else {
-        if (launch_status(c->query(c->d_states, c->d_rewards, c->d_term, c->d_valid, c->d_end))) return -1;
-        if (copy_out(c, states, c->d_states, sizeof(float) * c->N * c->hm.S) || copy_out(c, rewards, c->d_rewards, sizeof(float) * c->N) ||
-            copy_out(c, terminate, c->d_term, sizeof(int) * c->N) || copy_out(c, valid, c->d_valid, sizeof(int) * c->N) || copy_out(c, episode_end, c->d_end, sizeof(int) * c->N)) return -1;
-    }
-    if (need_new_action) {
-        std::vector<int> flg((size_t)c->N * 4);
-        if (c->get_state(nullptr, nullptr, nullptr, nullptr, nullptr, flg.data())) return -1;
-        for (int e = 0; e < c->N; ++e) need_new_action[e] = flg[(size_t)e * 4];
-    }
-    return 0;
+    return guarded(ctx, [&](CtxBase* c) {
+        if (query_io(c, StepOut{states, rewards, terminate, valid, episode_end, nullptr}, c->dev_out(false), flags)) return -1;
+        return need_new_action ? c->need_new_action(need_new_action) : 0;
+    });
 }
 
 int dm_step_batch(dm_ctx* ctx, const float* actions, double timestep, int n_updates, float* states, float* rewards,
                   int32_t* terminate, int32_t* valid, int32_t* episode_end, int flags) {
-    if (!ctx) return fail("null ctx");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (flags & DM_DEVICE_PTRS) return launch_status(c->step(actions, timestep, n_updates, states, rewards, terminate, valid, episode_end, flags));
-    const float* adev = nullptr;
-    if (actions) { if (rt_h2d(c->d_actions, actions, sizeof(float) * c->N * c->hm.A, c->stream)) return fail("copy failed"); adev = c->d_actions; }
-    if (launch_status(c->step(adev, timestep, n_updates, c->d_states, c->d_rewards, c->d_term, c->d_valid, c->d_end, flags))) return -1;
-    if (copy_out(c, states, c->d_states, sizeof(float) * c->N * c->hm.S) || copy_out(c, rewards, c->d_rewards, sizeof(float) * c->N) ||
-        copy_out(c, terminate, c->d_term, sizeof(int) * c->N) || copy_out(c, valid, c->d_valid, sizeof(int) * c->N) || copy_out(c, episode_end, c->d_end, sizeof(int) * c->N)) return -1;
-    return 0;
+    return dm_step_batch_amp(ctx, actions, timestep, n_updates, states, rewards, terminate, valid, episode_end, nullptr, flags);
+}
+int dm_step_batch_amp(dm_ctx* ctx, const float* actions, double timestep, int n_updates, float* states, float* rewards,
+                      int32_t* terminate, int32_t* valid, int32_t* episode_end, float* amp_obs, int flags) {
+    return guarded(ctx, [&](CtxBase* c) { return step_io(c, actions, c->N, timestep, n_updates, StepOut{states, rewards, terminate, valid, episode_end, amp_obs}, flags); });
 }
 
 int dm_step_envs(dm_ctx* ctx, const int32_t* env_ids, int n, const float* actions, double timestep, int n_updates, float* states, float* rewards,
                  int32_t* terminate, int32_t* valid, int32_t* episode_end, float* amp_obs, double* clocks, int flags) {
     if (!ctx || !env_ids) return fail("null argument");
     CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    const int N = c->N, S = c->hm.S, A = c->hm.A;
+    const int N = c->N, S = c->hm.S;
     if (n < 1 || n > N) return fail("dm_step_envs: n must be in [1, num_envs]");
     if (flags & DM_DEVICE_PTRS) return fail("dm_step_envs takes host pointers");
-    if (amp_obs && !c->amp_size) return fail("AMP observations need a `--scene imitate_amp` context (dm_scene_tables.scene_amp)");
+    if (amp_obs && !need_amp(c)) return -1;
     std::vector<char> seen((size_t)N, 0);
     for (int i = 0; i < n; ++i) { const int e = env_ids[i]; if (e < 0 || e >= N || seen[e]) return fail("dm_step_envs: env ids must be distinct and in [0, num_envs)"); seen[e] = 1; }
     if (!c->d_ids) { c->d_ids = (int*)c->dalloc(sizeof(int) * (size_t)N); if (!c->d_ids) return fail("device allocation failed"); }
     if (rt_h2d(c->d_ids, env_ids, sizeof(int) * (size_t)n, c->stream)) return fail("copy failed");
-    const float* adev = nullptr;
-    if (actions) { if (rt_h2d(c->d_actions, actions, sizeof(float) * (size_t)n * A, c->stream)) return fail("copy failed"); adev = c->d_actions; }      // compact: row i = env_ids[i]
+    // the kernels write every output at the env's own row: take the whole arrays back and hand out the rows asked for (the actions are compact: row i = env_ids[i])
+    std::vector<float> hs(states ? (size_t)N * S : 0), hr(rewards ? N : 0), ha(amp_obs ? (size_t)N * c->amp_size : 0); std::vector<int> ht(terminate ? N : 0), hv(valid ? N : 0), he(episode_end ? N : 0);
     c->step_ids = c->d_ids; c->step_n_ids = n;
-    const int rc = launch_status(c->step(adev, timestep, n_updates, c->d_states, c->d_rewards, c->d_term, c->d_valid, c->d_end, flags, amp_obs ? c->d_amp : nullptr));
+    const int rc = step_io(c, actions, n, timestep, n_updates, StepOut{states ? hs.data() : nullptr, rewards ? hr.data() : nullptr, terminate ? ht.data() : nullptr, valid ? hv.data() : nullptr,
+                                                                        episode_end ? he.data() : nullptr, amp_obs ? ha.data() : nullptr}, flags);
     c->step_ids = nullptr; c->step_n_ids = 0;
     if (rc) return -1;
-    // the kernels write every output at the env's own row: copy the arrays back and hand out the rows asked for
-    std::vector<float> hs(states ? (size_t)N * S : 0), hr(rewards ? N : 0), ha(amp_obs ? (size_t)N * c->amp_size : 0); std::vector<int> ht(terminate ? N : 0), hv(valid ? N : 0), he(episode_end ? N : 0);
-    if ((states && copy_out(c, hs.data(), c->d_states, sizeof(float) * hs.size())) || (rewards && copy_out(c, hr.data(), c->d_rewards, sizeof(float) * N)) ||
-        (terminate && copy_out(c, ht.data(), c->d_term, sizeof(int) * N)) || (valid && copy_out(c, hv.data(), c->d_valid, sizeof(int) * N)) ||
-        (episode_end && copy_out(c, he.data(), c->d_end, sizeof(int) * N)) || (amp_obs && copy_out(c, ha.data(), c->d_amp, sizeof(float) * ha.size()))) return -1;
     std::vector<double> hc;
     if (clocks) { hc.resize((size_t)N * 5); if (c->get_state(nullptr, nullptr, nullptr, nullptr, hc.data(), nullptr)) return -1; }
     for (int i = 0; i < n; ++i) {
@@ -1078,93 +1069,60 @@ int dm_step_envs(dm_ctx* ctx, const int32_t* env_ids, int n, const float* action
 int dm_amp_obs_size(const dm_ctx* ctx) { return ctx ? ctx->c->amp_size : 0; }
 
 int dm_query_amp(dm_ctx* ctx, float* amp_obs, int flags) {
-    if (!ctx || !amp_obs) return fail("null argument");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (!c->amp_size) return fail("AMP observations need a `--scene imitate_amp` context (dm_scene_tables.scene_amp)");
-    if (flags & DM_DEVICE_PTRS) return launch_status(c->query(nullptr, nullptr, nullptr, nullptr, nullptr, amp_obs));
-    if (launch_status(c->query(nullptr, nullptr, nullptr, nullptr, nullptr, c->d_amp))) return -1;
-    return copy_out(c, amp_obs, c->d_amp, sizeof(float) * (size_t)c->N * c->amp_size);
+    return guarded(ctx, amp_obs, [&](CtxBase* c) { return need_amp(c) ? query_io(c, StepOut{nullptr, nullptr, nullptr, nullptr, nullptr, amp_obs}, StepOut{nullptr, nullptr, nullptr, nullptr, nullptr, c->d_amp}, flags) : -1; });
 }
 
-int dm_step_batch_amp(dm_ctx* ctx, const float* actions, double timestep, int n_updates, float* states, float* rewards,
-                      int32_t* terminate, int32_t* valid, int32_t* episode_end, float* amp_obs, int flags) {
-    if (!ctx) return fail("null ctx");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (amp_obs && !c->amp_size) return fail("AMP observations need a `--scene imitate_amp` context (dm_scene_tables.scene_amp)");
-    if (flags & DM_DEVICE_PTRS) return launch_status(c->step(actions, timestep, n_updates, states, rewards, terminate, valid, episode_end, flags, amp_obs));
-    const float* adev = nullptr;
-    if (actions) { if (rt_h2d(c->d_actions, actions, sizeof(float) * c->N * c->hm.A, c->stream)) return fail("copy failed"); adev = c->d_actions; }
-    if (launch_status(c->step(adev, timestep, n_updates, c->d_states, c->d_rewards, c->d_term, c->d_valid, c->d_end, flags, amp_obs ? c->d_amp : nullptr))) return -1;
-    if (copy_out(c, states, c->d_states, sizeof(float) * c->N * c->hm.S) || copy_out(c, rewards, c->d_rewards, sizeof(float) * c->N) ||
-        copy_out(c, terminate, c->d_term, sizeof(int) * c->N) || copy_out(c, valid, c->d_valid, sizeof(int) * c->N) || copy_out(c, episode_end, c->d_end, sizeof(int) * c->N) ||
-        copy_out(c, amp_obs, c->d_amp, sizeof(float) * (size_t)c->N * c->amp_size)) return -1;
-    return 0;
+// n expert observations through device temporaries: sample times, optional clip ids and ground heights up, n x amp_size floats back
+static int amp_expert_io(CtxBase* c, int n, const int* clips, const double* times, const double* ground_h, float* out) {
+    const size_t out_bytes = sizeof(float) * (size_t)n * c->amp_size;
+    int rc = 0;
+    DevTmp td(rc, c->stream, sizeof(double) * n, times), cd(rc, c->stream, sizeof(int) * n, clips), od(rc, c->stream, out_bytes, nullptr, true),
+           gd(rc, c->stream, sizeof(double) * n, ground_h);
+    if (!rc) rc = launch_status(c->amp_expert_clips(n, (const int*)cd.p, (const double*)td.p, (const double*)gd.p, (float*)od.p));
+    if (!rc && rt_d2h(out, od.p, out_bytes, c->stream)) rc = fail("copy failed");
+    rt_sync(c->stream);
+    return rc;
 }
 
 int dm_amp_expert(dm_ctx* ctx, int n, const double* times, const double* ground_h, float* out, int flags) {
-    if (!ctx || !out) return fail("null argument");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (!c->amp_size) return fail("AMP observations need a `--scene imitate_amp` context (dm_scene_tables.scene_amp)");
-    if (n <= 0) return 0;
-    if (flags & DM_DEVICE_PTRS) {
-        if (!times) return fail("dm_amp_expert with device pointers needs explicit sample times");
-        return launch_status(c->amp_expert(n, times, ground_h, out));
-    }
-    std::vector<double> t(n);
-    if (times) memcpy(t.data(), times, sizeof(double) * n);
-    else { for (int i = 0; i < n; ++i) t[i] = c->hm.duration * dm_rand01(c->seed, (uint64_t)c->env_off + 0x414D50ull, c->expert_calls, (uint64_t)i); c->expert_calls++; }
-    void *td = nullptr, *gd = nullptr, *od = nullptr; int rc = 0;
-    if (rt_malloc(&td, sizeof(double) * n) || rt_malloc(&od, sizeof(float) * (size_t)n * c->amp_size) || (ground_h && rt_malloc(&gd, sizeof(double) * n))) rc = fail("device allocation failed");
-    if (!rc && (rt_h2d(td, t.data(), sizeof(double) * n, c->stream) || (ground_h && rt_h2d(gd, ground_h, sizeof(double) * n, c->stream)))) rc = fail("copy failed");
-    if (!rc) rc = launch_status(c->amp_expert(n, (const double*)td, (const double*)gd, (float*)od));
-    if (!rc && rt_d2h(out, od, sizeof(float) * (size_t)n * c->amp_size, c->stream)) rc = fail("copy failed");
-    rt_sync(c->stream);
-    if (td) rt_free(td); if (gd) rt_free(gd); if (od) rt_free(od);
-    return rc;
+    return guarded(ctx, out, [&](CtxBase* c) {
+        if (!need_amp(c)) return -1;
+        if (n <= 0) return 0;
+        if (flags & DM_DEVICE_PTRS) return times ? launch_status(c->amp_expert_clips(n, nullptr, times, ground_h, out)) : fail("dm_amp_expert with device pointers needs explicit sample times");
+        std::vector<double> t(n);
+        if (times) memcpy(t.data(), times, sizeof(double) * n);
+        else { for (int i = 0; i < n; ++i) t[i] = c->hm.duration * dm_rand01(c->seed, (uint64_t)c->env_off + 0x414D50ull, c->expert_calls, (uint64_t)i); c->expert_calls++; }      // (counted only when the times are drawn here)
+        return amp_expert_io(c, n, nullptr, t.data(), ground_h, out);
+    });
 }
 
 int dm_amp_expert_clips(dm_ctx* ctx, int n, const int32_t* clips, const double* times, const double* ground_h, float* out) {
-    if (!ctx || !out) return fail("null argument");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (!c->amp_size) return fail("AMP observations need a `--scene imitate_amp` context (dm_scene_tables.scene_amp)");
-    if (n <= 0) return 0;
-    const HostModel& h = c->hm;
-    std::vector<int> cl(n); std::vector<double> t(n);
-    for (int i = 0; i < n; ++i) {
-        if (clips) { if (clips[i] < 0 || clips[i] >= h.num_clips) return fail("clip id out of range"); cl[i] = clips[i]; }
-        else { double u = dm_rand01(c->seed, (uint64_t)c->env_off + 0x434C50ull, c->expert_calls, (uint64_t)i); int k = 0; while (k < h.num_clips - 1 && !(u < h.clip_cdf[k])) ++k; cl[i] = k; }
-        t[i] = times ? times[i] : h.clip_dur[cl[i]] * dm_rand01(c->seed, (uint64_t)c->env_off + 0x414D50ull, c->expert_calls, (uint64_t)i);
-    }
-    c->expert_calls++;
-    void *td = nullptr, *gd = nullptr, *od = nullptr, *cd = nullptr; int rc = 0;
-    if (rt_malloc(&td, sizeof(double) * n) || rt_malloc(&cd, sizeof(int) * n) || rt_malloc(&od, sizeof(float) * (size_t)n * c->amp_size) || (ground_h && rt_malloc(&gd, sizeof(double) * n))) rc = fail("device allocation failed");
-    if (!rc && (rt_h2d(td, t.data(), sizeof(double) * n, c->stream) || rt_h2d(cd, cl.data(), sizeof(int) * n, c->stream) || (ground_h && rt_h2d(gd, ground_h, sizeof(double) * n, c->stream)))) rc = fail("copy failed");
-    if (!rc) rc = launch_status(c->amp_expert_clips(n, (const int*)cd, (const double*)td, (const double*)gd, (float*)od));
-    if (!rc && rt_d2h(out, od, sizeof(float) * (size_t)n * c->amp_size, c->stream)) rc = fail("copy failed");
-    rt_sync(c->stream);
-    if (td) rt_free(td); if (gd) rt_free(gd); if (od) rt_free(od); if (cd) rt_free(cd);
-    return rc;
+    return guarded(ctx, out, [&](CtxBase* c) {
+        if (!need_amp(c)) return -1;
+        if (n <= 0) return 0;
+        const HostModel& h = c->hm;
+        std::vector<int> cl(n); std::vector<double> t(n);
+        for (int i = 0; i < n; ++i) {
+            if (clips) { if (clips[i] < 0 || clips[i] >= h.num_clips) return fail("clip id out of range"); cl[i] = clips[i]; }
+            else { double u = dm_rand01(c->seed, (uint64_t)c->env_off + 0x434C50ull, c->expert_calls, (uint64_t)i); int k = 0; while (k < h.num_clips - 1 && !(u < h.clip_cdf[k])) ++k; cl[i] = k; }
+            t[i] = times ? times[i] : h.clip_dur[cl[i]] * dm_rand01(c->seed, (uint64_t)c->env_off + 0x414D50ull, c->expert_calls, (uint64_t)i);
+        }
+        c->expert_calls++;      // (always)
+        return amp_expert_io(c, n, cl.data(), t.data(), ground_h, out);
+    });
 }
 
+static int copy_goals(CtxBase* c, float* goals) { return copy_out(c, goals, c->d_goals, sizeof(float) * (size_t)c->N * c->goal_size); }
 int dm_query_goal(dm_ctx* ctx, float* goals, int flags) {
-    if (!ctx || !goals) return fail("null argument");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (!c->goal_size) return fail("RecordGoal needs a goal scene (dm_scene_tables.scene_goal)");
-    if (launch_status(c->query(nullptr, nullptr, nullptr, nullptr, nullptr))) return -1;
     (void)flags;
-    return copy_out(c, goals, c->d_goals, sizeof(float) * (size_t)c->N * c->goal_size);
+    return guarded(ctx, goals, [&](CtxBase* c) { return (!need_goal(c) || launch_status(c->query(StepOut{}))) ? -1 : copy_goals(c, goals); });
 }
-int dm_last_goals(dm_ctx* ctx, float* goals) {
-    if (!ctx || !goals) return fail("null argument");
-    CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (!c->goal_size) return fail("RecordGoal needs a goal scene (dm_scene_tables.scene_goal)");
-    return copy_out(c, goals, c->d_goals, sizeof(float) * (size_t)c->N * c->goal_size);
-}
+int dm_last_goals(dm_ctx* ctx, float* goals) { return guarded(ctx, goals, [&](CtxBase* c) { return need_goal(c) ? copy_goals(c, goals) : -1; }); }
 // the same into a DEVICE buffer, asynchronously on the ctx stream (no host sync: a device-resident learner reads it after the step)
 int dm_last_goals_device(dm_ctx* ctx, float* goals_dev) {
     if (!ctx || !goals_dev) return fail("null argument");
     CtxBase* c = ctx->c; DevGuard guard(c->device_id);
-    if (!c->goal_size) return fail("RecordGoal needs a goal scene (dm_scene_tables.scene_goal)");
+    if (!need_goal(c)) return -1;
     const size_t bytes = sizeof(float) * (size_t)c->N * c->goal_size;
 #ifdef DM_EMU
     memcpy(goals_dev, c->d_goals, bytes);
@@ -1173,30 +1131,30 @@ int dm_last_goals_device(dm_ctx* ctx, float* goals_dev) {
 #endif
     return 0;
 }
-int dm_get_goal_state(dm_ctx* ctx, double* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->get_goal(out); }
-int dm_set_goal_state(dm_ctx* ctx, const double* in) { if (!ctx || !in) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->set_goal(in); }
+int dm_get_goal_state(dm_ctx* ctx, double* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->goal_state(out, nullptr); }); }
+int dm_set_goal_state(dm_ctx* ctx, const double* in) { return guarded(ctx, in, [&](CtxBase* c) { return c->goal_state(nullptr, in); }); }
 int dm_goal_size(const dm_ctx* ctx) { return ctx ? ctx->c->goal_size : 0; }
-int dm_get_goal_aux(dm_ctx* ctx, double* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->goal_aux(out, nullptr); }
-int dm_set_goal_aux(dm_ctx* ctx, const double* in) { if (!ctx || !in) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->goal_aux(nullptr, in); }
-int dm_get_perturb_state(dm_ctx* ctx, double* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->pert_state(out, nullptr); }
-int dm_set_perturb_state(dm_ctx* ctx, const double* in) { if (!ctx || !in) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->pert_state(nullptr, in); }
-int dm_get_obj_state(dm_ctx* ctx, double* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->obj_state(out, nullptr); }
-int dm_set_obj_state(dm_ctx* ctx, const double* in) { if (!ctx || !in) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->obj_state(nullptr, in); }
-int dm_get_manifolds(dm_ctx* ctx, double* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->manifolds(out, nullptr); }
-int dm_set_manifolds(dm_ctx* ctx, const double* in) { if (!ctx || !in) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->manifolds(nullptr, in); }
+int dm_get_goal_aux(dm_ctx* ctx, double* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->goal_aux(out, nullptr); }); }
+int dm_set_goal_aux(dm_ctx* ctx, const double* in) { return guarded(ctx, in, [&](CtxBase* c) { return c->goal_aux(nullptr, in); }); }
+int dm_get_perturb_state(dm_ctx* ctx, double* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->pert_state(out, nullptr); }); }
+int dm_set_perturb_state(dm_ctx* ctx, const double* in) { return guarded(ctx, in, [&](CtxBase* c) { return c->pert_state(nullptr, in); }); }
+int dm_get_obj_state(dm_ctx* ctx, double* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->obj_state(out, nullptr); }); }
+int dm_set_obj_state(dm_ctx* ctx, const double* in) { return guarded(ctx, in, [&](CtxBase* c) { return c->obj_state(nullptr, in); }); }
+int dm_get_manifolds(dm_ctx* ctx, double* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->manifolds(out, nullptr); }); }
+int dm_set_manifolds(dm_ctx* ctx, const double* in) { return guarded(ctx, in, [&](CtxBase* c) { return c->manifolds(nullptr, in); }); }
 int dm_set_mode(dm_ctx* ctx, int test_mode) { if (!ctx) return fail("null ctx"); ctx->c->set_mode(test_mode); return 0; }
-int dm_set_draw_tape(dm_ctx* ctx, const double* tape) { if (!ctx) return fail("null ctx"); DevGuard guard(ctx->c->device_id); return ctx->c->draw_tape(tape, tape == nullptr, nullptr); }
+int dm_set_draw_tape(dm_ctx* ctx, const double* tape) { return guarded(ctx, [&](CtxBase* c) { return c->draw_tape(tape, tape == nullptr, nullptr); }); }
 int dm_set_draw_tape_envs(dm_ctx* ctx, const int32_t* env_ids, int n, const double* rows) {
     if (!ctx) return fail("null ctx");
     if (n > 0 && (!env_ids || !rows)) return fail("null argument");
-    DevGuard guard(ctx->c->device_id); return ctx->c->draw_tape_envs(env_ids, n > 0 ? n : 0, n > 0 ? rows : nullptr, nullptr);
+    return guarded(ctx, [&](CtxBase* c) { return c->draw_tape_envs(env_ids, n > 0 ? n : 0, n > 0 ? rows : nullptr, nullptr); });
 }
 int dm_get_draw_tape_state_envs(dm_ctx* ctx, const int32_t* env_ids, int n, double* out) {
     if (!ctx || !env_ids || !out) return fail("null argument");
     if (n <= 0) return 0;
-    DevGuard guard(ctx->c->device_id); return ctx->c->draw_tape_envs(env_ids, n, nullptr, out);
+    return guarded(ctx, [&](CtxBase* c) { return c->draw_tape_envs(env_ids, n, nullptr, out); });
 }
-int dm_get_draw_tape_state(dm_ctx* ctx, double* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->draw_tape(nullptr, 0, out); }
+int dm_get_draw_tape_state(dm_ctx* ctx, double* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->draw_tape(nullptr, 0, out); }); }
 int dm_clip_table(const dm_ctx* ctx, double* durations, double* cdf) {
     if (!ctx) return fail("null ctx");
     const HostModel& h = ctx->c->hm;
@@ -1210,11 +1168,10 @@ int dm_clip_table(const dm_ctx* ctx, double* durations, double* cdf) {
 int dm_set_env_keys(dm_ctx* ctx, const int32_t* env_ids, int n, const uint64_t* seeds) {
     if (!ctx || !env_ids || !seeds) return fail("null argument");
     if (n <= 0) return 0;
-    DevGuard guard(ctx->c->device_id);
-    return ctx->c->set_env_keys(env_ids, n, seeds);
+    return guarded(ctx, [&](CtxBase* c) { return c->set_env_keys(env_ids, n, seeds); });
 }
-int dm_set_clips(dm_ctx* ctx, const int32_t* in) { if (!ctx || !in) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->set_clips(in); }
-int dm_get_clips(dm_ctx* ctx, int32_t* out) { if (!ctx || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->get_clips(out); }
+int dm_set_clips(dm_ctx* ctx, const int32_t* in) { return guarded(ctx, in, [&](CtxBase* c) { return c->clips(nullptr, in); }); }
+int dm_get_clips(dm_ctx* ctx, int32_t* out) { return guarded(ctx, out, [&](CtxBase* c) { return c->clips(out, nullptr); }); }
 
 int dm_build_offsets_scales(const dm_ctx* ctx, double* s_off, double* s_scale, double* a_off, double* a_scale, double* a_min, double* a_max, int32_t* s_norm_groups) {
     if (!ctx) return fail("null ctx");
@@ -1230,30 +1187,28 @@ int dm_build_offsets_scales(const dm_ctx* ctx, double* s_off, double* s_scale, d
 }
 
 int dm_get_state(dm_ctx* ctx, double* pose, double* vel, double* tar, double* kin, double* clocks, int32_t* flags) {
-    if (!ctx) return fail("null ctx");
-    DevGuard guard(ctx->c->device_id);
-    return ctx->c->get_state(pose, vel, tar, kin, clocks, flags);
+    return guarded(ctx, [&](CtxBase* c) { return c->get_state(pose, vel, tar, kin, clocks, flags); });
 }
 int dm_set_state(dm_ctx* ctx, const double* pose, const double* vel, const double* tar, const double* kin, const double* clocks, const int32_t* flags) {
-    if (!ctx) return fail("null ctx");
-    DevGuard guard(ctx->c->device_id);
-    return ctx->c->set_state(pose, vel, tar, kin, clocks, flags);
+    return guarded(ctx, [&](CtxBase* c) { return c->set_state(pose, vel, tar, kin, clocks, flags); });
 }
-int dm_probe(dm_ctx* ctx, int what, double dt) { if (!ctx) return fail("null ctx"); DevGuard guard(ctx->c->device_id); int rc = launch_status(ctx->c->probe(what, dt)); if (rt_sync(ctx->c->stream) != 0 && !rc) rc = fail("stream synchronize failed"); return rc; }
-int dm_set_tau(dm_ctx* ctx, const double* tau) { if (!ctx || !tau) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->set_tau(tau); }
-int dm_get_debug(dm_ctx* ctx, const char* name, double* out) { if (!ctx || !name || !out) return fail("null argument"); DevGuard guard(ctx->c->device_id); return ctx->c->get_debug(name, out); }
+int dm_probe(dm_ctx* ctx, int what, double dt) {
+    return guarded(ctx, [&](CtxBase* c) { int rc = launch_status(c->probe(what, dt)); if (rt_sync(c->stream) != 0 && !rc) rc = fail("stream synchronize failed"); return rc; });
+}
+int dm_set_tau(dm_ctx* ctx, const double* tau) { return guarded(ctx, tau, [&](CtxBase* c) { return c->set_tau(tau); }); }
+int dm_get_debug(dm_ctx* ctx, const char* name, double* out) { if (!name) return fail("null argument"); return guarded(ctx, out, [&](CtxBase* c) { return c->get_debug(name, out); }); }
 
 int dm_bench_rollout(dm_ctx* ctx, int warmup, int steps, double timestep, int n_updates, int flags, float* states_dev, float* rewards_dev, double* elapsed_ms) {
     if (!ctx) return fail("null ctx");
     CtxBase* c = ctx->c; DevGuard guard(c->device_id);
     float* sdev = states_dev ? states_dev : c->d_states; float* rdev = rewards_dev ? rewards_dev : c->d_rewards;
-    for (int k = 0; k < warmup; ++k) if (c->step(nullptr, timestep, n_updates, sdev, rdev, c->d_term, c->d_valid, c->d_end, flags)) return -1;
+    for (int k = 0; k < warmup; ++k) if (c->step(nullptr, timestep, n_updates, StepOut{sdev, rdev, c->d_term, c->d_valid, c->d_end, nullptr}, flags)) return -1;
 #ifndef DM_EMU
     hipEvent_t e0, e1;
     HIPCHK(hipEventCreate(&e0)); HIPCHK(hipEventCreate(&e1));
     HIPCHK(hipEventRecord(e0, c->stream));
 #endif
-    for (int k = 0; k < steps; ++k) if (c->step(nullptr, timestep, n_updates, sdev, rdev, c->d_term, c->d_valid, c->d_end, flags)) return -1;
+    for (int k = 0; k < steps; ++k) if (c->step(nullptr, timestep, n_updates, StepOut{sdev, rdev, c->d_term, c->d_valid, c->d_end, nullptr}, flags)) return -1;
 #ifndef DM_EMU
     HIPCHK(hipEventRecord(e1, c->stream));
     HIPCHK(hipEventSynchronize(e1));
