@@ -19,7 +19,7 @@
 //   spd_*()      sim/ImpPDController.cpp:136-195, sim/SimBodyJoint.cpp:299-307,636-695
 //   substep_*()  DM-physics v1 standing in for btMultiBodyDynamicsWorld::stepSimulation
 //   emit()       scenes/SceneImitate.cpp:7-127,163-205; sim/CtController.cpp:281-478; sim/SimCharacter.cpp:542-586
-//   reset_env()  scenes/SceneSimChar.cpp:487-583,628-644; scenes/SceneImitate.cpp:320-368,386-418
+//   reset_env()  scenes/SceneSimChar.cpp:487-583,628-644; scenes/SceneImitate.cpp:320-368,386-418 (reset_episode: the order of a whole episode start around it)
 #pragma once
 #include <type_traits>
 #include "dm_math.h"
@@ -2919,6 +2919,30 @@ template <bool EXP, typename Real> DM_DEV double draw_time_limit(const ModelDev<
     if (EXP) { if (m.timer_exp > 0) { const double t = m.time_lim_min - m.timer_exp * log1p(-u); return t < m.time_lim_max ? t : m.time_lim_max; } }
     return m.time_lim_min + (m.time_lim_max - m.time_lim_min) * u;
 }
+// The start of a new episode, once for the auto-reset of k_env_step_duo (mirrors DeepMimic.py:70-79) and for k_env_reset.  The time limit is drawn first (stream 1),
+// then a get-up scene may go on as a recovery episode (timers only); otherwise the scene reset: reset_goal_env for an env with a goal row, else the clip time over the
+// clip (stream 0), reset_env, empty ground manifolds, a fresh pose history, ResetRandPertrub by lane 0 of the character (`lane0`: the caller's own spelling of that
+// lane -- EnvSim::l is an opaque copy, and testing it changes the code of every AMP two-per-wave kernel).  HIST / V2: what the calling instantiation carries
+// (k_env_reset: both, its guards are then the pointer tests alone).  kin_time / max_time: given by the caller of dm_reset.  A draw tape bound and no clip time
+// given (one-per-wave only, tape()): NaN = the timer draws are looked up inside the reset, in the reference's order.
+// k_env_step keeps these steps written out: called from there, this routine changes the code of its plain production instantiations (docs/HISTORY.md).
+template <bool HIST, bool V2, typename Sim, typename Real>
+DM_DEV void reset_episode(Sim& sim, const EnvState<Real>& st, int e, double* pert, bool lane0, const double* kin_time = nullptr, const double* max_time = nullptr) {
+    const ModelDev<Real>& m = sim.m;
+    const uint64_t ep = (uint64_t)sim.s.flg[FLG_EPISODE];
+    double mt = max_time ? *max_time
+              : (HIST && st.goal && !kin_time && sim.tape(e)) ? (double)NAN
+              : draw_time_limit<HIST>(m, e, ep, (HIST && st.goal) ? st.goal + (size_t)e * GS_WIDTH : nullptr);
+    if (HIST && st.goal) {           // clip by weight, random yaw, goal reset -- unless the episode goes on as a recovery episode
+        if (kin_time || !sim.try_recovery_reset(st, e, mt)) reset_goal_env(sim, m, sim.s, st, e, ep, kin_time, mt, true, pert);
+        return;
+    }
+    const double kt = kin_time ? *kin_time : m.duration * dm_rand01(m.seed, (uint64_t)(e + m.env_off), ep, 0);
+    sim.reset_env(kt, mt);
+    if (V2) sim.manif_clear(st, e);
+    if (HIST && st.hist) sim.init_hist(st, e);
+    if (HIST && pert && lane0) sim.pert_reset(pert, e);
+}
 // AMP: the `--scene imitate_amp` instantiation (pose history latch inside the update loop, AMP observation at the end); the
 // plain production kernel carries none of it.  The tap build (tests, profiling) serves both scene kinds.
 // PHYS2: DM-physics v2 -- its own instantiation, so that the AMP kernels of the shipped scenes do not carry it
@@ -2966,7 +2990,7 @@ __global__ void __launch_bounds__(64) DM_WAVES_PER_EU((StepWaves<Real, C>::value
             uint64_t ep = (uint64_t)lds.flg[FLG_EPISODE];
             double mt = draw_time_limit<HIST>(m, e, ep, (HIST && st.goal) ? st.goal + (size_t)e * GS_WIDTH : nullptr);
             bool rec = false;
-            if (HIST && st.goal) {           // clip by weight, random yaw, goal reset -- unless the episode goes on as a recovery episode
+            if (HIST && st.goal) {           // (the steps of reset_episode, written out: see there)
                 rec = sim.try_recovery_reset(st, e, mt);
                 if (!rec) reset_goal_env<Real, C, TAPS>(sim, m, lds, st, e, ep, nullptr, mt, true, pert);      // (ResetScene -> ResetRandPertrub; a recovery episode only resets the timers)
             }
@@ -2994,24 +3018,8 @@ __global__ void __launch_bounds__(64) k_env_reset(ModelDev<Real> m, EnvState<Rea
     const int e = env_ids ? env_ids[b] : b;
     EnvSim<Real, C> sim(m, lds, l);
     sim.load(st, e);
-    uint64_t ep = (uint64_t)lds.flg[FLG_EPISODE];
-    // (draw tape bound and no clip time given: NaN = the timer draws are looked up inside the reset, in the reference's order)
-    double mt = max_times ? max_times[b]
-              : (st.goal && !kin_times && sim.tape(e)) ? (double)NAN
-              : draw_time_limit<true>(m, e, ep, st.goal ? st.goal + (size_t)e * GS_WIDTH : nullptr);
-    double* pert = st.pert ? st.pert + (size_t)e * PT_WIDTH : nullptr;
-    bool rec = false;
-    if (st.goal) {
-        sim.goal_sync_flags(st, e);
-        rec = !kin_times && sim.try_recovery_reset(st, e, mt);
-        if (!rec) reset_goal_env<Real, C, true>(sim, m, lds, st, e, ep, kin_times ? &kin_times[b] : nullptr, mt, true, pert);
-    } else {
-        double kt = kin_times ? kin_times[b] : m.duration * dm_rand01(m.seed, (uint64_t)(e + m.env_off), ep, 0);
-        sim.reset_env(kt, mt);
-        sim.manif_clear(st, e);
-        if (st.hist) sim.init_hist(st, e);
-        if (pert && l == 0) sim.pert_reset(pert, e);
-    }
+    if (st.goal) sim.goal_sync_flags(st, e);
+    reset_episode<true, true>(sim, st, e, st.pert ? st.pert + (size_t)e * PT_WIDTH : nullptr, l == 0, kin_times ? &kin_times[b] : nullptr, max_times ? &max_times[b] : nullptr);
     sim.store(st, e);
 }
 
