@@ -465,6 +465,13 @@ class BatchEnv:
         self._chk(self.lib.dm_step_batch(self.h, vp(actions_ptr), C.c_double(timestep), int(n_updates), vp(states_ptr),
                                          vp(rewards_ptr), vp(term_ptr), vp(valid_ptr), vp(end_ptr), flags))
 
+    def set_terminal_outputs(self, term_states_ptr: int = 0, term_goals_ptr: int = 0):
+        """include/dm_hip.h dm_set_terminal_outputs: bind device buffers (raw pointers: N x S float32, and N x G float32 for a goal scene) that every
+        auto-reset launch fills, for the envs it resets, with RecordState / RecordGoal of the moment the episode ended; (0, 0) unbinds.  Rows of envs that
+        were not reset are left alone.  The caller keeps the buffers alive while they are bound."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self._chk(self.lib.dm_set_terminal_outputs(self.h, vp(term_states_ptr), vp(term_goals_ptr)))
+
     def set_stream(self, stream_handle: int):
         # torch's default stream has the null handle, which dm_set_stream reads as "back to the ctx's own stream": select the legacy
         # default stream explicitly, so that `env.set_stream(torch.cuda.current_stream().cuda_stream)` orders the launches against

@@ -2326,6 +2326,17 @@ struct EnvSim {
         sync();
         amp_build(pp, pv, s.pose, s.vel, (Real)0, true, io.amp_obs + (size_t)e * 2 * (m.amp_pose_size + m.amp_vel_size));
     }
+    // dm_set_terminal_outputs: the RecordState / RecordGoal rows the first emit pass has just written for env e, copied aside before the auto-reset overwrites them with
+    // the first observation of the next episode (`ended` is known only after that pass, emit_goal's own termination included).  A lane reads words its neighbours
+    // stored to global memory: the caller stands behind the sync() that ends emit / emit_goal / emit_amp -- __syncthreads, i.e. the stores of this workgroup's
+    // lanes have completed and are visible to its loads -- and the many sync() of the reset separate these loads from the second pass's stores.
+    DM_DEV void emit_terminal(const StepIO<Real>& io, int e, bool goal) {
+        if (io.states) {
+            const float* src = io.states + (size_t)e * m.S; float* dst = io.term_states + (size_t)e * m.S;
+            for (int i = l; i < m.S; i += LW) dst[i] = src[i];
+        }
+        if (goal && io.term_goals && io.goals && l < m.goal_dim) io.term_goals[(size_t)e * m.goal_dim + l] = io.goals[(size_t)e * m.goal_dim + l];
+    }
     // RecordAMPObsExpert (:115-138): raw clip frames (no origin transform, no cycle offset) at `time` and one control
     // period earlier; ground height := the caller's kin origin y.  Uses this wave's LDS record as scratch only.
     DM_DEV void amp_expert(double time, Real ground_h, float* out) {
@@ -2987,6 +2998,7 @@ __global__ void __launch_bounds__(64) DM_WAVES_PER_EU((StepWaves<Real, C>::value
             const bool ended = lds.sc[6] != (Real)0;
             if (HIST && pass == 0 && io.amp_obs && st.hist) sim.emit_amp(io, st, e);       // end-of-path observation of a finished episode included
             if (pass == 1 || !(io.auto_reset && ended)) break;
+            if (io.term_states) sim.emit_terminal(io, e, goal);                            // the row of the moment the episode ended (dm_set_terminal_outputs)
             uint64_t ep = (uint64_t)lds.flg[FLG_EPISODE];
             double mt = draw_time_limit<HIST>(m, e, ep, (HIST && st.goal) ? st.goal + (size_t)e * GS_WIDTH : nullptr);
             bool rec = false;

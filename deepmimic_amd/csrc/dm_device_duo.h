@@ -1291,6 +1291,7 @@ __global__ void __launch_bounds__(64) DM_WAVES_PER_EU((DuoWaves<Real>::value)) k
         const bool ended = lds[half].sc[6] != (Real)0;
         if (HIST && io.amp_obs && st.hist) sim.b.emit_amp(io, st, e);
         if (io.auto_reset && ended) {                    // per character; no cross-half traffic inside
+            if (io.term_states) sim.b.emit_terminal(io, e, goal);      // the row of the moment the episode ended (dm_set_terminal_outputs), before it is overwritten
             reset_episode<HIST, V2>(sim.b, st, e, pert, (wl & 31) == 0);
             sim.b.emit(io, tap, e, false);
             if (goal) sim.b.emit_goal(io, st, e, false);

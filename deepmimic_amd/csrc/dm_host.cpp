@@ -362,6 +362,7 @@ struct CtxBase {
     StepOut dev_out(bool amp) const { return StepOut{d_states, d_rewards, d_term, d_valid, d_end, amp ? d_amp : nullptr}; }
     int amp_size = 0; float* d_amp = nullptr; uint64_t expert_calls = 0;
     int goal_size = 0; float* d_goals = nullptr;            // RecordGoal of the last emit (goal scenes)
+    float *term_states = nullptr, *term_goals = nullptr;    // dm_set_terminal_outputs: the caller's device buffers (N x S, N x goal_size) for the rows of envs a DM_AUTO_RESET launch resets; null = unbound
     virtual int goal_state(double* out, const double* in) = 0; virtual int clips(int* out, const int* in) = 0; virtual int need_new_action(int* out) = 0;
     virtual int goal_aux(double* out, const double* in) = 0; virtual void set_mode(int test) = 0; virtual int pert_state(double* out, const double* in) = 0;
     virtual int obj_state(double* out, const double* in) = 0;
@@ -618,6 +619,7 @@ struct CtxT : CtxBase {
         io.env_ids = step_ids; const int GN = step_ids ? step_n_ids : N;      // workgroups of the one-per-wave launches
         if (md.draw_tape && (flags & DM_AUTO_RESET)) return fail("a draw tape is bound (dm_set_draw_tape): resets go through dm_reset, where the tape serves the reference's draw order");
         io.n_updates = n_updates; io.dt = dt; io.auto_reset = (flags & DM_AUTO_RESET) ? 1 : 0; io.emit = (flags & DM_NO_EMIT) ? 0 : 1; io.open_loop = (flags & DM_OPEN_LOOP) ? 1 : 0; io.end_early = (flags & DM_END_EPISODE_EARLY) ? 1 : 0;
+        if (io.auto_reset && io.emit && !step_ids) { io.term_states = term_states; io.term_goals = term_goals; }      // (dm_set_terminal_outputs; the subset route of dm_step_envs leaves them out)
         // Variant.  The tap instantiation only when a parity test armed the debug taps (dm_probe); DM-physics v2 has its own (AMP code + manifolds); the AMP
         // instantiation also carries the perturbation code; ClsBipedObj has no plain family
         int variant = dbg.H ? SV_TAPS : st.manif ? SV_V2 : (st.hist || st.pert || md.enable_root_rot_fail || md.timer_exp > 0) ? SV_AMP : SV_PLAIN;
@@ -1066,6 +1068,14 @@ int dm_step_envs(dm_ctx* ctx, const int32_t* env_ids, int n, const float* action
     return 0;
 }
 
+int dm_set_terminal_outputs(dm_ctx* ctx, float* term_states_dev, float* term_goals_dev) {
+    if (!ctx) return fail("null ctx");
+    if (term_goals_dev && !term_states_dev) return fail("dm_set_terminal_outputs: terminal goals are bound together with terminal states (NULL, NULL unbinds)");
+    if (term_goals_dev && !need_goal(ctx->c)) return -1;
+    ctx->c->term_states = term_states_dev; ctx->c->term_goals = term_goals_dev;
+    return 0;
+}
+
 int dm_amp_obs_size(const dm_ctx* ctx) { return ctx ? ctx->c->amp_size : 0; }
 
 int dm_query_amp(dm_ctx* ctx, float* amp_obs, int flags) {
@@ -1427,3 +1437,4 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_policy_host.h"
 #include "dm_scene_load.h"
 #include "dm_norm.h"          // (after dm_scene_load.h: <map>; after dm_policy_host.h: dm_policy)
+#include "dm_returns.h"       // TD(lambda) returns over a device-resident rollout

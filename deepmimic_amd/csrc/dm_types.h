@@ -304,6 +304,8 @@ struct StepIO {
     int end_early;          // stop an env's updates at the update after which its episode is over (DM_END_EPISODE_EARLY)
     float* goals;           // N x goal_dim  RecordGoal at the end of the call (goal scenes only)
     const int* env_ids;     // non-null (one-per-wave kernels, dm_step_envs): workgroup b steps env env_ids[b] -- `actions` rows are indexed by b (compact), every output by the env id
+    float* term_states;     // N x S  dm_set_terminal_outputs: RecordState at the moment the episode ended, rows of the envs this launch resets only (auto_reset + emit; needs `states`)
+    float* term_goals;      // N x goal_dim  RecordGoal of that moment (goal scenes)
 };
 
 // Debug taps for component parity tests (device pointers, null when unused)

@@ -1,0 +1,64 @@
+"""TD(lambda) returns over a device-resident rollout (libdm_hip.so `dm_td_lambda_returns`, deepmimic_amd/csrc/dm_returns.h): the critic targets of the
+reference's learner -- RLUtil.compute_return (learning/rl_util.py:3-18) per path under the end-of-path rules of learning/ppo_agent.py:251-284 -- for T
+control steps of N envs whose records never left HBM.  Everything is time-major, row t = step t of the N envs, the way a sampler stacks the outputs
+of `TorchVecEnv.step`:
+
+    rewards [T, N]        reward of step t
+    values [T + 1, N]     critic on the observation the action of step t was taken from; row T: on the observation after the last step
+    term_values [T, N]    critic on info["terminal_obs"] / info["terminal_goal"] of step t; used only where done[t] is set
+    terminate, done, valid [T, N] int32   info["terminate"], the `done` of step t, info["valid"]
+
+Behind a step that is not done stands values[t + 1]; behind a done step val_fail / val_succ (terminate Fail / Succ) or term_values[t] (Null: episode timer,
+clip end).  A window cut at T is bootstrapped from values[T] like a Null end -- the one deviation from the reference, which stores whole paths only.
+`mask` is 0 for the steps of an episode that ended invalid inside the window (the reference's driver discards it).  The arithmetic is fp64 in the
+reference's association with one rounding to fp32.  Advantage (returns - values[:T]), value clipping and advantage normalisation stay the caller's."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+from .core import load_library
+
+_ARGTYPES = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double] * 4 + [C.c_void_p] * 3
+
+
+def td_lambda_returns(T: int, N: int, rewards_ptr: int, values_ptr: int, term_values_ptr: int, terminate_ptr: int, done_ptr: int, valid_ptr: int,
+                      gamma: float, td_lambda: float, val_fail: float, val_succ: float, returns_ptr: int, mask_ptr: int = 0,
+                      stream: int = 0, device_id: int = 0, lib_path: Optional[str] = None):
+    """Raw device pointers (ints; valid_ptr and mask_ptr may be 0), asynchronous on the HIP stream `stream` (0 = the null stream) of `device_id`."""
+    lib = load_library(lib_path)
+    lib.dm_td_lambda_returns.argtypes = _ARGTYPES
+    vp = lambda p: C.c_void_p(int(p)) if p else None
+    rc = lib.dm_td_lambda_returns(int(device_id), int(T), int(N), vp(rewards_ptr), vp(values_ptr), vp(term_values_ptr), vp(terminate_ptr), vp(done_ptr), vp(valid_ptr),
+                                  float(gamma), float(td_lambda), float(val_fail), float(val_succ), vp(returns_ptr), vp(mask_ptr), vp(stream))
+    if rc != 0:
+        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+
+
+def td_lambda_returns_torch(rewards, values, term_values, terminate, done, valid, gamma: float, td_lambda: float, val_fail: float, val_succ: float,
+                            lib_path: Optional[str] = None):
+    """The same on torch tensors of one GPU, on torch's current stream: returns (returns [T, N] float32, mask [T, N] int32).  `done` may be a bool
+    tensor (what `TorchVecEnv.step` hands out) or int32; `valid` may be None (every episode valid)."""
+    import torch
+    if rewards.dim() != 2:
+        raise ValueError("rewards must be [T, N]")
+    T, N = int(rewards.shape[0]), int(rewards.shape[1])
+    dev = rewards.device
+    if dev.type != "cuda":
+        raise ValueError("td_lambda_returns_torch needs GPU tensors (deepmimic_amd has no CPU path)")
+    if done.dtype == torch.bool:
+        done = done.to(torch.int32)
+
+    def check(name, x, shape, dtype):
+        if x.device != dev or x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
+
+    check("rewards", rewards, (T, N), torch.float32); check("values", values, (T + 1, N), torch.float32); check("term_values", term_values, (T, N), torch.float32)
+    check("terminate", terminate, (T, N), torch.int32); check("done", done, (T, N), torch.int32)
+    if valid is not None:
+        check("valid", valid, (T, N), torch.int32)
+    returns = torch.empty((T, N), dtype=torch.float32, device=dev); mask = torch.empty((T, N), dtype=torch.int32, device=dev)
+    td_lambda_returns(T, N, rewards.data_ptr(), values.data_ptr(), term_values.data_ptr(), terminate.data_ptr(), done.data_ptr(),
+                      valid.data_ptr() if valid is not None else 0, gamma, td_lambda, val_fail, val_succ, returns.data_ptr(), mask.data_ptr(),
+                      stream=int(torch.cuda.current_stream(dev).cuda_stream), device_id=dev.index or 0, lib_path=lib_path)
+    return returns, mask

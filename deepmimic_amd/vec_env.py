@@ -17,7 +17,9 @@ from .model import SceneTables
 
 class TorchVecEnv:
     def __init__(self, tables: SceneTables, num_envs: int, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
-                 updates_per_step: int = 20, amp_obs: bool = False, **env_kwargs):
+                 updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, **env_kwargs):
+        """terminal_obs (default on): keep `terminal_obs` / `terminal_goal` tensors bound to the context (BatchEnv.set_terminal_outputs), handed out as
+        info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -33,6 +35,11 @@ class TorchVecEnv:
         self.terminate = torch.zeros(self.n, **i32); self.valid = torch.zeros(self.n, **i32); self.episode_end = torch.zeros(self.n, **i32)
         self.amp_obs = torch.zeros((self.n, self.env.amp_size), **f32) if (amp_obs and self.env.amp_size) else None
         self.goal = torch.zeros((self.n, self.goal_dim), **f32) if self.goal_dim else None      # RecordGoal of the last step (goal scenes), device resident
+        # observation / goal of the moment an episode ended, written by the launch that resets the env (rows of other envs keep what they held)
+        self.terminal_obs = torch.zeros((self.n, self.obs_dim), **f32) if terminal_obs else None
+        self.terminal_goal = torch.zeros((self.n, self.goal_dim), **f32) if (terminal_obs and self.goal_dim) else None
+        if terminal_obs:
+            self.env.set_terminal_outputs(self.terminal_obs.data_ptr(), self.terminal_goal.data_ptr() if self.terminal_goal is not None else 0)
         # the launches go to the caller's CURRENT torch stream (looked up at every call): ordered against the caller's work on both sides
         # without events (torch's default stream has the null handle; BatchEnv.set_stream maps it to the legacy default stream)
         self._stream_handle = None
@@ -61,7 +68,10 @@ class TorchVecEnv:
     def step(self, actions) -> Tuple["object", "object", "object", Dict[str, "object"]]:
         """One control step for every env.  `actions`: (N, A) float32 on this device.  Envs whose episode ended during the step are
         reset inside the launch; their `obs` row is already the first observation of the next episode, `reward` / `terminate` describe
-        the step that ended (eTerminateNull 0 / Fail 1 / Succ 2; episode_end also covers the episode timer).
+        the step that ended (eTerminateNull 0 / Fail 1 / Succ 2; episode_end also covers the episode timer).  The observation (and, in a goal
+        scene, the goal) such an env had when its episode ended -- the path-end state a critic bootstraps a timer end from, learning/ppo_agent.py:251-266 --
+        is info["terminal_obs"] / info["terminal_goal"]: (N, S) / (N, G) tensors whose row i is meaningful where done[i] is set in THIS step (other
+        rows keep what an earlier step left there).  deepmimic_amd.returns.td_lambda_returns turns a stacked rollout of these into critic targets.
         `done` = every env that was reset inside the launch: episode_end (cDeepMimicCore::IsEpisodeEnd) OR an INVALID episode (valid == 0:
         cSceneSimChar::CheckValidEpisode failed, a link velocity beyond 100 -- the reference's driver ends and DISCARDS such an episode,
         DeepMimic.py:62-80 / learning/rl_agent.py end_episode; info["valid"] tells the two apart).  A learner that bootstraps across a row with
@@ -78,6 +88,10 @@ class TorchVecEnv:
         if self.goal_dim:
             self.env.last_goals_device(self.goal.data_ptr())        # device-to-device on the same stream, behind the step kernel: no host sync
             info["goal"] = self.goal
+        if self.terminal_obs is not None:
+            info["terminal_obs"] = self.terminal_obs
+            if self.terminal_goal is not None:
+                info["terminal_goal"] = self.terminal_goal
         return self.obs, self.reward, (self.episode_end != 0) | (self.valid == 0), info
 
     def close(self):
@@ -93,7 +107,7 @@ class TorchVecEnvGroups:
     as in a `TorchVecEnv` of the whole batch (draws are keyed by the global env id; tests/test_vec_env.py)."""
 
     def __init__(self, tables: SceneTables, num_envs: int, groups: int = 2, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
-                 updates_per_step: int = 20, amp_obs: bool = False, **env_kwargs):
+                 updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, **env_kwargs):
         import torch
         from .groups import EnvGroups
         self.torch = torch
@@ -111,6 +125,12 @@ class TorchVecEnvGroups:
         self.terminate = torch.zeros(self.n, **i32); self.valid = torch.zeros(self.n, **i32); self.episode_end = torch.zeros(self.n, **i32)
         self.amp_obs = torch.zeros((self.n, self.g.amp_size), **f32) if (amp_obs and self.g.amp_size) else None
         self.goal = torch.zeros((self.n, self.goal_dim), **f32) if self.goal_dim else None
+        # terminal observation / goal as in TorchVecEnv: whole-batch tensors, each group's context bound to its own rows
+        self.terminal_obs = torch.zeros((self.n, self.obs_dim), **f32) if terminal_obs else None
+        self.terminal_goal = torch.zeros((self.n, self.goal_dim), **f32) if (terminal_obs and self.goal_dim) else None
+        for g, e in enumerate(self.g.envs if terminal_obs else []):
+            r = self.g.rows(g)
+            e.set_terminal_outputs(self.terminal_obs[r].data_ptr(), self.terminal_goal[r].data_ptr() if self.terminal_goal is not None else 0)
         # the contexts' own streams (created back to back: distinct hardware queues), visible to torch as external streams
         self.streams = [torch.cuda.ExternalStream(e.own_stream(), device=self.device) for e in self.g.envs]
 
@@ -133,6 +153,10 @@ class TorchVecEnvGroups:
             info["amp_obs"] = self.amp_obs[r]
         if self.goal is not None:
             info["goal"] = self.goal[r]
+        if self.terminal_obs is not None:       # rows meaningful where `done` is set in this step (TorchVecEnv.step)
+            info["terminal_obs"] = self.terminal_obs[r]
+            if self.terminal_goal is not None:
+                info["terminal_goal"] = self.terminal_goal[r]
         return info
 
     def reset(self):

@@ -164,9 +164,20 @@ int dm_query(dm_ctx* ctx, float* states, float* rewards, int32_t* terminate, int
              int32_t* need_new_action, int flags);
 /* Batched control step = [SetAction] + n_updates x Update + query (+ auto reset), one kernel launch.
  * actions may be NULL (keep the latched targets).  With DM_AUTO_RESET, envs whose episode ended are reset after
- * their terminal reward/flags are written and `states` holds the first observation of the new episode. */
+ * their terminal reward/flags are written and `states` holds the first observation of the new episode (the observation of the moment
+ * the episode ended goes to the buffers of dm_set_terminal_outputs, when bound). */
 int dm_step_batch(dm_ctx* ctx, const float* actions, double timestep, int n_updates, float* states, float* rewards,
                   int32_t* terminate, int32_t* valid, int32_t* episode_end, int flags);
+/* Hand back the observation of the moment an episode ended.  Binds two DEVICE buffers to the ctx: term_states_dev N x S floats, term_goals_dev
+ * N x dm_goal_size() floats (goal scenes; may be NULL); NULL, NULL unbinds.  While they are bound, every launch with DM_AUTO_RESET that emits (dm_step_batch,
+ * dm_step_batch_amp with a non-NULL `states`, and the loop of dm_bench_rollout) writes, for each env it resets -- episode_end != 0 or valid == 0 -- the RecordState row
+ * and the RecordGoal row the env had when its episode ended (with DM_END_EPISODE_EARLY: at the update that ended it), i.e. what `states` / the goals held
+ * before the reset overwrote them with the first observation of the next episode: the path-end state of learning/path.py:12-22 that the critic
+ * bootstraps a timer end from (learning/ppo_agent.py:251-266).  Rows of envs the launch did not reset are NOT written; an invalid episode's row is
+ * written as computed, non-finite values included.  Everything else the launch writes, and the stored env state, is bit for bit what it is with
+ * nothing bound; without DM_AUTO_RESET the binding has no effect.  dm_step_envs (the subset route) ignores the binding.  The buffers must stay
+ * allocated while bound; the rows are written on the ctx stream by the step kernel itself. */
+int dm_set_terminal_outputs(dm_ctx* ctx, float* term_states_dev, float* term_goals_dev);
 
 /* dm_step_batch for a SUBSET of the ctx's envs: env_ids[n] distinct ids; actions (n x A, NULL = keep the latched targets), states (n x S), rewards,
  * flags, amp_obs (n x dm_amp_obs_size(), imitate_amp scenes) and clocks (n x 5 doubles: kin_time, ctrl_time, init_time_offset, timer_time, timer_max
@@ -475,6 +486,24 @@ int dm_norm_normalize(dm_normalizer* norm, const float* x_dev, int n, float* out
  * ordered on hip_stream): the actor's next dm_policy_forward on that stream normalises with the statistics of the last dm_norm_update / dm_norm_set.
  * s_norm at column 0 and g_norm at column state_size, as the reference keeps them (learning/rl_agent.py:212-222). */
 int dm_policy_bind_obs_normalizer(dm_policy* policy, dm_normalizer* norm, int first_column, void* hip_stream);
+
+/* ---- TD(lambda) returns over a device-resident rollout: RLUtil.compute_return (learning/rl_util.py:3-18) per path with the end-of-path rules of
+ * learning/ppo_agent.py:251-284, for T control steps of N envs that stayed in HBM.  All arrays are DEVICE pointers, time-major (row t = the N envs'
+ * values of step t, the way a sampler stacks TorchVecEnv's outputs): rewards T x N; values (T + 1) x N, values[t] = the critic on the observation the
+ * action of step t was taken from, values[T] = the critic on the observation after the last step; term_values T x N, the critic on the terminal
+ * observation of step t (dm_set_terminal_outputs), used only where done[t] != 0; terminate (eTerminate), done (the env was reset in step t:
+ * episode_end != 0 or valid == 0) and valid (NULL = every episode valid), T x N int32 each.  Per env column, backwards in time, the value behind step t is
+ * v_next = values[t + 1] if the step is not done, val_fail / val_succ if it is done with terminate Fail / Succ, term_values[t] if it is done with Null;
+ * a step that closes a path (done, or t = T - 1) gets ret = r + gamma v_next, any other ret = r + gamma ((1 - td_lambda) v_next + td_lambda ret[t + 1]):
+ * fp64 arithmetic on the fp32 inputs in the reference's association, rounded once into returns (T x N floats).  gamma = 0 gives the rewards back
+ * (ppo_agent.py:269-270).  mask (T x N int32, NULL = not wanted): 0 for every step of an episode that ended with valid == 0 inside the window, back to
+ * the previous done or to t = 0 -- the reference's driver discards such an episode --, 1 elsewhere.
+ * ONE DEVIATION: the reference stores whole paths only; a rollout window cut at T is bootstrapped from values[T] like a Null path end, and a path that
+ * began before the window starts at row 0.  Advantages, value clipping and their normalisation stay the caller's (one-line tensor ops).
+ * Needs no dm_ctx; asynchronous on hip_stream of device device_id.  T < 1, N < 1 or a NULL required pointer: error, nothing is launched. */
+int dm_td_lambda_returns(int device_id, int T, int N, const float* rewards_dev, const float* values_dev, const float* term_values_dev,
+                         const int32_t* terminate_dev, const int32_t* done_dev, const int32_t* valid_dev, double gamma, double td_lambda,
+                         double val_fail, double val_succ, float* returns_dev, int32_t* mask_dev, void* hip_stream);
 
 #ifdef __cplusplus
 }
