@@ -775,4 +775,109 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
 #undef DMF_STAMP
 }
 
+// ---------------------------------------------------------------- weight refresh on the device (dm_policy_set_weights)
+// ONE launch re-packs every array of a context from fp32 sources in device memory into the buffers the forward kernels read.  The kernel is
+// DESTINATION-ordered: a job is one destination array, a workgroup is 256 consecutive destination units of one job (PackArgs::first maps blockIdx to the
+// job), and a thread owns one unit -- a whole 16-byte fragment row [8 bf16] of a packed weight array or of the fused stream, or one fp32 element of a
+// vector.  The thread computes the source (k, n) of its row from the row's index (the inverse of pack_weights, composed with the inverse of
+// pack_fused_stream(_gated) for the fused stream, which is therefore written straight from the fp32 source and not copied from w1p / w2p), reads eight
+// fp32 ELEMENTS (sources are only 4-byte aligned: torch views) and writes one vector store.  Source layout by PackArgs::out_in: [in x out] row-major
+// (tf.layers.dense: the 16 lanes of a quarter-wave read 64 consecutive bytes per k) or [out x in] (torch.nn.Linear.weight: 32 consecutive bytes per
+// lane, 128 per column over the four quarter-waves).  Rounding: f32_to_bf16_host's, NaN case included.  A fused-stream row whose source array is not
+// given keeps its bytes (the host adds a job only for a source that is there).
+enum { PK_FRAG = 0, PK_FUSED = 1, PK_VEC = 2, PK_RECIP = 3, PK_MAX_JOBS = 28 };
+struct PackJob {
+    int kind;
+    int K, N;              // PK_FRAG: the source is W [K x N] ([N x K] with out_in), rows / columns behind them are zero padding; PK_VEC / PK_RECIP: N source elements
+    int KS;                // PK_FRAG: k-steps of the destination (padded K / 32)
+    int rows;              // destination units: 16-byte rows (PK_FRAG, PK_FUSED) or fp32 elements (PK_VEC: zero behind N; PK_RECIP: 1 / x)
+    const float* src; void* dst;
+};
+struct PackFused {         // sources of the fused stream (any may be null: those rows are kept); widths fixed by k_policy_fused: H1 = 1024, H2 = 512, GH = 64
+    int gated, NB1, S;     // NB1 = K1 / 64 layer-1 blocks per chunk; w1 is [S x 1024]
+    const float *w1, *w2;
+    const float *ws[2], *wb[2], *bs[2], *bb[2];   // gate{i}/dense_1 and gate{i}/dense kernels [64 x H_i], their biases [H_i]
+};
+struct PackArgs { int njobs, out_in; int first[PK_MAX_JOBS + 1]; PackJob job[PK_MAX_JOBS]; PackFused fs; };
+
+// f32_to_bf16_host for device code: round to nearest even, every NaN -> 0x7fc0 (the device f32_to_bf16 above has no NaN case)
+DMP_DEV uint16_t f32_to_bf16_nan(float f) {
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+struct alignas(16) u32x4_rec { uint32_t x, y, z, w; };
+// the row of lane l in fragment (nt, ks) of W [K x N]: column n = 16 nt + (l & 15), k = 32 ks + 8 (l >> 4) + i
+DMP_DEV u32x4_rec pack_row(const float* W, int K, int N, int out_in, int nt, int ks, int l) {
+    const int n = 16 * nt + (l & 15), k0 = 32 * ks + 8 * (l >> 4);
+    // branch-free: a padding element reads W[0] and is replaced by zero afterwards, so the eight loads of a lane are in flight together
+    float f[8]; uint32_t h[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+        const int k = k0 + i;
+        const size_t at = out_in ? (size_t)n * K + k : (size_t)k * N + n;
+        f[i] = W[(k < K && n < N) ? at : 0];
+    }
+#pragma unroll
+    for (int i = 0; i < 8; ++i) h[i] = (k0 + i < K && n < N) ? (uint32_t)f32_to_bf16_nan(f[i]) : 0u;
+    u32x4_rec v; v.x = h[0] | (h[1] << 16); v.y = h[2] | (h[3] << 16); v.z = h[4] | (h[5] << 16); v.w = h[6] | (h[7] << 16);
+    return v;
+}
+// slots 4 / 5 of a gate tile: the lane's four biases (features 16 ft + 4 (l >> 4) + r) as fp32 bits
+DMP_DEV u32x4_rec pack_bias_row(const float* b, int ft, int l) {
+    const float* s = b + 16 * ft + 4 * (l >> 4);
+    u32x4_rec v; v.x = __builtin_bit_cast(uint32_t, s[0]); v.y = __builtin_bit_cast(uint32_t, s[1]); v.z = __builtin_bit_cast(uint32_t, s[2]); v.w = __builtin_bit_cast(uint32_t, s[3]);
+    return v;
+}
+
+__global__ void __launch_bounds__(256) k_policy_pack(PackArgs a) {
+    const int b = blockIdx.x;
+    int j = 0;
+    while (j + 1 < a.njobs && b >= a.first[j + 1]) ++j;
+    const int kind = a.job[j].kind, rows = a.job[j].rows;
+    const int r = (b - a.first[j]) * 256 + (int)threadIdx.x;
+    if (r >= rows) return;
+    if (kind == PK_VEC || kind == PK_RECIP) {
+        const float* src = a.job[j].src;
+        float v = 0.0f;
+        if (r < a.job[j].N) v = (kind == PK_RECIP) ? 1.0f / src[r] : src[r];
+        static_cast<float*>(a.job[j].dst)[r] = v;
+        return;
+    }
+    u32x4_rec* dst = static_cast<u32x4_rec*>(a.job[j].dst) + r;
+    const int f = r >> 6, l = r & 63;                     // fragment of the destination, lane row inside it
+    if (kind == PK_FRAG) {
+        const int KS = a.job[j].KS;
+        *dst = pack_row(a.job[j].src, a.job[j].K, a.job[j].N, a.out_in, f / KS, f % KS, l);
+        return;
+    }
+    // PK_FUSED: f = (w * NBLK + block) * 8 + slot, the inverse of pack_fused_stream / pack_fused_stream_gated (dm_policy_host.h)
+    const PackFused& s = a.fs;
+    const int NB1 = s.NB1, KS1 = 2 * NB1, NBQ = NB1 + (s.gated ? 11 : 8), NBLK = 4 * NBQ + (s.gated ? 6 : 0);
+    const int w = f / (8 * NBLK), blk = (f >> 3) % NBLK, slot = f & 7;
+    int layer = -1, ft = 0, gs = 0;                       // a gate slot: layer, feature tile, slot 0 .. 5 of the tile
+    if (blk < 4 * NBQ) {
+        const int q = blk / NBQ, bq = blk % NBQ;
+        if (bq < NB1) {                                   // two k-steps x feature tiles 16 q + 4 w + j of layer 1
+            if (s.w1) *dst = pack_row(s.w1, s.S, 1024, a.out_in, 16 * q + 4 * w + (slot & 3), 2 * bq + (slot >> 2), l);
+            return;
+        }
+        if (!s.gated || bq >= NB1 + 3) {                  // k-step 8 q + ksl of layer 2 x feature tiles 8 w + n
+            if (s.w2) *dst = pack_row(s.w2, 1024, 512, a.out_in, 8 * w + slot, 8 * q + bq - NB1 - (s.gated ? 3 : 0), l);
+            return;
+        }
+        const int g = (bq - NB1) * 8 + slot;
+        layer = 0; ft = 16 * q + 4 * w + g / 6; gs = g % 6;
+    } else {
+        const int g = (blk - 4 * NBQ) * 8 + slot;
+        layer = 1; ft = 8 * w + g / 6; gs = g % 6;
+    }
+    const int H = layer ? 512 : 1024;
+    if (gs < 2) { if (s.ws[layer]) *dst = pack_row(s.ws[layer], 64, H, a.out_in, ft, gs, l); }
+    else if (gs < 4) { if (s.wb[layer]) *dst = pack_row(s.wb[layer], 64, H, a.out_in, ft, gs - 2, l); }
+    else if (gs == 4) { if (s.bs[layer]) *dst = pack_bias_row(s.bs[layer], ft, l); }
+    else if (s.bb[layer]) *dst = pack_bias_row(s.bb[layer], ft, l);
+}
+
 }  // namespace dmp

@@ -300,3 +300,149 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
 }
 
 }  // extern "C"
+
+// ---------------------------------------------------------------- weights into a live context (k_policy_pack, dm_policy.h)
+// The jobs of one k_policy_pack launch: one per destination array whose source is given, in the buffers policy_create allocated (their sizes: packed_array)
+struct PackPlan {
+    dmp::PackArgs a; unsigned blocks = 0;
+    PackPlan() { memset(&a, 0, sizeof(a)); }
+    void add(int kind, const float* src, const void* dst, int K, int N, int KS, size_t rows) {
+        if (a.njobs >= dmp::PK_MAX_JOBS) return;
+        dmp::PackJob& j = a.job[a.njobs];
+        j.kind = kind; j.K = K; j.N = N; j.KS = KS; j.rows = (int)rows; j.src = src; j.dst = const_cast<void*>(dst);
+        a.first[a.njobs++] = (int)blocks; blocks += (unsigned)((rows + 255) / 256); a.first[a.njobs] = (int)blocks;
+    }
+    // W [K x N] into fragments padded to Kp x Np
+    void frag(const float* W, const uint16_t* dst, int K, int N, int Kp, int Np) { if (W) add(dmp::PK_FRAG, W, dst, K, N, Kp / 32, (size_t)Kp * Np / 8); }
+    void vec(const float* src, const float* dst, int n, int np) { if (src) add(dmp::PK_VEC, src, dst, 0, n, 0, (size_t)np); }
+};
+
+// bytes of the fused stream a context holds (pack_fused_stream / pack_fused_stream_gated)
+static size_t fused_stream_bytes(const dm_policy* p) {
+    const int NB1 = p->pd.K1 / 64, NBLK = p->gated ? 4 * (NB1 + 3 + 8) + 6 : 4 * (NB1 + 8);
+    return (size_t)4 * NBLK * 8 * 512 * 2;
+}
+
+// the packed device array `which` (include/dm_hip.h dm_policy_packed) and its size; null: the context holds no such array
+static const void* packed_array(const dm_policy* p, int which, size_t* bytes) {
+    const dmp::PolicyDev& d = p->pd; const dmp::GateDev& q = p->gd;
+    const size_t f = sizeof(float);
+    switch (which) {
+    case DM_POLICY_PACKED_W1P: *bytes = (size_t)d.K1 * d.H1 * 2; return d.w1p;
+    case DM_POLICY_PACKED_W2P: *bytes = (size_t)d.H1 * d.H2 * 2; return d.w2p;
+    case DM_POLICY_PACKED_W3P: *bytes = (size_t)d.H2 * d.N3 * 2; return d.w3p;
+    case DM_POLICY_PACKED_B1: *bytes = f * d.H1; return d.b1;
+    case DM_POLICY_PACKED_B2: *bytes = f * d.H2; return d.b2;
+    case DM_POLICY_PACKED_B3: *bytes = f * d.N3; return d.b3;
+    case DM_POLICY_PACKED_S_MEAN: *bytes = f * d.S; return d.s_mean;
+    case DM_POLICY_PACKED_S_INV_STD: *bytes = f * d.S; return d.s_inv_std;
+    case DM_POLICY_PACKED_A_MEAN: *bytes = f * d.A; return d.a_mean;
+    case DM_POLICY_PACKED_A_STD: *bytes = f * d.A; return d.a_std;
+    case DM_POLICY_PACKED_LOGSTD: *bytes = f * d.A; return d.logstd;
+    case DM_POLICY_PACKED_WFS: *bytes = fused_stream_bytes(p); return d.wfs;
+    default: break;
+    }
+    if (!p->gated || which < DM_POLICY_PACKED_GATE_WCP || which > DM_POLICY_PACKED_GATE_BS1) return nullptr;
+    if (which == DM_POLICY_PACKED_GATE_WCP) { *bytes = (size_t)q.KG * q.GC * 2; return q.wcp; }
+    if (which == DM_POLICY_PACKED_GATE_BC) { *bytes = f * q.GC; return q.bc; }
+    const int i = (which - DM_POLICY_PACKED_GATE_WEP0) / 6, H = i ? d.H2 : d.H1;      // six ids per gated layer, in the order of dm_policy_gate_params
+    switch ((which - DM_POLICY_PACKED_GATE_WEP0) % 6) {
+    case 0: *bytes = (size_t)q.GC * q.GH * 2; return q.wep[i];
+    case 1: *bytes = f * q.GH; return q.be[i];
+    case 2: *bytes = (size_t)q.GH * H * 2; return q.wbp[i];
+    case 3: *bytes = f * H; return q.bb[i];
+    case 4: *bytes = (size_t)q.GH * H * 2; return q.wsp[i];
+    default: *bytes = f * H; return q.bs[i];
+    }
+}
+
+static int width_mismatch(const char* what, int got, int have) {
+    return fail(std::string("dm_policy_set_weights: ") + what + " is " + std::to_string(got) + ", the context has " + std::to_string(have));
+}
+
+extern "C" {
+
+int dm_policy_set_weights(dm_policy* p, const dm_policy_params* pp, const dm_policy_gate_params* gp, int flags, void* hip_stream) {
+    if (!p || !pp) return fail("null argument");
+    if (flags & ~(DM_DEVICE_PTRS | DM_WEIGHTS_OUT_IN)) return fail("dm_policy_set_weights: flags takes DM_DEVICE_PTRS and DM_WEIGHTS_OUT_IN only");
+    const dmp::PolicyDev& d = p->pd; const dmp::GateDev& q = p->gd;
+    if (pp->state_dim != d.S) return width_mismatch("state_dim", pp->state_dim, d.S);
+    if (pp->hidden1 != d.H1) return width_mismatch("hidden1", pp->hidden1, d.H1);
+    if (pp->hidden2 != d.H2) return width_mismatch("hidden2", pp->hidden2, d.H2);
+    if (pp->action_dim != d.A) return width_mismatch("action_dim", pp->action_dim, d.A);
+    if (gp && !p->gated) return fail("dm_policy_set_weights: gate parameters for a context without a gate (dm_policy_create)");
+    if (!gp && p->gated) return fail("dm_policy_set_weights: a gated context (dm_policy_create_gated) needs its dm_policy_gate_params (null arrays in it keep the gate)");
+    if (gp) {
+        if (gp->goal_dim != q.G) return width_mismatch("goal_dim", gp->goal_dim, q.G);
+        if (gp->gate_common != q.GC) return width_mismatch("gate_common", gp->gate_common, q.GC);
+        if (gp->gate_hidden != q.GH) return width_mismatch("gate_hidden", gp->gate_hidden, q.GH);
+    }
+    dm_policy_params w = *pp; dm_policy_gate_params g; memset(&g, 0, sizeof(g)); if (gp) g = *gp;
+    // every array of the two structs with its element count, in one table: the host mode stages through it, nothing else walks the fields
+    struct Arr { const float** ptr; size_t count; };
+    const size_t S = d.S, H1 = d.H1, H2 = d.H2, A = d.A, G = q.G, GC = q.GC, GH = q.GH;
+    const Arr arrs[] = {{&w.w1, S * H1}, {&w.b1, H1}, {&w.w2, H1 * H2}, {&w.b2, H2}, {&w.w3, H2 * A}, {&w.b3, A}, {&w.s_mean, S}, {&w.s_std, S}, {&w.a_mean, A}, {&w.a_std, A}, {&w.logstd, A},
+                        {&g.gc_w, G * GC}, {&g.gc_b, GC}, {&g.g0_w, GC * GH}, {&g.g0_b, GH}, {&g.g0_bias_w, GH * H1}, {&g.g0_bias_b, H1}, {&g.g0_scale_w, GH * H1}, {&g.g0_scale_b, H1},
+                        {&g.g1_w, GC * GH}, {&g.g1_b, GH}, {&g.g1_bias_w, GH * H2}, {&g.g1_bias_b, H2}, {&g.g1_scale_w, GH * H2}, {&g.g1_scale_b, H2}};
+    DevGuard guard(p->device_id);
+    rt_stream stream = (rt_stream)hip_stream;
+    int rc = 0;
+    // host arrays: one scoped device temporary holds them all, the same kernel reads it
+    std::vector<float> host;
+    if (!(flags & DM_DEVICE_PTRS)) for (const Arr& r : arrs) if (*r.ptr) host.insert(host.end(), *r.ptr, *r.ptr + r.count);
+    DevTmp stage(rc, stream, sizeof(float) * host.size(), host.empty() ? nullptr : host.data());
+    if (rc) return rc;
+    if (stage.p) { const float* at = (const float*)stage.p; for (const Arr& r : arrs) if (*r.ptr) { *r.ptr = at; at += r.count; } }
+
+    PackPlan plan; plan.a.out_in = (flags & DM_WEIGHTS_OUT_IN) ? 1 : 0;
+    plan.frag(w.w1, d.w1p, d.S, d.H1, d.K1, d.H1); plan.frag(w.w2, d.w2p, d.H1, d.H2, d.H1, d.H2); plan.frag(w.w3, d.w3p, d.H2, d.A, d.H2, d.N3);
+    plan.vec(w.b1, d.b1, d.H1, d.H1); plan.vec(w.b2, d.b2, d.H2, d.H2); plan.vec(w.b3, d.b3, d.A, d.N3);
+    plan.vec(w.s_mean, d.s_mean, d.S, d.S); if (w.s_std) plan.add(dmp::PK_RECIP, w.s_std, d.s_inv_std, 0, d.S, 0, (size_t)d.S);
+    plan.vec(w.a_mean, d.a_mean, d.A, d.A); plan.vec(w.a_std, d.a_std, d.A, d.A); plan.vec(w.logstd, d.logstd, d.A, d.A);
+    const float* sw[2] = {g.g0_scale_w, g.g1_scale_w}; const float* sb[2] = {g.g0_scale_b, g.g1_scale_b};
+    const float* bw[2] = {g.g0_bias_w, g.g1_bias_w}; const float* bb[2] = {g.g0_bias_b, g.g1_bias_b};
+    if (p->gated) {
+        const float* ew[2] = {g.g0_w, g.g1_w}; const float* eb[2] = {g.g0_b, g.g1_b};
+        plan.frag(g.gc_w, q.wcp, q.G, q.GC, q.KG, q.GC); plan.vec(g.gc_b, q.bc, q.GC, q.GC);
+        for (int i = 0; i < 2; ++i) {
+            const int H = i ? d.H2 : d.H1;
+            plan.frag(ew[i], q.wep[i], q.GC, q.GH, q.GC, q.GH); plan.vec(eb[i], q.be[i], q.GH, q.GH);
+            plan.frag(bw[i], q.wbp[i], q.GH, H, q.GH, H); plan.vec(bb[i], q.bb[i], H, H);
+            plan.frag(sw[i], q.wsp[i], q.GH, H, q.GH, H); plan.vec(sb[i], q.bs[i], H, H);
+        }
+    }
+    // the fused stream straight from the fp32 sources; a row whose source is not given keeps its bytes
+    dmp::PackFused& fs = plan.a.fs;
+    fs.gated = p->gated ? 1 : 0; fs.NB1 = d.K1 / 64; fs.S = d.S; fs.w1 = w.w1; fs.w2 = w.w2;
+    for (int i = 0; i < 2; ++i) { fs.ws[i] = sw[i]; fs.wb[i] = bw[i]; fs.bs[i] = sb[i]; fs.bb[i] = bb[i]; }
+    const bool fused_src = w.w1 || w.w2 || (p->gated && (sw[0] || sw[1] || bw[0] || bw[1] || sb[0] || sb[1] || bb[0] || bb[1]));
+    if (d.wfs && fused_src) plan.add(dmp::PK_FUSED, nullptr, d.wfs, 0, 0, 0, fused_stream_bytes(p) / 16);   // (its sources: PackFused)
+    if (plan.blocks == 0) return 0;                        // nothing given: nothing to do
+    RT_LAUNCH4(dmp::k_policy_pack, plan.blocks, stream, plan.a);
+#ifndef DM_EMU
+    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
+#endif
+    if (stage.p && rt_sync(stream) != 0) return fail("stream synchronize failed");      // the temporary is freed with this scope
+    return 0;
+}
+
+int dm_policy_read_packed(dm_policy* p, int which, void* host_out, size_t capacity, size_t* bytes) {
+    if (!p) return fail("null argument");
+    size_t n = 0;
+    const void* dev = packed_array(p, which, &n);
+    if (!dev) {
+        if (which == DM_POLICY_PACKED_WFS) return fail("dm_policy_read_packed: this context holds no fused weight stream (widths k_policy_fused is not compiled for: the per-layer kernels)");
+        if (which >= DM_POLICY_PACKED_GATE_WCP && which <= DM_POLICY_PACKED_GATE_BS1) return fail("dm_policy_read_packed: a gate array of a context without a gate");
+        return fail("dm_policy_read_packed: unknown array id");
+    }
+    if (bytes) *bytes = n;
+    if (!host_out) return 0;                               // size query
+    if (capacity < n) return fail("dm_policy_read_packed: the host buffer is smaller than the array (" + std::to_string(n) + " bytes)");
+    DevGuard guard(p->device_id);
+#ifndef DM_EMU
+    if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");      // a refresh pending on any stream of the device is complete
+#endif
+    return rt_d2h(host_out, dev, n, 0) == 0 ? 0 : fail("device to host copy failed");
+}
+
+}  // extern "C"

@@ -40,6 +40,14 @@ def _fp(a):
     return None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
 
 
+PLAIN_KEYS = tuple(k for k, _ in _PolicyParams._fields_[4:15])
+DM_DEVICE_PTRS, DM_WEIGHTS_OUT_IN = 1, 32      # include/dm_hip.h
+# dm_policy_packed (include/dm_hip.h): the device arrays read_packed hands back, by the names of dm_policy.h PolicyDev / GateDev
+PACKED_IDS = dict(w1p=0, w2p=1, w3p=2, b1=3, b2=4, b3=5, s_mean=6, s_inv_std=7, a_mean=8, a_std=9, logstd=10, wfs=11, gate_wcp=16, gate_bc=17,
+                  gate_wep0=18, gate_be0=19, gate_wbp0=20, gate_bb0=21, gate_wsp0=22, gate_bs0=23,
+                  gate_wep1=24, gate_be1=25, gate_wbp1=26, gate_bb1=27, gate_wsp1=28, gate_bs1=29)
+
+
 class Policy:
     """weights: dict with w1 [S,H1], b1 [H1], w2 [H1,H2], b2 [H2], w3 [H2,A], b3 [A] (tf.layers.dense layout) and optional
     s_mean, s_std, a_mean, a_std, logstd.  With the arrays of GATE_KEYS and "goal_dim" (the last goal_dim of the S input columns are the goal) the
@@ -58,6 +66,8 @@ class Policy:
         pp = _PolicyParams(self.S, self.H1, self.H2, self.A, *[_fp(w[k]) for k in ("w1", "b1", "w2", "b2", "w3", "b3", "s_mean", "s_std", "a_mean", "a_std", "logstd")],
                            float(s_clip))
         self.h = C.c_void_p()
+        self.device_id = int(device_id)
+        self.gate_dims = None
         self.gated = is_gated(weights)
         if self.gated:
             missing = [k for k in GATE_KEYS + ("goal_dim",) if weights.get(k) is None]
@@ -74,6 +84,7 @@ class Policy:
             if not hasattr(self.lib, "dm_policy_create_gated"):
                 raise RuntimeError("libdm_hip: this library has no dm_policy_create_gated (rebuild it)")
             gp = _GateParams(G, GC, GH, *[_fp(gw[k]) for k in GATE_KEYS])
+            self.gate_dims = (G, GC, GH)
             rc = self.lib.dm_policy_create_gated(int(device_id), C.byref(pp), C.byref(gp), C.byref(self.h))
         else:
             rc = self.lib.dm_policy_create(int(device_id), C.byref(pp), C.byref(self.h))
@@ -139,6 +150,83 @@ class Policy:
             raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
         return dict(K1=int(out[0]), N3=int(out[1]), fused=bool(out[2]), path=int(out[3]), rows=int(out[4]), gated=bool(out[5]), goal_dim=int(out[6]),
                     gated_fused=bool(out[7]))
+
+    # ---- new weights into the live context (include/dm_hip.h dm_policy_set_weights): one kernel launch packs them in place
+    def weight_shapes(self, out_in: bool = False) -> dict:
+        """the shape of every array set_weights* takes, by key: 2-D arrays [in, out] (tf.layers.dense), or [out, in] (torch.nn.Linear.weight) with out_in"""
+        S, H1, H2, A = self.S, self.H1, self.H2, self.A
+        sh = dict(w1=(S, H1), b1=(H1,), w2=(H1, H2), b2=(H2,), w3=(H2, A), b3=(A,), s_mean=(S,), s_std=(S,), a_mean=(A,), a_std=(A,), logstd=(A,))
+        if self.gated:
+            G, GC, GH = self.gate_dims
+            sh.update(gc_w=(G, GC), gc_b=(GC,))
+            for i, H in ((0, H1), (1, H2)):
+                sh.update({"g%d_w" % i: (GC, GH), "g%d_b" % i: (GH,), "g%d_bias_w" % i: (GH, H), "g%d_bias_b" % i: (H,), "g%d_scale_w" % i: (GH, H), "g%d_scale_b" % i: (H,)})
+        return {k: (v[::-1] if out_in else v) for k, v in sh.items()}
+
+    def _set_weights(self, ptrs: dict, flags: int, stream: int):
+        if not hasattr(self.lib, "dm_policy_set_weights"):
+            raise RuntimeError("libdm_hip: this library has no dm_policy_set_weights (rebuild it)")
+        unknown = [k for k in ptrs if k not in PLAIN_KEYS + GATE_KEYS + ("goal_dim",)]
+        if unknown:
+            raise ValueError("set_weights: unknown key %s" % unknown[0])
+        fp = lambda k: C.cast(C.c_void_p(int(ptrs[k])), C.POINTER(C.c_float)) if ptrs.get(k) else None
+        pp = _PolicyParams(self.S, self.H1, self.H2, self.A, *[fp(k) for k in PLAIN_KEYS], 0.0)
+        gp = None
+        if self.gated or any(k in ptrs for k in GATE_KEYS):       # (a gate for a plain context: the library refuses it)
+            G, GC, GH = self.gate_dims if self.gated else (int(ptrs.get("goal_dim", 0)), 0, 0)
+            gp = C.byref(_GateParams(G, GC, GH, *[fp(k) for k in GATE_KEYS]))
+        self.lib.dm_policy_set_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        if self.lib.dm_policy_set_weights(self.h, C.byref(pp), gp, int(flags), C.c_void_p(stream) if stream else None) != 0:
+            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+
+    def set_weights(self, weights: dict):
+        """host arrays under the constructor's keys (and GATE_KEYS); a missing key keeps what the context holds.  Staged through a device temporary; synchronous."""
+        want = self.weight_shapes()
+        w = {k: np.ascontiguousarray(v, dtype=np.float32) for k, v in weights.items() if v is not None and k != "goal_dim"}
+        for k, a in w.items():
+            if k in want and a.shape != want[k]:
+                raise ValueError("set_weights: %s is %s, not %s" % (k, a.shape, want[k]))
+        self._set_weights({k: a.ctypes.data for k, a in w.items()}, 0, 0)
+
+    def set_weights_device(self, ptrs: dict, out_in: bool = False, stream: int = 0):
+        """raw device addresses of fp32 arrays (4-byte aligned is enough) under the same keys, shapes as weight_shapes(out_in); asynchronous on `stream`:
+        no allocation, no host copy, no synchronisation.  Ordering against forwards on other streams is the caller's."""
+        self._set_weights(ptrs, DM_DEVICE_PTRS | (DM_WEIGHTS_OUT_IN if out_in else 0), stream)
+
+    def set_weights_torch(self, tensors: dict, layout: str = "in_out", stream=None):
+        """torch tensors on the policy's device, e.g. layout="out_in" with the .weight / .bias of torch.nn.Linear layers after an optimiser step.  Runs on torch's
+        current stream unless `stream` (a torch.cuda.Stream or a raw handle) is given: enqueue it behind the optimiser step and in front of the next forward."""
+        import torch
+        if layout not in ("in_out", "out_in"):
+            raise ValueError('layout must be "in_out" or "out_in"')
+        want = self.weight_shapes(layout == "out_in")
+        dev = torch.device("cuda", self.device_id)
+        ptrs = {}
+        for k, t in tensors.items():
+            if t is None or k == "goal_dim":
+                continue
+            if k not in want:
+                raise ValueError("set_weights: unknown key %s" % k)
+            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != want[k] or not t.is_contiguous():
+                raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (k, want[k], dev))
+            ptrs[k] = t.data_ptr()
+        if stream is None:
+            stream = torch.cuda.current_stream(dev)
+        self.set_weights_device(ptrs, layout == "out_in", int(getattr(stream, "cuda_stream", stream)))
+
+    def read_packed(self, name: str) -> np.ndarray:
+        """the bytes (uint8) of one packed device array as the kernels read it (PACKED_IDS: w1p .. logstd, wfs, gate_*); synchronises the device.
+        RuntimeError where the context holds no such array (wfs on widths without the fused kernel, gate_* on a plain context)."""
+        if not hasattr(self.lib, "dm_policy_read_packed"):
+            raise RuntimeError("libdm_hip: this library has no dm_policy_read_packed (rebuild it)")
+        self.lib.dm_policy_read_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
+        n = C.c_size_t(0)
+        if self.lib.dm_policy_read_packed(self.h, PACKED_IDS[name], None, 0, C.byref(n)) != 0:
+            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        out = np.zeros(n.value, np.uint8)
+        if self.lib.dm_policy_read_packed(self.h, PACKED_IDS[name], out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)) != 0:
+            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        return out
 
     def close(self):
         if getattr(self, "h", None):

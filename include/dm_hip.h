@@ -11,6 +11,7 @@
  */
 #ifndef DM_HIP_H
 #define DM_HIP_H
+#include <stddef.h>
 #include <stdint.h>
 #ifdef __cplusplus
 extern "C" {
@@ -458,6 +459,35 @@ typedef struct {
     const float *g1_w, *g1_b, *g1_bias_w, *g1_bias_b, *g1_scale_w, *g1_scale_b;
 } dm_policy_gate_params;
 int dm_policy_create_gated(int device_id, const dm_policy_params* params, const dm_policy_gate_params* gate, dm_policy** out);
+
+/* New weights into a live context, in place: ONE kernel launch on hip_stream (k_policy_pack, deepmimic_amd/csrc/dm_policy.h) rounds the fp32 arrays to bf16
+ * (round to nearest even, NaN -> 0x7fc0) and scatters them into the fragment layouts the forward kernels read -- w1p / w2p / w3p, the fused stream, the gate's
+ * arrays and the gated fused stream with its interleaved scale / bias vectors -- in the buffers dm_policy_create(_gated) allocated, byte for byte what create
+ * makes of the same arrays.  A learner whose parameters live on the device calls it after every optimiser step instead of destroy + create.
+ *  - params / gate: the structs of create.  The widths (state_dim, hidden1, hidden2, action_dim; goal_dim, gate_common, gate_hidden) must equal the context's,
+ *    else an error names the mismatch and nothing is written.  gate must be non-NULL exactly when the context is gated.
+ *  - a NULL array keeps what the context holds (only logstd, only the three layers, ...).  s_mean / s_std become s_mean / 1 / s_std; s_clip is ignored and
+ *    stays as created; K1 / N3 and the choice of kernels stay what create made them (dm_policy_info).
+ *  - flags: DM_DEVICE_PTRS -- the arrays are DEVICE pointers (4-byte alignment is enough: views of a torch tensor); the call then allocates nothing, copies
+ *    nothing from the host and does not synchronise: it may be enqueued between two dm_policy_forward on one stream, and the second one sees the new weights.
+ *    Without it they are host arrays, staged through one device temporary of the call; the call then synchronises hip_stream.
+ *    DM_WEIGHTS_OUT_IN -- every 2-D array is [out x in] row-major (torch.nn.Linear.weight) instead of [in x out] (tf.layers.dense); vectors are the same.
+ *  - ordering is the caller's: the refresh is ordered on hip_stream like every other call here.  A forward on ANOTHER stream that overlaps it reads a mixture
+ *    of old and new weights; so does a bound normaliser copy (dm_policy_bind_obs_normalizer) racing a refresh of s_mean / s_std. */
+enum { DM_WEIGHTS_OUT_IN = 32 };            /* shares the flag word of DM_DEVICE_PTRS */
+int dm_policy_set_weights(dm_policy* policy, const dm_policy_params* params, const dm_policy_gate_params* gate, int flags, void* hip_stream);
+/* One packed DEVICE array of the context to the host, as the kernels read it (tests, diagnosis): *bytes = its size; host_out = NULL asks for the size only,
+ * else capacity must cover it.  Synchronises the device first.  DM_POLICY_PACKED_WFS fails on a context without a fused stream (out[2] of dm_policy_info),
+ * the gate ids on a context without a gate.  Sizes: w1p K1 x hidden1, w2p hidden1 x hidden2, w3p hidden2 x N3 bf16 in [n-tile][k-step][lane][8] order;
+ * b3 N3 floats (zero-padded); s_inv_std = 1 / s_std; gate ids per gated layer i in the order of dm_policy_gate_params. */
+enum dm_policy_packed {
+    DM_POLICY_PACKED_W1P = 0, DM_POLICY_PACKED_W2P, DM_POLICY_PACKED_W3P, DM_POLICY_PACKED_B1, DM_POLICY_PACKED_B2, DM_POLICY_PACKED_B3,
+    DM_POLICY_PACKED_S_MEAN, DM_POLICY_PACKED_S_INV_STD, DM_POLICY_PACKED_A_MEAN, DM_POLICY_PACKED_A_STD, DM_POLICY_PACKED_LOGSTD, DM_POLICY_PACKED_WFS,
+    DM_POLICY_PACKED_GATE_WCP = 16, DM_POLICY_PACKED_GATE_BC,                                       /* gc_w (KG x gate_common, KG = goal_dim rounded up to 32), gc_b */
+    DM_POLICY_PACKED_GATE_WEP0, DM_POLICY_PACKED_GATE_BE0, DM_POLICY_PACKED_GATE_WBP0, DM_POLICY_PACKED_GATE_BB0, DM_POLICY_PACKED_GATE_WSP0, DM_POLICY_PACKED_GATE_BS0,
+    DM_POLICY_PACKED_GATE_WEP1, DM_POLICY_PACKED_GATE_BE1, DM_POLICY_PACKED_GATE_WBP1, DM_POLICY_PACKED_GATE_BB1, DM_POLICY_PACKED_GATE_WSP1, DM_POLICY_PACKED_GATE_BS1
+};
+int dm_policy_read_packed(dm_policy* policy, int which, void* host_out, size_t capacity, size_t* bytes);
 
 /* ---- Running observation statistics on the device: the Normalizer of the reference's learner (learning/normalizer.py:6-152; the
  * s_norm / g_norm / amp_obs_norm of learning/rl_agent.py:466-483, amp_agent.py:290-291) for records that stay in HBM.
