@@ -29,6 +29,22 @@ struct PolicyDev {
 };
 
 struct GateDev;
+// The scalar head of the device nets (include/dm_hip.h dm_scalar_head): a net with ONE output column -- the critic of learning/pg_agent.py:161-171, the AMP
+// discriminator of learning/amp_agent.py:178-194 -- whose last step is not the Gaussian head but, per row, with y = acc + b3[0]:
+//   HEAD_VALUE  v = min(max(y, lo), hi) (amp_agent.py:441-443; infinite bounds: PPO), then val_fail / val_succ where terminate is Fail (1) / Succ (2) (ppo_agent.py:262-264)
+//   HEAD_STYLE  d = 1 - y, r = scale max(0, 1 - d^2 / 4), then (1 - lerp) r + lerp task_r with a task reward (amp_agent.py:294-297, 393-434)
+// No noise is drawn, logstd / a_mean / a_std are not read, no logp is written.  row_mask (int32 per row, optional): a row whose flag is 0 gets `fill` in both outputs;
+// a tile of rows whose flags are all 0 leaves before its first weight request.  raw (optional): y itself (the discriminator's logit statistics).
+enum { HEAD_VALUE = 0, HEAD_STYLE = 1 };
+struct ScalarHead {
+    int kind;
+    float lo, hi, val_fail, val_succ;
+    float scale, lerp, fill;
+    const int32_t* terminate;      // M or null
+    const float* task_r;           // M or null
+    const int32_t* row_mask;       // M or null
+    float* raw;                    // M or null
+};
 struct PolicyIO {
     const float* states;   // M x S fp32 (RecordState of every env)
     uint16_t* s16;         // M x K1 bf16: normalised, clipped, zero-padded observations (written by k_policy_prep)
@@ -51,6 +67,11 @@ struct PolicyIO {
     const float *gsig1, *gbeta1;   // M x H2
     const GateDev* gate;           // device copy of the context's GateDev: k_policy_fused<.., true> reads the gate's first layers through it
 };
+// what a HEAD = 1 instantiation takes in PolicyIO's place (dm_policy_eval_scalar): the finished scalar goes to `actions` [M].  PolicyIO itself is what it was, so the
+// kernel arguments of every other kernel lie where they lay.
+struct ScalarIO : PolicyIO { ScalarHead sh; };
+template <int HEAD> struct HeadIO { typedef PolicyIO type; };
+template <> struct HeadIO<1> { typedef ScalarIO type; };
 
 // The gate of learning/nets/fc_2layers_gated_1024units.py: a small net on the NORMALISED GOAL (the last G input columns, input_tfs[-1]) that scales and
 // shifts the pre-activations of both hidden layers,
@@ -150,6 +171,36 @@ DMP_DEV float philox_normal(uint32_t env, uint32_t ctr, uint32_t seed_lo, uint32
     uint32_t r[4]; philox4x32_10(ctr, 0, 0, 0, seed_lo + env, seed_hi, r);
     const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.0f / 16777216.0f), u2 = ((float)(r[1] >> 8) + 0.5f) * (1.0f / 16777216.0f);
     return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// The scalar head's epilogue for one row < M (ScalarHead above).  Every multiply-add that may be contracted is an explicit fmaf and no other product feeds a sum, so
+// device and emulator round at the same points: d (one rounding), d / 4 (exact), fmaf, the product with scale, 1 - lerp, its product with r, fmaf.  A NaN y gives
+// lo (fmaxf returns its other operand) / a style reward of 0.
+DMP_DEV void scalar_head_store(const ScalarIO& io, int row, float y) {
+    const ScalarHead& h = io.sh;
+    float out = h.fill, raw = h.fill;
+    if (!h.row_mask || h.row_mask[row] != 0) {
+        raw = y;
+        if (h.kind == HEAD_VALUE) {
+            out = fminf(fmaxf(y, h.lo), h.hi);
+            if (h.terminate) { const int tm = h.terminate[row]; if (tm == 1) out = h.val_fail; else if (tm == 2) out = h.val_succ; }
+        } else {
+            const float d = 1.0f - y;
+            out = fmaxf(fmaf(-0.25f * d, d, 1.0f), 0.0f) * h.scale;
+            if (h.task_r) out = fmaf(h.lerp, h.task_r[row], (1.0f - h.lerp) * out);
+        }
+    }
+    io.actions[row] = out;
+    if (h.raw) h.raw[row] = raw;
+}
+// row_mask of the `rows` rows from row0 on: 0 if every flag is 0 (the addresses are uniform over the workgroup and clamped: scalar loads, one latency); fills the tile then
+DMP_DEV bool scalar_head_tile_masked(const ScalarIO& io, int row0, int rows, int t) {
+    if (!io.sh.row_mask) return false;
+    int any = 0;
+    for (int m = 0; m < rows; ++m) { const int row = row0 + m; any |= io.sh.row_mask[row < io.M ? row : io.M - 1]; }
+    if (any) return false;
+    if (t < rows && row0 + t < io.M) { io.actions[row0 + t] = io.sh.fill; if (io.sh.raw) io.sh.raw[row0 + t] = io.sh.fill; }
+    return true;
 }
 
 // observation normaliser (learning/normalizer.py:95-98) fused with the bf16 conversion and the zero padding of K to a multiple of 32:
@@ -260,9 +311,11 @@ __global__ void __launch_bounds__(256) k_policy_gate(PolicyDev p, PolicyIO io, G
 // The k loop is software-pipelined by hand: the A / B fragments of step ks + 1 are requested before the MFMAs of step ks issue
 // (two register sets), so one wave keeps its matrix core busy while the next 16-byte-per-lane reads are in flight.
 // GATED (MODE 0 / 1): the epilogue reads sigma / beta of its elements from the scratch k_policy_gate filled: relu(fmaf(sigma, acc + b, beta)).
-template <int MODE, int MT, int NT, bool GATED = false>
-__global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
+// HEAD = 1 (MODE 2, NT = 1): the scalar head (ScalarHead) -- column tile 0 only, no noise, no logp; a 16 MT-row tile that row_mask switches off leaves at once.
+template <int MODE, int MT, int NT, bool GATED = false, int HEAD = 0>
+__global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, typename HeadIO<HEAD>::type io) {
     const int l = threadIdx.x, c = l & 15, g = l >> 4;
+    if constexpr (HEAD != 0) { if (scalar_head_tile_masked(io, (int)blockIdx.x * 16 * MT, 16 * MT, l)) return; }
     const int K = (MODE == 0) ? p.K1 : (MODE == 1 ? p.H1 : p.H2);
     const int N = (MODE == 0) ? p.H1 : (MODE == 1 ? p.H2 : p.N3);
     const int n_col_tiles = N / (16 * NT);
@@ -272,7 +325,7 @@ __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
     // component, so the column blocks are walked inside the workgroup (A = 36 / 58 need two blocks of 32) and logp is written once.
     const int cb_first = (MODE == 2) ? 0 : (int)blockIdx.x / row_blocks, rb = (MODE == 2) ? (int)blockIdx.x : (int)blockIdx.x % row_blocks;
     if (cb_first >= n_col_tiles || rb >= row_blocks) return;
-    const int cb_last = (MODE == 2) ? n_col_tiles : cb_first + 1;
+    const int cb_last = (MODE == 2 && HEAD == 0) ? n_col_tiles : cb_first + 1;
     const int row0 = rb * 16 * MT, KS = K / 32;
     const uint16_t* wp = (MODE == 0) ? p.w1p : (MODE == 1 ? p.w2p : p.w3p);
     const uint16_t* ain = (MODE == 0) ? io.s16 : (MODE == 1 ? io.h1 : io.h2);
@@ -347,6 +400,16 @@ __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
                     else if (row < io.M) out[(size_t)row * N + col] = f32_to_bf16(fmaxf(acc[i][j][r] + bc, 0.0f));
                 }
         }
+    } else if constexpr (HEAD != 0) {
+        // scalar head: column 0 of the tile is on the lanes c = 0, rows 4 g + r
+        const float b30 = p.b3[0];
+#pragma unroll
+        for (int i = 0; i < MT; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + 16 * i + 4 * g + r;
+                if (c == 0 && row < io.M) scalar_head_store(io, row, acc[i][0][r] + b30);
+            }
     } else {
         // Gaussian head: norm_a = mean + exp(logstd) z, a = norm_a * a_std + a_mean, logp = sum_j (-z^2/2 - logstd_j) - A/2 log 2 pi
 #pragma unroll
@@ -375,7 +438,7 @@ __global__ void __launch_bounds__(64) k_policy_layer(PolicyDev p, PolicyIO io) {
     }
     }   // column blocks
 
-    if (MODE == 2) {
+    if (MODE == 2 && HEAD == 0) {
 #pragma unroll
         for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -504,8 +567,14 @@ __global__ void __launch_bounds__(256) k_policy_gemm(PolicyDev p, PolicyIO io) {
 // 4 feature tiles x {sigma k-steps 0 1, beta k-steps 0 1, scale biases, bias-projection biases}, behind the last chunk 6 blocks for the 8 layer-2 tiles; a tile's sigma and
 // beta are formed in the epilogue that already holds its accumulators (gated_tile_store), 8 MFMAs per feature tile.  Block t + 2 is still requested when block t is entered,
 // and a block is entered once the block before it is used up (a tile's six slots may straddle two blocks).  The plain instantiations are untouched by the switch.
-template <int KS1, int N3T, bool GATED = false>
-__global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO io) {
+//
+// HEAD = 1 (dm_policy_eval_scalar, action_dim = 1): the scalar head (ScalarHead) in place of the Gaussian one.  A tile that row_mask switches off leaves before the first
+// weight request; no Philox draw; layer 3 is ONE 16-column tile (N3T = 1) on the two waves that own it (waves 2 and 3 are done behind the barrier that completes h2), its column 0
+// goes through scalar_head_store.  Layers 1 and 2, the stream and the ring are the code above, so y is bit for bit the mode action of an actor with A = 1.  HEAD = 0 is
+// untouched by the switch.
+template <int KS1, int N3T, bool GATED = false, int HEAD = 0>
+__global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, typename HeadIO<HEAD>::type io) {
+    static_assert(HEAD == 0 || N3T == 1, "the scalar head multiplies one column tile of layer 3");
     constexpr int NGB1 = GATED ? 3 : 0, NGB2 = GATED ? 6 : 0;
     constexpr int R = 32, NQ = 4, NB1 = KS1 / 2, NB2 = 8, NBQ = NB1 + NGB1 + NB2, NBLK = NQ * NBQ + NGB2;
     constexpr int LDS_S16 = KS1 * 2 * 64, LDS_H1C = 8 * 2 * 64, LDS_H2 = 16 * 2 * 64;            // in 16-byte records
@@ -524,6 +593,7 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
 #define DMF_STAMP(i_) {}
 #endif
     DMF_STAMP(0)
+    if constexpr (HEAD != 0) { if (scalar_head_tile_masked(io, row0, R, t)) return; }
     const uint16_t* const ws = p.wfs + ((size_t)w * NBLK * 8 * 64 + l) * 8;      // this wave's stream; fragment f of block b at ws + (b * 8 + f) * 512
     bf16x8 ring[3][8];
 #define DMF_LOAD(slot_, blk_)                                                                                              \
@@ -554,7 +624,7 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
     // the head's noise does not depend on the net: drawn now, while the weight and observation requests are in flight (4 Philox + Box-Muller per owned action tile and lane)
     constexpr int NT3W = (N3T + 1) / 2;
     float hz[NT3W][4]; bool explore;
-    {
+    if constexpr (HEAD == 0) {
         const int row = row0 + 16 * (w & 1) + c;
         explore = io.sample && row < io.M;
         if (explore && io.exp_rate < 1.0f) explore = philox_coin((uint32_t)(io.env_off + row), io.step, io.seed_lo, io.seed_hi) < io.exp_rate;
@@ -700,7 +770,17 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
 #undef DMF_GF
 #undef DMF_LOAD
     // the first action tile's 16 weight fragments of layer 3 are requested now (the ring is dead): they arrive during the epilogue and the barrier
-    {
+    float hb3 = 0.0f;
+    if constexpr (HEAD != 0) {
+        // scalar head: tile 0 only, for the two waves that multiply it; of the constants b3[0] alone (a scalar load: not behind the vector requests)
+        if (w < 2) {
+            DMP_SCHED_FENCE();
+#pragma unroll
+            for (int ks = 0; ks < KS3; ++ks) wf[ks] = *reinterpret_cast<const bf16x8*>(p.w3p + ((size_t)ks * 64 + l) * 8);
+            DMP_SCHED_FENCE();
+        }
+        hb3 = p.b3[0];
+    } else {
         const int ntc0 = (w >> 1) < N3T ? (w >> 1) : N3T - 1;
         DMP_SCHED_FENCE();
 #pragma unroll
@@ -708,6 +788,7 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
         DMP_SCHED_FENCE();
     }
     // ... and so are the head's per-column constants of every tile this wave owns (branch-free, clamped: one latency for all of them)
+    if constexpr (HEAD == 0) {
 #pragma unroll
     for (int it = 0; it < NT3W; ++it)
 #pragma unroll
@@ -715,6 +796,7 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
             const int col = 16 * ((w >> 1) + 2 * it) + 4 * g + r, cc = col < p.A ? col : p.A - 1;
             hc_ls[it][r] = p.logstd[cc]; hc_b3[it][r] = p.b3[cc]; hc_as[it][r] = p.a_std[cc]; hc_am[it][r] = p.a_mean[cc];
         }
+    }
     DMP_SCHED_FENCE();
     // layer-2 epilogue -> h2 (B-fragment order of layer 3: k = 128 w + 16 n + 4 g + r).  Every wave is past the barrier of the last chunk, so s16 and
     // h1c[0], which h2 overlays, are dead; h1c[1] (still being read by slower waves) lies behind them.
@@ -733,8 +815,18 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, PolicyIO i
     }
     __syncthreads();
     DMF_STAMP(4)
-    // layer 3 + Gaussian head: wave w owns batch tile w & 1 and the action tiles (w >> 1), (w >> 1) + 2, ...; K = 512
-    {
+    if constexpr (HEAD != 0) {
+        // layer 3 + scalar head: waves 0 and 1 own batch tiles 0 and 1 of column tile 0; the lanes g = 0 hold column 0 (features 4 g + r) of batch row c
+        if (w >= 2) return;
+        const int row = row0 + 16 * w + c;
+        f32x4 acc;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[r] = 0.0f;
+#pragma unroll
+        for (int ks = 0; ks < KS3; ++ks) acc = mfma16(wf[ks], h2[(ks * 2 + w) * 64 + l], acc);
+        if (g == 0 && row < io.M) scalar_head_store(io, row, acc[0] + hb3);
+    } else {
+        // layer 3 + Gaussian head: wave w owns batch tile w & 1 and the action tiles (w >> 1), (w >> 1) + 2, ...; K = 512
         const int bt = w & 1, row = row0 + 16 * bt + c;
         float lp = 0.0f;
 #pragma unroll

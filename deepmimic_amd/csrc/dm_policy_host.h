@@ -5,6 +5,7 @@
 struct dm_policy {
     dmp::PolicyDev pd; int device_id = 0; int cap = 0;
     int last_path = DM_POLICY_PATH_NONE, last_rows = 0;      // dm_policy_info: the kernels of the last dm_policy_forward(_ex)
+    int scalar_path = DM_POLICY_PATH_NONE, scalar_rows = 0, scalar_kind = 0, scalar_masked = 0;      // dm_policy_scalar_info: the last dm_policy_eval_scalar
     uint16_t *h1 = nullptr, *h2 = nullptr, *s16 = nullptr;
     bool gated = false; dmp::GateDev gd; const dmp::GateDev* gd_dev = nullptr;   // dm_policy_create_gated: the gate's packed weights (gd_dev: the copy the fused kernel reads)
     float* gbuf[4] = {nullptr, nullptr, nullptr, nullptr};   // sigma_0, beta_0 [cap x H1], sigma_1, beta_1 [cap x H2] fp32, grown with h1 / h2
@@ -91,6 +92,12 @@ static void launch_fused(int path, unsigned grid, rt_stream stream, const dmp::P
     case DM_POLICY_PATH_FUSED_12_2: RT_LAUNCH4((dmp::k_policy_fused<12, 2, GATED>), grid, stream, d, io); break;
     default: RT_LAUNCH4((dmp::k_policy_fused<12, 4, GATED>), grid, stream, d, io); break;
     }
+}
+// the scalar head's one-launch kernels: action_dim = 1, so N3 = 32 and the id is one of the two K1 choices
+template <bool GATED>
+static void launch_fused_scalar(int path, unsigned grid, rt_stream stream, const dmp::PolicyDev& d, const dmp::ScalarIO& io) {
+    if (path == DM_POLICY_PATH_FUSED_8_2) RT_LAUNCH4((dmp::k_policy_fused<8, 1, GATED, 1>), grid, stream, d, io);
+    else RT_LAUNCH4((dmp::k_policy_fused<12, 1, GATED, 1>), grid, stream, d, io);
 }
 // layers 1 and 2; tiles sized so that every launch has at least ~1 wave per SIMD at 4096 rows: 64 x 64 (layer 1), 32 x 64 (layer 2)
 template <bool GATED>
@@ -215,6 +222,8 @@ static int policy_create(int device_id, const dm_policy_params* pp, const dm_pol
     return 0;
 }
 
+static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_stream);
+
 extern "C" {
 
 int dm_policy_create(int device_id, const dm_policy_params* pp, dm_policy** out) { return policy_create(device_id, pp, nullptr, out); }
@@ -241,6 +250,19 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
     if (p->gated && goal_dim != 0 && goal_dim != p->gd.G) return fail("dm_policy_forward_ex: a gated actor takes its goal as a block of the gate's goal_dim columns, or goal_dim = 0 with the goal in the last columns of states_dev");
     if (!(exp_rate >= 0.0 && exp_rate <= 1.0)) return fail("dm_policy_forward_ex: exp_rate must be in [0, 1]");
     if (n <= 0) return 0;
+    dmp::ScalarIO io; memset(&io, 0, sizeof(io));
+    io.states = states_dev; io.actions = actions_dev; io.logp = logp_dev; io.M = n; io.sample = sample ? 1 : 0;
+    io.seed_lo = (uint32_t)seed; io.seed_hi = (uint32_t)(seed >> 32); io.step = step; io.env_off = env_id_offset;
+    io.goals = goal_dim ? goals_dev : nullptr; io.G = goal_dim; io.exp_rate = (float)exp_rate; io.exp_flags = exp_flags_dev;
+    return policy_run(p, io, false, hip_stream);
+}
+
+}  // extern "C"
+
+// What dm_policy_forward_ex and dm_policy_eval_scalar share: the activation buffers grown to io.M rows, the kernel choice (policy_path) and the launches.  `io` carries the
+// call's own members (inputs, outputs, noise or head); scalar: the HEAD = 1 instantiation of the kernel that holds layer 3, everything in front of it as for the actor.
+static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_stream) {
+    const int n = io.M;
     DevGuard guard(p->device_id);
     rt_stream stream = (rt_stream)hip_stream;
     if (n > p->cap) {                       // hidden activations: n x (H1 + H2) bf16, grown on demand
@@ -256,22 +278,25 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
         }
         p->h1 = (uint16_t*)a; p->h2 = (uint16_t*)b; p->s16 = (uint16_t*)c; p->cap = n;
     }
-    dmp::PolicyIO io; memset(&io, 0, sizeof(io));
-    io.states = states_dev; io.s16 = p->s16; io.h1 = p->h1; io.h2 = p->h2; io.actions = actions_dev; io.logp = logp_dev; io.M = n; io.sample = sample ? 1 : 0;
-    io.seed_lo = (uint32_t)seed; io.seed_hi = (uint32_t)(seed >> 32); io.step = step; io.env_off = env_id_offset;
-    if (const char* pr = getenv("DM_POLICY_PROBE")) io.probe = atoi(pr);
-    io.goals = goal_dim ? goals_dev : nullptr; io.G = goal_dim; io.exp_rate = (float)exp_rate; io.exp_flags = exp_flags_dev;
+    io.s16 = p->s16; io.h1 = p->h1; io.h2 = p->h2;
+    if (!scalar) if (const char* pr = getenv("DM_POLICY_PROBE")) io.probe = atoi(pr);
     io.gsig0 = p->gbuf[0]; io.gbeta0 = p->gbuf[1]; io.gsig1 = p->gbuf[2]; io.gbeta1 = p->gbuf[3]; io.gate = p->gd_dev;
     const dmp::PolicyDev& d = p->pd;
     const int path = policy_path(d);
-    p->last_path = path; p->last_rows = n;
+    const dmp::PolicyIO& pio = io;          // what every kernel but the HEAD = 1 ones takes
+    if (scalar) { p->scalar_path = path; p->scalar_rows = n; p->scalar_kind = io.sh.kind; p->scalar_masked = io.sh.row_mask ? 1 : 0; }
+    else { p->last_path = path; p->last_rows = n; }
     if (path < DM_POLICY_PATH_LAYERED_BASE) {
         const unsigned grid = (unsigned)((n + 31) / 32);
+        if (scalar) {
+            if (p->gated) launch_fused_scalar<true>(path, grid, stream, d, io); else launch_fused_scalar<false>(path, grid, stream, d, io);
+            return launch_status(0);
+        }
 #ifndef DM_EMU
         static unsigned long long* prof_buf = nullptr; static int prof_calls = 0;
         if (io.probe == 2) { if (!prof_buf && hipMalloc((void**)&prof_buf, (size_t)8192 * 8 * 8) != hipSuccess) prof_buf = nullptr; io.prof = grid <= 8192 ? prof_buf : nullptr; }
 #endif
-        if (p->gated) launch_fused<true>(path, grid, stream, d, io); else launch_fused<false>(path, grid, stream, d, io);
+        if (p->gated) launch_fused<true>(path, grid, stream, d, pio); else launch_fused<false>(path, grid, stream, d, pio);
 #ifndef DM_EMU
         hipError_t le0 = hipGetLastError(); if (le0 != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le0));
         if (io.prof && ++prof_calls == 100) {          // DM_POLICY_PROBE=2: phase times of the 100th launch (100 MHz constant clock -> ns), mean over the workgroups
@@ -286,16 +311,41 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
         return 0;
     }
     // tiles sized so that every launch has at least ~1 wave per SIMD at 4096 rows: 64 x 64 (layer 1), 32 x 64 (layer 2), 16 x 32 (layer 3)
-    RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
+    RT_LAUNCH(dmp::k_policy_prep, n, stream, d, pio);
     if (p->gated) {
         // the launch is (path id, gated): the same kernel choice per layer, its GATED instantiation, behind k_policy_gate (32 rows per workgroup)
-        RT_LAUNCH4(dmp::k_policy_gate, (n + 31) / 32, stream, d, io, p->gd);
-        launch_layers<true>(path, n, stream, d, io);
-    } else launch_layers<false>(path, n, stream, d, io);
-    RT_LAUNCH((dmp::k_policy_layer<2, 1, 2>), (n + 15) / 16, stream, d, io);   // one workgroup per 16 rows owns all N3 columns (logp is a row sum)
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
+        RT_LAUNCH4(dmp::k_policy_gate, (n + 31) / 32, stream, d, pio, p->gd);
+        launch_layers<true>(path, n, stream, d, pio);
+    } else launch_layers<false>(path, n, stream, d, pio);
+    if (scalar) { RT_LAUNCH((dmp::k_policy_layer<2, 1, 1, false, 1>), (n + 15) / 16, stream, d, io); }   // the scalar head: column tile 0 alone
+    else { RT_LAUNCH((dmp::k_policy_layer<2, 1, 2>), (n + 15) / 16, stream, d, pio); }   // one workgroup per 16 rows owns all N3 columns (logp is a row sum)
+    return launch_status(0);
+}
+
+extern "C" {
+
+int dm_policy_eval_scalar(dm_policy* p, const float* states_dev, const float* goals_dev, int goal_dim, int n, const dm_scalar_head* head, float* out_dev,
+                          float* raw_out_dev, void* hip_stream) {
+    if (!p || !states_dev || !head || !out_dev) return fail("null argument");
+    if (p->pd.A != 1) return fail("dm_policy_eval_scalar: the context has action_dim " + std::to_string(p->pd.A) + ", a scalar head needs a net with one output (create it with action_dim = 1)");
+    if (goal_dim < 0 || goal_dim >= p->pd.S || (goal_dim > 0 && !goals_dev)) return fail("dm_policy_eval_scalar: goal_dim must be in [0, state_dim) with a goal block when positive (state_dim counts the goal columns)");
+    if (p->gated && goal_dim != 0 && goal_dim != p->gd.G) return fail("dm_policy_eval_scalar: a gated net takes its goal as a block of the gate's goal_dim columns, or goal_dim = 0 with the goal in the last columns of states_dev");
+    if (head->kind != DM_SCALAR_HEAD_VALUE && head->kind != DM_SCALAR_HEAD_STYLE) return fail("dm_policy_eval_scalar: head kind must be DM_SCALAR_HEAD_VALUE or DM_SCALAR_HEAD_STYLE");
+    if (head->kind == DM_SCALAR_HEAD_VALUE && !(head->lo <= head->hi)) return fail("dm_policy_eval_scalar: value head needs lo <= hi (infinite bounds: no clipping)");
+    if (head->kind == DM_SCALAR_HEAD_STYLE && head->task_reward_dev && !(head->lerp >= 0.0f && head->lerp <= 1.0f)) return fail("dm_policy_eval_scalar: lerp must be in [0, 1]");
+    if (n <= 0) return 0;
+    dmp::ScalarIO io; memset(&io, 0, sizeof(io));
+    io.states = states_dev; io.actions = out_dev; io.M = n; io.goals = goal_dim ? goals_dev : nullptr; io.G = goal_dim; io.exp_rate = 1.0f;
+    dmp::ScalarHead& h = io.sh;
+    h.kind = head->kind == DM_SCALAR_HEAD_STYLE ? dmp::HEAD_STYLE : dmp::HEAD_VALUE;
+    h.lo = head->lo; h.hi = head->hi; h.val_fail = head->val_fail; h.val_succ = head->val_succ; h.scale = head->scale; h.lerp = head->lerp; h.fill = head->fill;
+    h.terminate = head->terminate_dev; h.task_r = head->task_reward_dev; h.row_mask = head->row_mask_dev; h.raw = raw_out_dev;
+    return policy_run(p, io, true, hip_stream);
+}
+
+int dm_policy_scalar_info(dm_policy* p, int32_t* out) {
+    if (!p || !out) return fail("null argument");
+    out[0] = p->scalar_path; out[1] = p->scalar_rows; out[2] = p->scalar_kind; out[3] = p->scalar_masked;
     return 0;
 }
 

@@ -62,3 +62,20 @@ def td_lambda_returns_torch(rewards, values, term_values, terminate, done, valid
                       valid.data_ptr() if valid is not None else 0, gamma, td_lambda, val_fail, val_succ, returns.data_ptr(), mask.data_ptr(),
                       stream=int(torch.cuda.current_stream(dev).cuda_stream), device_id=dev.index or 0, lib_path=lib_path)
     return returns, mask
+
+
+def critic_returns_torch(critic, obs, goals, terminal_obs, terminal_goal, terminate, done, valid, rewards, gamma: float, td_lambda: float,
+                         lib_path: Optional[str] = None):
+    """TD(lambda) targets of a stacked rollout straight from a `deepmimic_amd.heads.Critic`: obs [T + 1, N, S] (row T: the observation after the last step),
+    goals [T + 1, N, G] or None, terminal_obs [T, N, S] / terminal_goal [T, N, G] (info["terminal_obs"] / info["terminal_goal"] of every step), the flags and
+    rewards [T, N].  Two critic launches -- values on obs, and term_values on terminal_obs under row_mask = done, so tiles without a finished episode cost
+    nothing -- then dm_td_lambda_returns with the critic's val_fail / val_succ.  The Fail / Succ override is td_lambda_returns' own rule, so the values stay
+    the net's (clipped) output.  Returns (returns [T, N] float32, mask [T, N] int32); all on torch's current stream."""
+    import torch
+    T = int(rewards.shape[0])
+    if int(obs.shape[0]) != T + 1:
+        raise ValueError("obs must be [T + 1, N, S] for rewards [T, N]")
+    done_i = done.to(torch.int32) if done.dtype == torch.bool else done
+    values = critic.eval_torch(obs, goals)
+    term_values = critic.eval_torch(terminal_obs, terminal_goal, row_mask=done_i, fill=0.0)
+    return td_lambda_returns_torch(rewards, values, term_values, terminate, done_i, valid, gamma, td_lambda, critic.val_fail, critic.val_succ, lib_path=lib_path)

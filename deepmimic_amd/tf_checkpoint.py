@@ -260,3 +260,63 @@ def _actor_weights(idx, prefix, scope, state_dim, verify_below, extra) -> dict:
     if w["w1"].shape[0] != S + G or w["w2"].shape[0] != w["w1"].shape[1] or w["w3"].shape[0] != w["w2"].shape[1] or w["logstd"].size != w["w3"].shape[1]:
         raise ValueError("%s: layer shapes %s %s %s do not chain from %d + %d inputs" % (prefix, w["w1"].shape, w["w2"].shape, w["w3"].shape, S, G))
     return w
+
+
+def _mlp_weights(idx, prefix, base, out_layer, norms, verify_below, extra) -> dict:
+    """a two-layer net with a linear output under `base` (0/dense, 1/dense, <out_layer>) plus the normalisers `norms` ((resource group, key prefix), ...)"""
+    need = [base + "0/dense/kernel", base + "0/dense/bias", base + "1/dense/kernel", base + "1/dense/bias", base + out_layer + "/kernel", base + out_layer + "/bias"]
+    missing = [n for n in need + list(extra.values()) if n not in idx]
+    if missing:
+        raise ValueError("%s: no %s" % (prefix, missing[0]))
+    scope = base.split("/main/")[0]
+    nn = [scope + "/resource/%s/%s" % (g, k) for g, _ in norms for k in ("mean", "std")]
+    t = read_tensors(prefix, names=set(need + list(extra.values()) + [n for n in nn if n in idx]), verify_below=verify_below)
+    w = dict(w1=t[need[0]], b1=t[need[1]], w2=t[need[2]], b2=t[need[3]], w3=t[need[4]], b3=t[need[5]])
+    for k, n in extra.items():
+        w[k] = t[n]
+    for g, key in norms:
+        for k in ("mean", "std"):
+            n = scope + "/resource/%s/%s" % (g, k)
+            if n in t and t[n].size:
+                w["%s_%s" % (key, k)] = t[n].reshape(-1)
+    if w["w2"].shape[0] != w["w1"].shape[1] or w["w3"].shape != (w["w2"].shape[1], 1) or w["b3"].shape != (1,):
+        raise ValueError("%s: layer shapes %s %s %s under %s do not chain to one output" % (prefix, w["w1"].shape, w["w2"].shape, w["w3"].shape, base))
+    return w
+
+
+def is_gated_critic(prefix: str, scope: str = "agent") -> bool:
+    return any(n.startswith(scope + "/main/critic/gate") for n in read_index(prefix + ".index"))
+
+
+def critic_weights(prefix: str, scope: str = "agent", state_dim: Optional[int] = None, verify_below: int = 1 << 16) -> dict:
+    """The critic of a reference checkpoint (<scope>/main/critic/{0,1}/dense and the one-unit `dense`, learning/pg_agent.py:161-171) as the weights dict of
+    `deepmimic_amd.heads.Critic`: w1 b1 w2 b2 w3 [H2, 1] b3 [1], s_mean s_std (+ g_mean g_std with a goal: the net reads [norm_s, norm_g]); with
+    <scope>/main/critic/gate* variables ("CriticNet": "fc_2layers_gated_1024units", the AMP task agents) also the gate arrays (policy.GATE_KEYS) and goal_dim."""
+    idx = read_index(prefix + ".index")
+    c = scope + "/main/critic/"
+    extra = {}
+    if is_gated_critic(prefix, scope):
+        for key, var in GATE_VARIABLES.items():
+            extra[key + "_w"] = c + var + "/kernel"; extra[key + "_b"] = c + var + "/bias"
+    w = _mlp_weights(idx, prefix, c, "dense", (("s_norm", "s"), ("g_norm", "g")), verify_below, extra)
+    S = w["s_mean"].size if "s_mean" in w else w["w1"].shape[0]
+    G = w["g_mean"].size if "g_mean" in w else 0
+    if state_dim is not None and S != state_dim:
+        raise ValueError("%s was trained on %d state features, the scene records %d" % (prefix, S, state_dim))
+    if w["w1"].shape[0] != S + G:
+        raise ValueError("%s: the critic takes %d inputs, s_norm + g_norm have %d + %d" % (prefix, w["w1"].shape[0], S, G))
+    if extra:
+        if G < 1 or w["gc_w"].shape[0] != G:
+            raise ValueError("%s: the critic's gate takes %d inputs, g_norm has %d" % (prefix, w["gc_w"].shape[0], G))
+        w["goal_dim"] = G
+    return w
+
+
+def disc_weights(prefix: str, scope: str = "agent", verify_below: int = 1 << 16) -> dict:
+    """The AMP discriminator of a reference checkpoint (<scope>/main/disc/{0,1}/dense and `disc_logits`, learning/amp_agent.py:178-194) as the weights dict of
+    `deepmimic_amd.heads.Discriminator`, with <scope>/resource/amp_obs_norm as its input normaliser (s_mean, s_std)."""
+    idx = read_index(prefix + ".index")
+    w = _mlp_weights(idx, prefix, scope + "/main/disc/", "disc_logits", (("amp_obs_norm", "s"),), verify_below, {})
+    if "s_mean" in w and w["s_mean"].size != w["w1"].shape[0]:
+        raise ValueError("%s: the discriminator takes %d inputs, amp_obs_norm has %d" % (prefix, w["w1"].shape[0], w["s_mean"].size))
+    return w

@@ -489,6 +489,42 @@ enum dm_policy_packed {
 };
 int dm_policy_read_packed(dm_policy* policy, int which, void* host_out, size_t capacity, size_t* bytes);
 
+/* ---- Scalar heads of the device nets: the critic (learning/pg_agent.py:161-171: the actor's two-layer net with a one-unit linear output on [norm_s, norm_g];
+ * gated in the AMP task agents) and the AMP discriminator (learning/amp_agent.py:178-194: fc_2layers_1024units on amp_obs_norm-normalised observations, output
+ * disc_logits).  A scalar context IS a policy context with action_dim = 1: dm_policy_create / dm_policy_create_gated (a_mean, a_std, logstd may be NULL),
+ * dm_policy_set_weights, dm_policy_bind_obs_normalizer, dm_policy_read_packed and dm_policy_destroy work on it.  dm_policy_eval_scalar takes n observation rows
+ * (states_dev / goals_dev / goal_dim as dm_policy_forward_ex) to the finished per-row scalar in out_dev[n] in ONE launch where the one-launch kernel is compiled
+ * for the widths (else the per-layer kernels with the head in the last): no noise is drawn, logstd / a_mean / a_std are not read, nothing like logp is written.
+ * With y = the net's output (bf16 operands, fp32 accumulation: bit for bit the mode action of an actor built from the same arrays):
+ *   DM_SCALAR_HEAD_VALUE   v = min(max(y, lo), hi) -- the AMP agent's value clip (amp_agent.py:441-443), infinite bounds give PPO's behaviour; a NaN y gives lo --
+ *                          then, with terminate_dev (int32 per row, eTerminate), v = val_fail where it is 1 (Fail) and val_succ where it is 2 (Succ)
+ *                          (ppo_agent.py:262-264);
+ *   DM_SCALAR_HEAD_STYLE   d = 1 - y, r = scale * max(0, 1 - 0.25 d^2) (amp_agent.py:393-434), then, with task_reward_dev (float per row),
+ *                          r = (1 - lerp) r + lerp task_r (amp_agent.py:294-297), lerp in [0, 1]; fp32, every multiply-add one fma.
+ * row_mask_dev (int32 per row, optional): a row whose flag is 0 gets `fill` in out_dev and raw_out_dev.  In the one-launch kernel a whole 32-row tile of such
+ * rows leaves before its first weight request, so it costs a launch slot and 32 flag reads -- critic values on terminal observations are read only where the
+ * step was done.  LIMIT: on the per-layer route (widths without a one-launch kernel, or DM_POLICY_LAYERED=1) only the last launch, the layer-3 head kernel,
+ * honours the mask (16-row tiles); k_policy_prep, k_policy_gate and layers 1 and 2 still run for every row, so masking saves next to nothing there.
+ * raw_out_dev (optional, n floats): y itself, for the discriminator's logit statistics.  Rows [0, n) of the outputs are always written, nothing else is.
+ * Asynchronous on hip_stream; no allocation beyond the activation buffers a context grows to its largest n.  Fails on a context whose action_dim is not 1. */
+enum { DM_SCALAR_HEAD_VALUE = 0, DM_SCALAR_HEAD_STYLE = 1 };
+typedef struct {
+    int kind;                           /* DM_SCALAR_HEAD_VALUE / DM_SCALAR_HEAD_STYLE */
+    float lo, hi;                       /* value: clip bounds (-inf / +inf: none) */
+    float val_fail, val_succ;           /* value: what a Fail / Succ row gets with terminate_dev */
+    const int32_t* terminate_dev;       /* value: n flags or NULL */
+    float scale, lerp;                  /* style: reward_scale, task_reward_lerp */
+    const float* task_reward_dev;       /* style: n task rewards or NULL (then lerp is not used) */
+    const int32_t* row_mask_dev;        /* n flags or NULL (every row) */
+    float fill;                         /* what a masked-out row gets */
+} dm_scalar_head;
+int dm_policy_eval_scalar(dm_policy* policy, const float* states_dev, const float* goals_dev, int goal_dim, int n, const dm_scalar_head* head,
+                          float* out_dev, float* raw_out_dev, void* hip_stream);
+/* the LAST dm_policy_eval_scalar on this context: out[0] = the dm_policy_path id that served it (the HEAD instantiation of the kernel that holds layer 3;
+ * DM_POLICY_PATH_NONE before any), out[1] = its row count, out[2] = its head kind, out[3] = 1 if it had a row mask.  dm_policy_info keeps reporting the last
+ * dm_policy_forward(_ex) only. */
+int dm_policy_scalar_info(dm_policy* policy, int32_t* out);
+
 /* ---- Running observation statistics on the device: the Normalizer of the reference's learner (learning/normalizer.py:6-152; the
  * s_norm / g_norm / amp_obs_norm of learning/rl_agent.py:466-483, amp_agent.py:290-291) for records that stay in HBM.
  * group_ids (NULL = one NORM_GROUP_SINGLE group): per column -1 = never updated (NORM_GROUP_NONE), 0 = per element, k > 0 = the
