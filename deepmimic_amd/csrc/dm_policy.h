@@ -80,14 +80,12 @@ template <> struct HeadIO<1> { typedef ScalarIO type; };
 // Rounding points (mirrored by deepmimic_amd/policy.py reference_forward(bf16=True)): xg, c, e_i are bf16 where they become MFMA operands (xg IS the goal block
 // of the bf16 observations the main net reads); sigma, beta, acc + b and the gated pre-activation fmaf(sigma, acc + b, beta) stay fp32 (one rounding, written as
 // fmaf so that device and emulator agree); h1, h2 are bf16 as in the plain actor, whose products, accumulation order and rounding points the main layers keep.
-// Packed weights as pack_weights lays them out (dm_policy_host.h); KG = G rounded up to 32, GC and GH multiples of 32.
+// Packed weights in the fragment order of k_policy_pack (PK_FRAG, below); KG = G rounded up to 32, GC and GH multiples of 32.
 struct GateDev {
     int G, KG, GC, GH;
     const uint16_t *wcp, *wep[2], *wbp[2], *wsp[2];     // gate_common/0/dense; gate{i}/0/dense, gate{i}/dense (beta), gate{i}/dense_1 (sigma pre-activation)
     const float *bc, *be[2], *bb[2], *bs[2];
 };
-
-static inline uint16_t f32_to_bf16_host(float f) { uint32_t u; memcpy(&u, &f, 4); if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0; u += 0x7fffu + ((u >> 16) & 1u); return (uint16_t)(u >> 16); }
 
 #ifdef DM_EMU
 #define DMP_SCHED_FENCE() ((void)0)
@@ -867,16 +865,29 @@ __global__ void __launch_bounds__(256, 2) k_policy_fused(PolicyDev p, typename H
 #undef DMF_STAMP
 }
 
-// ---------------------------------------------------------------- weight refresh on the device (dm_policy_set_weights)
-// ONE launch re-packs every array of a context from fp32 sources in device memory into the buffers the forward kernels read.  The kernel is
-// DESTINATION-ordered: a job is one destination array, a workgroup is 256 consecutive destination units of one job (PackArgs::first maps blockIdx to the
-// job), and a thread owns one unit -- a whole 16-byte fragment row [8 bf16] of a packed weight array or of the fused stream, or one fp32 element of a
-// vector.  The thread computes the source (k, n) of its row from the row's index (the inverse of pack_weights, composed with the inverse of
-// pack_fused_stream(_gated) for the fused stream, which is therefore written straight from the fp32 source and not copied from w1p / w2p), reads eight
-// fp32 ELEMENTS (sources are only 4-byte aligned: torch views) and writes one vector store.  Source layout by PackArgs::out_in: [in x out] row-major
-// (tf.layers.dense: the 16 lanes of a quarter-wave read 64 consecutive bytes per k) or [out x in] (torch.nn.Linear.weight: 32 consecutive bytes per
-// lane, 128 per column over the four quarter-waves).  Rounding: f32_to_bf16_host's, NaN case included.  A fused-stream row whose source array is not
-// given keeps its bytes (the host adds a job only for a source that is there).
+// ---------------------------------------------------------------- the packed weights: their layout and the kernel that writes it
+// (dm_policy_create(_gated) once with every source given, dm_policy_set_weights with whichever are; host side: policy_pack, dm_policy_host.h)
+// ONE launch packs every array of a context from fp32 sources in device memory into the buffers the forward kernels read; nothing else writes them, so the
+// layout is what this kernel does:
+//  * fragment order (PK_FRAG) of W [K x N] (tf.layers.dense kernel layout: input index first), zero-padded to Kp x Np: [n-tile][k-step][lane][8] bf16 -- row r
+//    of the array is lane l = r % 64 of fragment (nt, ks) = (r / 64 / KS, r / 64 % KS), KS = Kp / 32, and holds column n = 16 nt + (l & 15),
+//    k = 32 ks + 8 (l >> 4) + i, i = 0 .. 7 (pack_row).  A fragment is 1 KB: the operand of one mfma16, 16 bytes per lane.
+//  * fused stream (PK_FUSED; H1 = 1024, H2 = 512, gate_hidden = 64): 1 KB slots of one fragment each, 8 slots to a block, NBLK blocks per wave w = 0 .. 3 of
+//    k_policy_fused in the order the wave consumes them.  Per layer-1 chunk q = 0 .. 3: NB1 = K1 / 64 blocks, block b slot 4 kk + j = layer-1 fragment (feature
+//    tile 16 q + 4 w + j, k-step 2 b + kk); gated: 3 blocks = 24 slots = the gate tiles of layer 1's feature tiles 16 q + 4 w + j, j = 0 .. 3; then 8 blocks, block
+//    ksl slot n = layer-2 fragment (feature tile 8 w + n, k-step 8 q + ksl).  Gated: behind the last chunk 6 blocks = 48 slots = the gate tiles of layer 2's
+//    feature tiles 8 w + n, n = 0 .. 7.  A gate tile of feature tile ft is six slots in consumption order: the sigma fragments (gate{i}/dense_1, K = 64) of
+//    k-steps 0 and 1, the beta fragments (gate{i}/dense) of k-steps 0 and 1, then lane l's four sigma biases and its four beta biases as fp32 bits (features
+//    16 ft + 4 (l >> 4) + r: pack_bias_row).
+//  * vectors (PK_VEC) are fp32 as given, zero behind the N source elements (b3 up to N3); s_inv_std is 1 / s_std (PK_RECIP).
+//  * fp32 -> bf16: round to nearest even, every NaN -> 0x7fc0 (f32_to_bf16_nan).
+// The kernel is DESTINATION-ordered: a job is one destination array, a workgroup is 256 consecutive destination units of one job (PackArgs::first maps blockIdx
+// to the job), and a thread owns one unit -- a whole 16-byte fragment row [8 bf16] of a packed weight array or of the fused stream, or one fp32 element of a
+// vector.  The thread decodes its row's index as above (for the fused stream: wave, block, slot first, so the stream is written straight from the fp32 sources
+// and not copied from w1p / w2p), reads eight fp32 ELEMENTS (sources are only 4-byte aligned: torch views) and writes one vector store.  Source layout by
+// PackArgs::out_in: [in x out] row-major (tf.layers.dense: the 16 lanes of a quarter-wave read 64 consecutive bytes per k) or [out x in]
+// (torch.nn.Linear.weight: 32 consecutive bytes per lane, 128 per column over the four quarter-waves).  A fused-stream row whose source array is not given keeps
+// its bytes (the host adds a job only for a source that is there); with every source given every byte of every array is written.
 enum { PK_FRAG = 0, PK_FUSED = 1, PK_VEC = 2, PK_RECIP = 3, PK_MAX_JOBS = 28 };
 struct PackJob {
     int kind;
@@ -892,7 +903,7 @@ struct PackFused {         // sources of the fused stream (any may be null: thos
 };
 struct PackArgs { int njobs, out_in; int first[PK_MAX_JOBS + 1]; PackJob job[PK_MAX_JOBS]; PackFused fs; };
 
-// f32_to_bf16_host for device code: round to nearest even, every NaN -> 0x7fc0 (the device f32_to_bf16 above has no NaN case)
+// the rounding of the packed weights: to nearest even, every NaN -> 0x7fc0 (the device f32_to_bf16 above has no NaN case)
 DMP_DEV uint16_t f32_to_bf16_nan(float f) {
     uint32_t u = __builtin_bit_cast(uint32_t, f);
     if ((u & 0x7fffffffu) > 0x7f800000u) return 0x7fc0;
@@ -944,7 +955,7 @@ __global__ void __launch_bounds__(256) k_policy_pack(PackArgs a) {
         *dst = pack_row(a.job[j].src, a.job[j].K, a.job[j].N, a.out_in, f / KS, f % KS, l);
         return;
     }
-    // PK_FUSED: f = (w * NBLK + block) * 8 + slot, the inverse of pack_fused_stream / pack_fused_stream_gated (dm_policy_host.h)
+    // PK_FUSED: f = (w * NBLK + block) * 8 + slot; block = q * NBQ + bq inside the four chunks (NBQ blocks each), the layer-2 gate tiles behind them
     const PackFused& s = a.fs;
     const int NB1 = s.NB1, KS1 = 2 * NB1, NBQ = NB1 + (s.gated ? 11 : 8), NBLK = 4 * NBQ + (s.gated ? 6 : 0);
     const int w = f / (8 * NBLK), blk = (f >> 3) % NBLK, slot = f & 7;

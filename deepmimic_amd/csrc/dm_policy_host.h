@@ -1,5 +1,6 @@
-// Host side of the on-device policy (dm_policy.h): packs the fp32 weights of the reference's actor into bf16 MFMA fragments
-// and launches the three layer kernels.  Included at the end of dm_host.cpp (shares its runtime shim).
+// Host side of the on-device policy (dm_policy.h): allocates a context's packed arrays, has k_policy_pack fill them from the fp32 weights of the
+// reference's actor -- the same launch for a new context and for new weights into a live one (policy_pack); the layout is defined there, in dm_policy.h --
+// and launches the layer kernels.  Included at the end of dm_host.cpp (shares its runtime shim).
 #include "dm_policy.h"
 
 struct dm_policy {
@@ -12,76 +13,8 @@ struct dm_policy {
     std::vector<void*> allocs;
     void free_gbuf() { for (float*& b : gbuf) { if (b) rt_free(b); b = nullptr; } }
     ~dm_policy() { for (void* p : allocs) rt_free(p); if (h1) rt_free(h1); if (h2) rt_free(h2); if (s16) rt_free(s16); free_gbuf(); }
-    void* up(const void* host, size_t bytes) { void* d = nullptr; if (rt_malloc(&d, bytes)) return nullptr; allocs.push_back(d); if (rt_h2d(d, host, bytes, 0)) return nullptr; return d; }
+    void* alloc(size_t bytes) { void* d = nullptr; if (rt_malloc(&d, bytes)) return nullptr; allocs.push_back(d); return d; }      // freed with the context
 };
-
-// fragment order [n-tile][k-step][lane][8]: lane l <-> column 16 nt + (l & 15), k = 32 ks + 8 (l >> 4) + i; W is [K x N] row-major
-// (tf.layers.dense kernel layout: input index first)
-static std::vector<uint16_t> pack_weights(const float* W, int K, int N, int Kp, int Np) {
-    std::vector<uint16_t> out((size_t)Kp * Np, 0);
-    const int KS = Kp / 32;
-    for (int nt = 0; nt < Np / 16; ++nt) for (int ks = 0; ks < KS; ++ks) for (int l = 0; l < 64; ++l) for (int i = 0; i < 8; ++i) {
-        const int n = 16 * nt + (l & 15), k = 32 * ks + 8 * (l >> 4) + i;
-        out[(((size_t)nt * KS + ks) * 64 + l) * 8 + i] = (k < K && n < N) ? dmp::f32_to_bf16_host(W[(size_t)k * N + n]) : (uint16_t)0;
-    }
-    return out;
-}
-
-// the weight stream of k_policy_fused (dm_policy.h): per wave w, per layer-1 chunk q: K1 / 64 blocks {2 k-steps x feature tiles 16 q + 4 w + j}, then 8 blocks
-// {k-step 8 q + ksl of layer 2 x feature tiles 8 w + n}; a block is 8 fragments of [lane][8] bf16 (1 KB each), fragments as pack_weights lays them out
-static std::vector<uint16_t> pack_fused_stream(const std::vector<uint16_t>& w1p, const std::vector<uint16_t>& w2p, int K1) {
-    const int KS1 = K1 / 32, NB1 = KS1 / 2, NBQ = NB1 + 8, NBLK = 4 * NBQ, KS2 = 1024 / 32;
-    std::vector<uint16_t> out((size_t)4 * NBLK * 8 * 512, 0);
-    for (int w = 0; w < 4; ++w) for (int q = 0; q < 4; ++q) {
-        for (int b1 = 0; b1 < NB1; ++b1) for (int kk = 0; kk < 2; ++kk) for (int j = 0; j < 4; ++j) {
-            const size_t dst = (((size_t)w * NBLK + q * NBQ + b1) * 8 + kk * 4 + j) * 512;
-            const size_t src = ((size_t)(16 * q + 4 * w + j) * KS1 + 2 * b1 + kk) * 512;
-            std::copy(w1p.begin() + src, w1p.begin() + src + 512, out.begin() + dst);
-        }
-        for (int ksl = 0; ksl < 8; ++ksl) for (int n = 0; n < 8; ++n) {
-            const size_t dst = (((size_t)w * NBLK + q * NBQ + NB1 + ksl) * 8 + n) * 512;
-            const size_t src = ((size_t)(8 * w + n) * KS2 + 8 * q + ksl) * 512;
-            std::copy(w2p.begin() + src, w2p.begin() + src + 512, out.begin() + dst);
-        }
-    }
-    return out;
-}
-
-// the gated twin: the same blocks, plus behind the layer-1 blocks of every chunk 3 blocks and behind the last chunk 6 blocks of gate projections -- per feature tile
-// (16 q + 4 w + j, then 8 w + n) six 1 KB slots in consumption order: sigma fragments of k-steps 0 and 1, beta fragments of k-steps 0 and 1 (pack_weights with K = GH = 64),
-// then the lane's four scale biases and four bias-projection biases as fp32 bits (lane l: features 16 ft + 4 (l >> 4) + r)
-static std::vector<uint16_t> pack_fused_stream_gated(const std::vector<uint16_t>& w1p, const std::vector<uint16_t>& w2p, int K1, const std::vector<uint16_t> (&wbp)[2],
-                                                     const std::vector<uint16_t> (&wsp)[2], const float* const (&bb)[2], const float* const (&bs)[2]) {
-    const int KS1 = K1 / 32, NB1 = KS1 / 2, NBQ = NB1 + 3 + 8, NBLK = 4 * NBQ + 6, KS2 = 1024 / 32;
-    std::vector<uint16_t> out((size_t)4 * NBLK * 8 * 512, 0);
-    auto gate_tile = [&](size_t slot0, int layer, int ft) {          // six slots from slot index slot0 on
-        for (int ks = 0; ks < 2; ++ks) {
-            std::copy(wsp[layer].begin() + ((size_t)ft * 2 + ks) * 512, wsp[layer].begin() + ((size_t)ft * 2 + ks + 1) * 512, out.begin() + (slot0 + ks) * 512);
-            std::copy(wbp[layer].begin() + ((size_t)ft * 2 + ks) * 512, wbp[layer].begin() + ((size_t)ft * 2 + ks + 1) * 512, out.begin() + (slot0 + 2 + ks) * 512);
-        }
-        for (int l = 0; l < 64; ++l) {
-            memcpy(&out[(slot0 + 4) * 512 + (size_t)l * 8], bs[layer] + 16 * ft + 4 * (l >> 4), 16);
-            memcpy(&out[(slot0 + 5) * 512 + (size_t)l * 8], bb[layer] + 16 * ft + 4 * (l >> 4), 16);
-        }
-    };
-    for (int w = 0; w < 4; ++w) {
-        for (int q = 0; q < 4; ++q) {
-            for (int b1 = 0; b1 < NB1; ++b1) for (int kk = 0; kk < 2; ++kk) for (int j = 0; j < 4; ++j) {
-                const size_t dst = (((size_t)w * NBLK + q * NBQ + b1) * 8 + kk * 4 + j) * 512;
-                const size_t src = ((size_t)(16 * q + 4 * w + j) * KS1 + 2 * b1 + kk) * 512;
-                std::copy(w1p.begin() + src, w1p.begin() + src + 512, out.begin() + dst);
-            }
-            for (int j = 0; j < 4; ++j) gate_tile(((size_t)w * NBLK + q * NBQ + NB1) * 8 + 6 * j, 0, 16 * q + 4 * w + j);
-            for (int ksl = 0; ksl < 8; ++ksl) for (int n = 0; n < 8; ++n) {
-                const size_t dst = (((size_t)w * NBLK + q * NBQ + NB1 + 3 + ksl) * 8 + n) * 512;
-                const size_t src = ((size_t)(8 * w + n) * KS2 + 8 * q + ksl) * 512;
-                std::copy(w2p.begin() + src, w2p.begin() + src + 512, out.begin() + dst);
-            }
-        }
-        for (int n = 0; n < 8; ++n) gate_tile(((size_t)w * NBLK + 4 * NBQ) * 8 + 6 * n, 1, 8 * w + n);
-    }
-    return out;
-}
 
 // the launches of a path id, plain or GATED: one copy of the kernel choice for both
 template <bool GATED>
@@ -144,7 +77,116 @@ int dm_policy_info(dm_policy* p, int32_t* out) {
 
 }  // extern "C"
 
-// gp == nullptr: the plain actor.  With a gate the fused stream is the gated one (pack_fused_stream_gated; gate_hidden = 64 only, else the per-layer kernels)
+// ---------------------------------------------------------------- fp32 weights into a context's packed arrays (k_policy_pack, dm_policy.h)
+// The jobs of one k_policy_pack launch: one per destination array whose source is given, in the buffers policy_create allocated (their sizes: packed_array)
+struct PackPlan {
+    dmp::PackArgs a; unsigned blocks = 0;
+    PackPlan() { memset(&a, 0, sizeof(a)); }
+    void add(int kind, const float* src, const void* dst, int K, int N, int KS, size_t rows) {
+        if (a.njobs >= dmp::PK_MAX_JOBS) return;
+        dmp::PackJob& j = a.job[a.njobs];
+        j.kind = kind; j.K = K; j.N = N; j.KS = KS; j.rows = (int)rows; j.src = src; j.dst = const_cast<void*>(dst);
+        a.first[a.njobs++] = (int)blocks; blocks += (unsigned)((rows + 255) / 256); a.first[a.njobs] = (int)blocks;
+    }
+    // W [K x N] into fragments padded to Kp x Np
+    void frag(const float* W, const uint16_t* dst, int K, int N, int Kp, int Np) { if (W) add(dmp::PK_FRAG, W, dst, K, N, Kp / 32, (size_t)Kp * Np / 8); }
+    void vec(const float* src, const float* dst, int n, int np) { if (src) add(dmp::PK_VEC, src, dst, 0, n, 0, (size_t)np); }
+};
+
+// bytes of the fused stream a context holds: per wave 4 chunks of K1 / 64 + 8 blocks, with a gate 3 more per chunk and 6 behind the last (k_policy_pack, PK_FUSED)
+static size_t fused_stream_bytes(const dm_policy* p) {
+    const int NB1 = p->pd.K1 / 64, NBLK = p->gated ? 4 * (NB1 + 3 + 8) + 6 : 4 * (NB1 + 8);
+    return (size_t)4 * NBLK * 8 * 512 * 2;
+}
+
+template <typename T> static const void* packed_member(const T*& member, void* fresh) { if (fresh) member = static_cast<const T*>(fresh); return member; }
+// the packed device array `which` (include/dm_hip.h dm_policy_packed) and its size; null: the context holds no such array (*bytes is set only for an id the
+// context's kind has).  `fresh`: policy_create's new allocation of that size, which becomes the array.  The ONE statement of the sizes.
+static const void* packed_array(dm_policy* p, int which, size_t* bytes, void* fresh = nullptr) {
+    dmp::PolicyDev& d = p->pd; dmp::GateDev& q = p->gd;
+    const size_t f = sizeof(float);
+    switch (which) {
+    case DM_POLICY_PACKED_W1P: *bytes = (size_t)d.K1 * d.H1 * 2; return packed_member(d.w1p, fresh);
+    case DM_POLICY_PACKED_W2P: *bytes = (size_t)d.H1 * d.H2 * 2; return packed_member(d.w2p, fresh);
+    case DM_POLICY_PACKED_W3P: *bytes = (size_t)d.H2 * d.N3 * 2; return packed_member(d.w3p, fresh);
+    case DM_POLICY_PACKED_B1: *bytes = f * d.H1; return packed_member(d.b1, fresh);
+    case DM_POLICY_PACKED_B2: *bytes = f * d.H2; return packed_member(d.b2, fresh);
+    case DM_POLICY_PACKED_B3: *bytes = f * d.N3; return packed_member(d.b3, fresh);
+    case DM_POLICY_PACKED_S_MEAN: *bytes = f * d.S; return packed_member(d.s_mean, fresh);
+    case DM_POLICY_PACKED_S_INV_STD: *bytes = f * d.S; return packed_member(d.s_inv_std, fresh);
+    case DM_POLICY_PACKED_A_MEAN: *bytes = f * d.A; return packed_member(d.a_mean, fresh);
+    case DM_POLICY_PACKED_A_STD: *bytes = f * d.A; return packed_member(d.a_std, fresh);
+    case DM_POLICY_PACKED_LOGSTD: *bytes = f * d.A; return packed_member(d.logstd, fresh);
+    case DM_POLICY_PACKED_WFS: *bytes = fused_stream_bytes(p); return packed_member(d.wfs, fresh);
+    default: break;
+    }
+    if (!p->gated || which < DM_POLICY_PACKED_GATE_WCP || which > DM_POLICY_PACKED_GATE_BS1) return nullptr;
+    if (which == DM_POLICY_PACKED_GATE_WCP) { *bytes = (size_t)q.KG * q.GC * 2; return packed_member(q.wcp, fresh); }
+    if (which == DM_POLICY_PACKED_GATE_BC) { *bytes = f * q.GC; return packed_member(q.bc, fresh); }
+    const int i = (which - DM_POLICY_PACKED_GATE_WEP0) / 6, H = i ? d.H2 : d.H1;      // six ids per gated layer, in the order of dm_policy_gate_params
+    switch ((which - DM_POLICY_PACKED_GATE_WEP0) % 6) {
+    case 0: *bytes = (size_t)q.GC * q.GH * 2; return packed_member(q.wep[i], fresh);
+    case 1: *bytes = f * q.GH; return packed_member(q.be[i], fresh);
+    case 2: *bytes = (size_t)q.GH * H * 2; return packed_member(q.wbp[i], fresh);
+    case 3: *bytes = f * H; return packed_member(q.bb[i], fresh);
+    case 4: *bytes = (size_t)q.GH * H * 2; return packed_member(q.wsp[i], fresh);
+    default: *bytes = f * H; return packed_member(q.bs[i], fresh);
+    }
+}
+
+// What dm_policy_create(_gated) and dm_policy_set_weights share behind their checks: every array of `pp` / `gp` that is given (widths: the context's) goes through
+// ONE k_policy_pack launch into the context's packed arrays; a null array keeps what the context holds.  Host pointers (no DM_DEVICE_PTRS) are staged through one
+// device temporary and the call returns when the launch is complete; device pointers: asynchronous on `stream`.  With every array given -- policy_create --
+// every byte of every packed array is written, padding included.
+static int policy_pack(dm_policy* p, const dm_policy_params& pp, const dm_policy_gate_params* gp, int flags, rt_stream stream) {
+    const dmp::PolicyDev& d = p->pd; const dmp::GateDev& q = p->gd;
+    dm_policy_params w = pp; dm_policy_gate_params g; memset(&g, 0, sizeof(g)); if (gp) g = *gp;
+    // every array of the two structs with its element count, in one table: the host mode stages through it, nothing else walks the fields
+    struct Arr { const float** ptr; size_t count; };
+    const size_t S = d.S, H1 = d.H1, H2 = d.H2, A = d.A, G = q.G, GC = q.GC, GH = q.GH;
+    const Arr arrs[] = {{&w.w1, S * H1}, {&w.b1, H1}, {&w.w2, H1 * H2}, {&w.b2, H2}, {&w.w3, H2 * A}, {&w.b3, A}, {&w.s_mean, S}, {&w.s_std, S}, {&w.a_mean, A}, {&w.a_std, A}, {&w.logstd, A},
+                        {&g.gc_w, G * GC}, {&g.gc_b, GC}, {&g.g0_w, GC * GH}, {&g.g0_b, GH}, {&g.g0_bias_w, GH * H1}, {&g.g0_bias_b, H1}, {&g.g0_scale_w, GH * H1}, {&g.g0_scale_b, H1},
+                        {&g.g1_w, GC * GH}, {&g.g1_b, GH}, {&g.g1_bias_w, GH * H2}, {&g.g1_bias_b, H2}, {&g.g1_scale_w, GH * H2}, {&g.g1_scale_b, H2}};
+    int rc = 0;
+    // host arrays: one scoped device temporary holds them all, the same kernel reads it
+    std::vector<float> host;
+    if (!(flags & DM_DEVICE_PTRS)) for (const Arr& r : arrs) if (*r.ptr) host.insert(host.end(), *r.ptr, *r.ptr + r.count);
+    DevTmp stage(rc, stream, sizeof(float) * host.size(), host.empty() ? nullptr : host.data());
+    if (rc) return rc;
+    if (stage.p) { const float* at = (const float*)stage.p; for (const Arr& r : arrs) if (*r.ptr) { *r.ptr = at; at += r.count; } }
+
+    PackPlan plan; plan.a.out_in = (flags & DM_WEIGHTS_OUT_IN) ? 1 : 0;
+    plan.frag(w.w1, d.w1p, d.S, d.H1, d.K1, d.H1); plan.frag(w.w2, d.w2p, d.H1, d.H2, d.H1, d.H2); plan.frag(w.w3, d.w3p, d.H2, d.A, d.H2, d.N3);
+    plan.vec(w.b1, d.b1, d.H1, d.H1); plan.vec(w.b2, d.b2, d.H2, d.H2); plan.vec(w.b3, d.b3, d.A, d.N3);
+    plan.vec(w.s_mean, d.s_mean, d.S, d.S); if (w.s_std) plan.add(dmp::PK_RECIP, w.s_std, d.s_inv_std, 0, d.S, 0, (size_t)d.S);
+    plan.vec(w.a_mean, d.a_mean, d.A, d.A); plan.vec(w.a_std, d.a_std, d.A, d.A); plan.vec(w.logstd, d.logstd, d.A, d.A);
+    const float* sw[2] = {g.g0_scale_w, g.g1_scale_w}; const float* sb[2] = {g.g0_scale_b, g.g1_scale_b};
+    const float* bw[2] = {g.g0_bias_w, g.g1_bias_w}; const float* bb[2] = {g.g0_bias_b, g.g1_bias_b};
+    if (p->gated) {
+        const float* ew[2] = {g.g0_w, g.g1_w}; const float* eb[2] = {g.g0_b, g.g1_b};
+        plan.frag(g.gc_w, q.wcp, q.G, q.GC, q.KG, q.GC); plan.vec(g.gc_b, q.bc, q.GC, q.GC);
+        for (int i = 0; i < 2; ++i) {
+            const int H = i ? d.H2 : d.H1;
+            plan.frag(ew[i], q.wep[i], q.GC, q.GH, q.GC, q.GH); plan.vec(eb[i], q.be[i], q.GH, q.GH);
+            plan.frag(bw[i], q.wbp[i], q.GH, H, q.GH, H); plan.vec(bb[i], q.bb[i], H, H);
+            plan.frag(sw[i], q.wsp[i], q.GH, H, q.GH, H); plan.vec(sb[i], q.bs[i], H, H);
+        }
+    }
+    // the fused stream straight from the fp32 sources; a row whose source is not given keeps its bytes
+    dmp::PackFused& fs = plan.a.fs;
+    fs.gated = p->gated ? 1 : 0; fs.NB1 = d.K1 / 64; fs.S = d.S; fs.w1 = w.w1; fs.w2 = w.w2;
+    for (int i = 0; i < 2; ++i) { fs.ws[i] = sw[i]; fs.wb[i] = bw[i]; fs.bs[i] = sb[i]; fs.bb[i] = bb[i]; }
+    const bool fused_src = w.w1 || w.w2 || (p->gated && (sw[0] || sw[1] || bw[0] || bw[1] || sb[0] || sb[1] || bb[0] || bb[1]));
+    if (d.wfs && fused_src) plan.add(dmp::PK_FUSED, nullptr, d.wfs, 0, 0, 0, fused_stream_bytes(p) / 16);   // (its sources: PackFused)
+    if (plan.blocks == 0) return 0;                        // nothing given: nothing to do
+    RT_LAUNCH4(dmp::k_policy_pack, plan.blocks, stream, plan.a);
+    if (launch_status(0)) return -1;
+    if (stage.p && rt_sync(stream) != 0) return fail("stream synchronize failed");      // the temporary is freed with this scope
+    return 0;
+}
+
+// gp == nullptr: the plain actor.  With a gate the fused stream is the gated one (gate_hidden = 64 only, else the per-layer kernels).  Validation, the padded widths
+// and the allocation are here; what goes into the arrays is policy_pack's.
 static int policy_create(int device_id, const dm_policy_params* pp, const dm_policy_gate_params* gp, dm_policy** out) {
     if (!pp || !out) return fail("null argument");
     if (pp->state_dim < 1 || pp->action_dim < 1 || pp->hidden1 < 64 || pp->hidden2 < 64) return fail("dm_policy_create: bad layer widths");
@@ -168,61 +210,42 @@ static int policy_create(int device_id, const dm_policy_params* pp, const dm_pol
     dmp::PolicyDev& d = p->pd; memset(&d, 0, sizeof(d));
     d.S = pp->state_dim; d.H1 = pp->hidden1; d.H2 = pp->hidden2; d.A = pp->action_dim;
     d.K1 = (d.S + 63) / 64 * 64; d.N3 = (d.A + 31) / 32 * 32;
-    std::vector<uint16_t> w1 = pack_weights(pp->w1, d.S, d.H1, d.K1, d.H1), w2 = pack_weights(pp->w2, d.H1, d.H2, d.H1, d.H2), w3 = pack_weights(pp->w3, d.H2, d.A, d.H2, d.N3);
-    std::vector<float> b3(d.N3, 0.0f), sm(d.S, 0.0f), si(d.S, 1.0f), am(d.A, 0.0f), as(d.A, 1.0f), ls(d.A, 0.0f);
-    for (int i = 0; i < d.A; ++i) { b3[i] = pp->b3[i]; if (pp->a_mean) am[i] = pp->a_mean[i]; if (pp->a_std) as[i] = pp->a_std[i]; if (pp->logstd) ls[i] = pp->logstd[i]; }
-    for (int i = 0; i < d.S; ++i) { if (pp->s_mean) sm[i] = pp->s_mean[i]; if (pp->s_std) si[i] = 1.0f / pp->s_std[i]; }
-    // one-launch actor: compiled for the reference's widths (1024, 512), K1 = 256 / 384 and up to 64 action slots; a K1 of 320 is padded up to 384
-    d.wfs = nullptr;
+    // one-launch actor: compiled for the reference's widths (1024, 512), K1 = 256 / 384 and up to 64 action slots; a K1 of 320 or below 256 is padded up
     const bool fusable = d.H1 == 1024 && d.H2 == 512 && d.K1 <= 384 && d.N3 <= 64 && (!gp || gp->gate_hidden == 64);
-    if (fusable) {
-        if (d.K1 == 320) { d.K1 = 384; w1 = pack_weights(pp->w1, d.S, d.H1, d.K1, d.H1); }
-        if (d.K1 < 256) { d.K1 = 256; w1 = pack_weights(pp->w1, d.S, d.H1, d.K1, d.H1); }
-    }
-    if (fusable && !gp) {
-        std::vector<uint16_t> fs = pack_fused_stream(w1, w2, d.K1);
-        d.wfs = (const uint16_t*)p->up(fs.data(), fs.size() * 2);
-        if (!d.wfs) { delete p; return fail("device allocation failed"); }
-    }
-    d.w1p = (const uint16_t*)p->up(w1.data(), w1.size() * 2); d.w2p = (const uint16_t*)p->up(w2.data(), w2.size() * 2); d.w3p = (const uint16_t*)p->up(w3.data(), w3.size() * 2);
-    d.b1 = (const float*)p->up(pp->b1, sizeof(float) * d.H1); d.b2 = (const float*)p->up(pp->b2, sizeof(float) * d.H2); d.b3 = (const float*)p->up(b3.data(), sizeof(float) * d.N3);
-    d.s_mean = (const float*)p->up(sm.data(), sizeof(float) * d.S); d.s_inv_std = (const float*)p->up(si.data(), sizeof(float) * d.S);
-    d.a_mean = (const float*)p->up(am.data(), sizeof(float) * d.A); d.a_std = (const float*)p->up(as.data(), sizeof(float) * d.A);
-    d.logstd = (const float*)p->up(ls.data(), sizeof(float) * d.A);
+    if (fusable) d.K1 = d.K1 <= 256 ? 256 : 384;
     d.s_clip = (pp->s_clip > 0) ? (float)pp->s_clip : std::numeric_limits<float>::infinity();
-    if (!d.w1p || !d.w2p || !d.w3p || !d.b1 || !d.b2 || !d.b3 || !d.s_mean || !d.s_inv_std || !d.a_mean || !d.a_std || !d.logstd) { delete p; return fail("device allocation failed"); }
-    if (gp) {
-        dmp::GateDev& q = p->gd; memset(&q, 0, sizeof(q));
-        q.G = gp->goal_dim; q.KG = (q.G + 31) / 32 * 32; q.GC = gp->gate_common; q.GH = gp->gate_hidden;
-        const float* ew[2] = {gp->g0_w, gp->g1_w}; const float* eb[2] = {gp->g0_b, gp->g1_b};
-        const float* bw[2] = {gp->g0_bias_w, gp->g1_bias_w}; const float* bb[2] = {gp->g0_bias_b, gp->g1_bias_b};
-        const float* sw[2] = {gp->g0_scale_w, gp->g1_scale_w}; const float* sb[2] = {gp->g0_scale_b, gp->g1_scale_b};
-        std::vector<uint16_t> last;
-        auto upw = [&](const float* W, int K, int N, int Kp) { last = pack_weights(W, K, N, Kp, N); return (const uint16_t*)p->up(last.data(), last.size() * 2); };
-        std::vector<uint16_t> hwb[2], hws[2];
-        q.wcp = upw(gp->gc_w, q.G, q.GC, q.KG); q.bc = (const float*)p->up(gp->gc_b, sizeof(float) * q.GC);
-        bool ok = q.wcp && q.bc;
-        for (int i = 0; i < 2; ++i) {
-            const int H = i ? d.H2 : d.H1;
-            q.wep[i] = upw(ew[i], q.GC, q.GH, q.GC); q.be[i] = (const float*)p->up(eb[i], sizeof(float) * q.GH);
-            q.wbp[i] = upw(bw[i], q.GH, H, q.GH); hwb[i] = last; q.bb[i] = (const float*)p->up(bb[i], sizeof(float) * H);
-            q.wsp[i] = upw(sw[i], q.GH, H, q.GH); hws[i] = last; q.bs[i] = (const float*)p->up(sb[i], sizeof(float) * H);
-            ok = ok && q.wep[i] && q.be[i] && q.wbp[i] && q.bb[i] && q.wsp[i] && q.bs[i];
-        }
-        if (ok && fusable) {
-            std::vector<uint16_t> fs = pack_fused_stream_gated(w1, w2, d.K1, hwb, hws, bb, sb);
-            d.wfs = (const uint16_t*)p->up(fs.data(), fs.size() * 2);
-            ok = d.wfs != nullptr;
-        }
-        if (ok) { p->gd_dev = (const dmp::GateDev*)p->up(&q, sizeof(q)); ok = p->gd_dev != nullptr; }
-        if (!ok) { delete p; return fail("device allocation failed"); }
-        p->gated = true;
+    dmp::GateDev& q = p->gd; memset(&q, 0, sizeof(q));
+    if (gp) { p->gated = true; q.G = gp->goal_dim; q.KG = (q.G + 31) / 32 * 32; q.GC = gp->gate_common; q.GH = gp->gate_hidden; }
+    // every packed array the context holds, at the size packed_array states for it (the fused stream only where its kernel is compiled)
+    for (int which = 0; which <= DM_POLICY_PACKED_GATE_BS1; ++which) {
+        size_t bytes = 0;
+        packed_array(p, which, &bytes);
+        if (bytes == 0 || (which == DM_POLICY_PACKED_WFS && !fusable)) continue;
+        if (!packed_array(p, which, &bytes, p->alloc(bytes))) { delete p; return fail("device allocation failed"); }
     }
+    if (gp) {                                             // the fused kernel reads the gate's first layers through a device copy of the pointers
+        void* g = p->alloc(sizeof(q));
+        if (!g || rt_h2d(g, &q, sizeof(q), 0)) { delete p; return fail("device allocation failed"); }
+        p->gd_dev = (const dmp::GateDev*)g;
+    }
+    // an optional array that is not given: its default, packed like a given one (s_inv_std = 1)
+    dm_policy_params w = *pp;
+    const std::vector<float> zeros((size_t)std::max(d.S, d.A), 0.0f), ones(zeros.size(), 1.0f);
+    for (const float** a : {&w.s_mean, &w.a_mean, &w.logstd}) if (!*a) *a = zeros.data();
+    for (const float** a : {&w.s_std, &w.a_std}) if (!*a) *a = ones.data();
+    if (policy_pack(p, w, gp, 0, 0)) { delete p; return -1; }
     *out = p;
     return 0;
 }
 
 static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_stream);
+
+// the goal arguments of dm_policy_forward_ex / dm_policy_eval_scalar; `fn`, `net`: the caller's name and its word for the context, for the message
+static int check_goal(const dm_policy* p, const char* fn, const char* net, const float* goals_dev, int goal_dim) {
+    if (goal_dim < 0 || goal_dim >= p->pd.S || (goal_dim > 0 && !goals_dev)) return fail(std::string(fn) + ": goal_dim must be in [0, state_dim) with a goal block when positive (state_dim counts the goal columns)");
+    if (p->gated && goal_dim != 0 && goal_dim != p->gd.G) return fail(std::string(fn) + ": a gated " + net + " takes its goal as a block of the gate's goal_dim columns, or goal_dim = 0 with the goal in the last columns of states_dev");
+    return 0;
+}
 
 extern "C" {
 
@@ -246,8 +269,7 @@ int dm_policy_forward(dm_policy* p, const float* states_dev, int n, float* actio
 int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goals_dev, int goal_dim, int n, float* actions_dev, float* logp_dev,
                          int32_t* exp_flags_dev, double exp_rate, int sample, uint64_t seed, uint32_t step, int env_id_offset, void* hip_stream) {
     if (!p || !states_dev || !actions_dev) return fail("null argument");
-    if (goal_dim < 0 || goal_dim >= p->pd.S || (goal_dim > 0 && !goals_dev)) return fail("dm_policy_forward_ex: goal_dim must be in [0, state_dim) with a goal block when positive (state_dim counts the goal columns)");
-    if (p->gated && goal_dim != 0 && goal_dim != p->gd.G) return fail("dm_policy_forward_ex: a gated actor takes its goal as a block of the gate's goal_dim columns, or goal_dim = 0 with the goal in the last columns of states_dev");
+    if (check_goal(p, "dm_policy_forward_ex", "actor", goals_dev, goal_dim)) return -1;
     if (!(exp_rate >= 0.0 && exp_rate <= 1.0)) return fail("dm_policy_forward_ex: exp_rate must be in [0, 1]");
     if (n <= 0) return 0;
     dmp::ScalarIO io; memset(&io, 0, sizeof(io));
@@ -297,8 +319,8 @@ static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_st
         if (io.probe == 2) { if (!prof_buf && hipMalloc((void**)&prof_buf, (size_t)8192 * 8 * 8) != hipSuccess) prof_buf = nullptr; io.prof = grid <= 8192 ? prof_buf : nullptr; }
 #endif
         if (p->gated) launch_fused<true>(path, grid, stream, d, pio); else launch_fused<false>(path, grid, stream, d, pio);
+        if (launch_status(0)) return -1;
 #ifndef DM_EMU
-        hipError_t le0 = hipGetLastError(); if (le0 != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le0));
         if (io.prof && ++prof_calls == 100) {          // DM_POLICY_PROBE=2: phase times of the 100th launch (100 MHz constant clock -> ns), mean over the workgroups
             (void)hipStreamSynchronize(stream);
             std::vector<unsigned long long> h((size_t)grid * 8); (void)hipMemcpy(h.data(), prof_buf, h.size() * 8, hipMemcpyDeviceToHost);
@@ -328,8 +350,7 @@ int dm_policy_eval_scalar(dm_policy* p, const float* states_dev, const float* go
                           float* raw_out_dev, void* hip_stream) {
     if (!p || !states_dev || !head || !out_dev) return fail("null argument");
     if (p->pd.A != 1) return fail("dm_policy_eval_scalar: the context has action_dim " + std::to_string(p->pd.A) + ", a scalar head needs a net with one output (create it with action_dim = 1)");
-    if (goal_dim < 0 || goal_dim >= p->pd.S || (goal_dim > 0 && !goals_dev)) return fail("dm_policy_eval_scalar: goal_dim must be in [0, state_dim) with a goal block when positive (state_dim counts the goal columns)");
-    if (p->gated && goal_dim != 0 && goal_dim != p->gd.G) return fail("dm_policy_eval_scalar: a gated net takes its goal as a block of the gate's goal_dim columns, or goal_dim = 0 with the goal in the last columns of states_dev");
+    if (check_goal(p, "dm_policy_eval_scalar", "net", goals_dev, goal_dim)) return -1;
     if (head->kind != DM_SCALAR_HEAD_VALUE && head->kind != DM_SCALAR_HEAD_STYLE) return fail("dm_policy_eval_scalar: head kind must be DM_SCALAR_HEAD_VALUE or DM_SCALAR_HEAD_STYLE");
     if (head->kind == DM_SCALAR_HEAD_VALUE && !(head->lo <= head->hi)) return fail("dm_policy_eval_scalar: value head needs lo <= hi (infinite bounds: no clipping)");
     if (head->kind == DM_SCALAR_HEAD_STYLE && head->task_reward_dev && !(head->lerp >= 0.0f && head->lerp <= 1.0f)) return fail("dm_policy_eval_scalar: lerp must be in [0, 1]");
@@ -350,61 +371,6 @@ int dm_policy_scalar_info(dm_policy* p, int32_t* out) {
 }
 
 }  // extern "C"
-
-// ---------------------------------------------------------------- weights into a live context (k_policy_pack, dm_policy.h)
-// The jobs of one k_policy_pack launch: one per destination array whose source is given, in the buffers policy_create allocated (their sizes: packed_array)
-struct PackPlan {
-    dmp::PackArgs a; unsigned blocks = 0;
-    PackPlan() { memset(&a, 0, sizeof(a)); }
-    void add(int kind, const float* src, const void* dst, int K, int N, int KS, size_t rows) {
-        if (a.njobs >= dmp::PK_MAX_JOBS) return;
-        dmp::PackJob& j = a.job[a.njobs];
-        j.kind = kind; j.K = K; j.N = N; j.KS = KS; j.rows = (int)rows; j.src = src; j.dst = const_cast<void*>(dst);
-        a.first[a.njobs++] = (int)blocks; blocks += (unsigned)((rows + 255) / 256); a.first[a.njobs] = (int)blocks;
-    }
-    // W [K x N] into fragments padded to Kp x Np
-    void frag(const float* W, const uint16_t* dst, int K, int N, int Kp, int Np) { if (W) add(dmp::PK_FRAG, W, dst, K, N, Kp / 32, (size_t)Kp * Np / 8); }
-    void vec(const float* src, const float* dst, int n, int np) { if (src) add(dmp::PK_VEC, src, dst, 0, n, 0, (size_t)np); }
-};
-
-// bytes of the fused stream a context holds (pack_fused_stream / pack_fused_stream_gated)
-static size_t fused_stream_bytes(const dm_policy* p) {
-    const int NB1 = p->pd.K1 / 64, NBLK = p->gated ? 4 * (NB1 + 3 + 8) + 6 : 4 * (NB1 + 8);
-    return (size_t)4 * NBLK * 8 * 512 * 2;
-}
-
-// the packed device array `which` (include/dm_hip.h dm_policy_packed) and its size; null: the context holds no such array
-static const void* packed_array(const dm_policy* p, int which, size_t* bytes) {
-    const dmp::PolicyDev& d = p->pd; const dmp::GateDev& q = p->gd;
-    const size_t f = sizeof(float);
-    switch (which) {
-    case DM_POLICY_PACKED_W1P: *bytes = (size_t)d.K1 * d.H1 * 2; return d.w1p;
-    case DM_POLICY_PACKED_W2P: *bytes = (size_t)d.H1 * d.H2 * 2; return d.w2p;
-    case DM_POLICY_PACKED_W3P: *bytes = (size_t)d.H2 * d.N3 * 2; return d.w3p;
-    case DM_POLICY_PACKED_B1: *bytes = f * d.H1; return d.b1;
-    case DM_POLICY_PACKED_B2: *bytes = f * d.H2; return d.b2;
-    case DM_POLICY_PACKED_B3: *bytes = f * d.N3; return d.b3;
-    case DM_POLICY_PACKED_S_MEAN: *bytes = f * d.S; return d.s_mean;
-    case DM_POLICY_PACKED_S_INV_STD: *bytes = f * d.S; return d.s_inv_std;
-    case DM_POLICY_PACKED_A_MEAN: *bytes = f * d.A; return d.a_mean;
-    case DM_POLICY_PACKED_A_STD: *bytes = f * d.A; return d.a_std;
-    case DM_POLICY_PACKED_LOGSTD: *bytes = f * d.A; return d.logstd;
-    case DM_POLICY_PACKED_WFS: *bytes = fused_stream_bytes(p); return d.wfs;
-    default: break;
-    }
-    if (!p->gated || which < DM_POLICY_PACKED_GATE_WCP || which > DM_POLICY_PACKED_GATE_BS1) return nullptr;
-    if (which == DM_POLICY_PACKED_GATE_WCP) { *bytes = (size_t)q.KG * q.GC * 2; return q.wcp; }
-    if (which == DM_POLICY_PACKED_GATE_BC) { *bytes = f * q.GC; return q.bc; }
-    const int i = (which - DM_POLICY_PACKED_GATE_WEP0) / 6, H = i ? d.H2 : d.H1;      // six ids per gated layer, in the order of dm_policy_gate_params
-    switch ((which - DM_POLICY_PACKED_GATE_WEP0) % 6) {
-    case 0: *bytes = (size_t)q.GC * q.GH * 2; return q.wep[i];
-    case 1: *bytes = f * q.GH; return q.be[i];
-    case 2: *bytes = (size_t)q.GH * H * 2; return q.wbp[i];
-    case 3: *bytes = f * H; return q.bb[i];
-    case 4: *bytes = (size_t)q.GH * H * 2; return q.wsp[i];
-    default: *bytes = f * H; return q.bs[i];
-    }
-}
 
 static int width_mismatch(const char* what, int got, int have) {
     return fail(std::string("dm_policy_set_weights: ") + what + " is " + std::to_string(got) + ", the context has " + std::to_string(have));
@@ -427,53 +393,8 @@ int dm_policy_set_weights(dm_policy* p, const dm_policy_params* pp, const dm_pol
         if (gp->gate_common != q.GC) return width_mismatch("gate_common", gp->gate_common, q.GC);
         if (gp->gate_hidden != q.GH) return width_mismatch("gate_hidden", gp->gate_hidden, q.GH);
     }
-    dm_policy_params w = *pp; dm_policy_gate_params g; memset(&g, 0, sizeof(g)); if (gp) g = *gp;
-    // every array of the two structs with its element count, in one table: the host mode stages through it, nothing else walks the fields
-    struct Arr { const float** ptr; size_t count; };
-    const size_t S = d.S, H1 = d.H1, H2 = d.H2, A = d.A, G = q.G, GC = q.GC, GH = q.GH;
-    const Arr arrs[] = {{&w.w1, S * H1}, {&w.b1, H1}, {&w.w2, H1 * H2}, {&w.b2, H2}, {&w.w3, H2 * A}, {&w.b3, A}, {&w.s_mean, S}, {&w.s_std, S}, {&w.a_mean, A}, {&w.a_std, A}, {&w.logstd, A},
-                        {&g.gc_w, G * GC}, {&g.gc_b, GC}, {&g.g0_w, GC * GH}, {&g.g0_b, GH}, {&g.g0_bias_w, GH * H1}, {&g.g0_bias_b, H1}, {&g.g0_scale_w, GH * H1}, {&g.g0_scale_b, H1},
-                        {&g.g1_w, GC * GH}, {&g.g1_b, GH}, {&g.g1_bias_w, GH * H2}, {&g.g1_bias_b, H2}, {&g.g1_scale_w, GH * H2}, {&g.g1_scale_b, H2}};
     DevGuard guard(p->device_id);
-    rt_stream stream = (rt_stream)hip_stream;
-    int rc = 0;
-    // host arrays: one scoped device temporary holds them all, the same kernel reads it
-    std::vector<float> host;
-    if (!(flags & DM_DEVICE_PTRS)) for (const Arr& r : arrs) if (*r.ptr) host.insert(host.end(), *r.ptr, *r.ptr + r.count);
-    DevTmp stage(rc, stream, sizeof(float) * host.size(), host.empty() ? nullptr : host.data());
-    if (rc) return rc;
-    if (stage.p) { const float* at = (const float*)stage.p; for (const Arr& r : arrs) if (*r.ptr) { *r.ptr = at; at += r.count; } }
-
-    PackPlan plan; plan.a.out_in = (flags & DM_WEIGHTS_OUT_IN) ? 1 : 0;
-    plan.frag(w.w1, d.w1p, d.S, d.H1, d.K1, d.H1); plan.frag(w.w2, d.w2p, d.H1, d.H2, d.H1, d.H2); plan.frag(w.w3, d.w3p, d.H2, d.A, d.H2, d.N3);
-    plan.vec(w.b1, d.b1, d.H1, d.H1); plan.vec(w.b2, d.b2, d.H2, d.H2); plan.vec(w.b3, d.b3, d.A, d.N3);
-    plan.vec(w.s_mean, d.s_mean, d.S, d.S); if (w.s_std) plan.add(dmp::PK_RECIP, w.s_std, d.s_inv_std, 0, d.S, 0, (size_t)d.S);
-    plan.vec(w.a_mean, d.a_mean, d.A, d.A); plan.vec(w.a_std, d.a_std, d.A, d.A); plan.vec(w.logstd, d.logstd, d.A, d.A);
-    const float* sw[2] = {g.g0_scale_w, g.g1_scale_w}; const float* sb[2] = {g.g0_scale_b, g.g1_scale_b};
-    const float* bw[2] = {g.g0_bias_w, g.g1_bias_w}; const float* bb[2] = {g.g0_bias_b, g.g1_bias_b};
-    if (p->gated) {
-        const float* ew[2] = {g.g0_w, g.g1_w}; const float* eb[2] = {g.g0_b, g.g1_b};
-        plan.frag(g.gc_w, q.wcp, q.G, q.GC, q.KG, q.GC); plan.vec(g.gc_b, q.bc, q.GC, q.GC);
-        for (int i = 0; i < 2; ++i) {
-            const int H = i ? d.H2 : d.H1;
-            plan.frag(ew[i], q.wep[i], q.GC, q.GH, q.GC, q.GH); plan.vec(eb[i], q.be[i], q.GH, q.GH);
-            plan.frag(bw[i], q.wbp[i], q.GH, H, q.GH, H); plan.vec(bb[i], q.bb[i], H, H);
-            plan.frag(sw[i], q.wsp[i], q.GH, H, q.GH, H); plan.vec(sb[i], q.bs[i], H, H);
-        }
-    }
-    // the fused stream straight from the fp32 sources; a row whose source is not given keeps its bytes
-    dmp::PackFused& fs = plan.a.fs;
-    fs.gated = p->gated ? 1 : 0; fs.NB1 = d.K1 / 64; fs.S = d.S; fs.w1 = w.w1; fs.w2 = w.w2;
-    for (int i = 0; i < 2; ++i) { fs.ws[i] = sw[i]; fs.wb[i] = bw[i]; fs.bs[i] = sb[i]; fs.bb[i] = bb[i]; }
-    const bool fused_src = w.w1 || w.w2 || (p->gated && (sw[0] || sw[1] || bw[0] || bw[1] || sb[0] || sb[1] || bb[0] || bb[1]));
-    if (d.wfs && fused_src) plan.add(dmp::PK_FUSED, nullptr, d.wfs, 0, 0, 0, fused_stream_bytes(p) / 16);   // (its sources: PackFused)
-    if (plan.blocks == 0) return 0;                        // nothing given: nothing to do
-    RT_LAUNCH4(dmp::k_policy_pack, plan.blocks, stream, plan.a);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    if (stage.p && rt_sync(stream) != 0) return fail("stream synchronize failed");      // the temporary is freed with this scope
-    return 0;
+    return policy_pack(p, *pp, gp, flags, (rt_stream)hip_stream);
 }
 
 int dm_policy_read_packed(dm_policy* p, int which, void* host_out, size_t capacity, size_t* bytes) {

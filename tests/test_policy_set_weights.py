@@ -1,10 +1,16 @@
 """New weights into a live policy context (include/dm_hip.h dm_policy_set_weights, dm_policy_read_packed; k_policy_pack of deepmimic_amd/csrc/dm_policy.h).
 
-The device pack must make of an fp32 array exactly what the host packers of dm_policy_create make of it.  For every shape of SHAPES -- the smallest set that
-reaches every packing branch -- two contexts P_A, P_B are created from the asymmetric random weights A and B (all biases, normalisers and logstd non-zero and
-different), P_A takes B through set_weights*, and then
+dm_policy_create(_gated) and dm_policy_set_weights pack through the same kernel, so "refresh equals create" says nothing about the layout.  Two things here do:
 
-* read_packed of EVERY array (padding included) is byte-equal between P_A and P_B -- and differed before the call;
+* np_packed: the layout stated once more, in numpy -- fragment order, the fused stream's block order (plain and gated), bias slots as fp32 bits, 1 / s_std, zero
+  padding, round-to-nearest-even to bf16 with NaN -> 0x7fc0.  Every expected byte of the refresh tests comes from it.
+* tests/golden/policy_packed_sha256.json: SHA-256 of every packed array of every shape, recorded from the last commit whose dm_policy_create packed on the host
+  (tests/golden/make_policy_packed_sha256.py).  A fresh context AND np_packed must reproduce them from golden_weights (integer arithmetic only).
+
+For every shape of SHAPES -- the smallest set that reaches every packing branch -- two contexts P_A, P_B are created from the asymmetric random weights A and B
+(all biases, normalisers and logstd non-zero and different), P_A takes B through set_weights*, and then
+
+* read_packed of EVERY array (padding included) of P_A and of P_B is byte-equal to np_packed(B) -- and P_A's differed before the call;
 * forward (mode, and sampled with one seed; 33 rows, so a 32-row tile is crossed) gives bit-identical actions and log-probabilities -- and differed before.
 
 Modes: "device" (device pointers, [in, out]; every source starts 4 bytes behind a 16-byte boundary, as a torch view may), "out_in" (the same B handed over as
@@ -14,6 +20,9 @@ compare bytes there and the small widths run the forward.
 """
 import ctypes as C
 import functools
+import hashlib
+import json
+import os
 from dataclasses import dataclass
 
 import numpy as np
@@ -146,6 +155,153 @@ def frag_index(k, n, Kp):
     return (((n // 16) * (Kp // 32) + k // 32) * 64 + (n % 16) + 16 * ((k % 32) // 8)) * 8 + k % 8
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------- the layout, in numpy
+def bf16_bits(x):
+    """fp32 -> bf16 codes: round to nearest, ties to even; every NaN -> 0x7fc0"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    out = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16).astype(np.uint16)
+    out[(u & 0x7FFFFFFF) > 0x7F800000] = 0x7FC0
+    return out
+
+
+def frags(W, Kp, Np):
+    """W [K x N] as MFMA B-operand fragments [n-tile][k-step][512]: bf16, zero-padded to Kp x Np; inside a fragment lane l = 16 g + c holds the eight
+    consecutive k = 32 ks + 8 g + i of column n = 16 nt + c (frag_index says the same per element)"""
+    K, N = W.shape
+    P = np.zeros((Kp, Np), np.uint16)
+    P[:K, :N] = bf16_bits(W)
+    return P.reshape(Kp // 32, 4, 8, Np // 16, 16).transpose(3, 0, 1, 4, 2).reshape(Np // 16, Kp // 32, 512)      # [ks, g, i, nt, c] -> [nt, ks, g, c, i]
+
+
+def bias_slot(b, ft):
+    """a 1 KB slot of fp32 bits: lane l holds the four biases of features 16 ft + 4 (l >> 4) + r"""
+    return np.repeat(np.ascontiguousarray(b[16 * ft:16 * ft + 16], dtype=np.float32).reshape(4, 1, 4), 16, axis=1).reshape(-1).view(np.uint16)
+
+
+def fused_stream(w, K1, gated):
+    """the weight stream of the one-launch actor (H1 = 1024, H2 = 512, gate_hidden = 64): 1 KB slots (one fragment each), eight to a block.  Per wave w = 0 .. 3 and
+    per layer-1 chunk q = 0 .. 3: K1 / 64 blocks {k-steps 2 b, 2 b + 1 x feature tiles 16 q + 4 w + j} of layer 1; gated: 3 blocks = the gate tiles of those four
+    feature tiles; 8 blocks {k-step 8 q + ksl x feature tiles 8 w + n} of layer 2.  Gated: behind the last chunk 6 blocks = the gate tiles of layer 2's feature
+    tiles 8 w + n.  A gate tile is six slots: sigma fragments of k-steps 0, 1, beta fragments of k-steps 0, 1, the sigma biases, the beta biases."""
+    F1, F2 = frags(w["w1"], K1, 1024), frags(w["w2"], 1024, 512)
+    if gated:
+        Fs = [frags(w["g%d_scale_w" % i], 64, H) for i, H in ((0, 1024), (1, 512))]
+        Fb = [frags(w["g%d_bias_w" % i], 64, H) for i, H in ((0, 1024), (1, 512))]
+    out = []
+
+    def gate_tile(i, ft):
+        out.extend([Fs[i][ft, 0], Fs[i][ft, 1], Fb[i][ft, 0], Fb[i][ft, 1], bias_slot(w["g%d_scale_b" % i], ft), bias_slot(w["g%d_bias_b" % i], ft)])
+    for wv in range(4):
+        for q in range(4):
+            for b in range(K1 // 64):
+                out.extend(F1[16 * q + 4 * wv + j, 2 * b + kk] for kk in range(2) for j in range(4))
+            if gated:
+                for j in range(4):
+                    gate_tile(0, 16 * q + 4 * wv + j)
+            for ksl in range(8):
+                out.extend(F2[8 * wv + n, 8 * q + ksl] for n in range(8))
+        if gated:
+            for n in range(8):
+                gate_tile(1, 8 * wv + n)
+    return np.concatenate(out)
+
+
+def np_packed(w, sh):
+    """every packed array of a context made from the weights dict `w` of Shape `sh`, as read_packed hands them back (uint8), by the names of PACKED_IDS"""
+    f32 = lambda a, n=None: np.concatenate([np.asarray(a, np.float32), np.zeros((n or len(a)) - len(a), np.float32)])
+    opt = lambda k, n, fill: w[k] if w.get(k) is not None else np.full(n, fill, np.float32)
+    out = dict(w1p=frags(w["w1"], sh.K1, sh.H1), w2p=frags(w["w2"], sh.H1, sh.H2), w3p=frags(w["w3"], sh.H2, sh.N3),
+               b1=f32(w["b1"]), b2=f32(w["b2"]), b3=f32(w["b3"], sh.N3), s_mean=f32(opt("s_mean", sh.S, 0)), s_inv_std=np.float32(1) / f32(opt("s_std", sh.S, 1)),
+               a_mean=f32(opt("a_mean", sh.A, 0)), a_std=f32(opt("a_std", sh.A, 1)), logstd=f32(opt("logstd", sh.A, 0)))
+    if sh.fused:
+        out["wfs"] = fused_stream(w, sh.K1, sh.G > 0)
+    if sh.G:
+        out.update(gate_wcp=frags(w["gc_w"], (sh.G + 31) // 32 * 32, sh.GC), gate_bc=f32(w["gc_b"]))
+        for i, H in ((0, sh.H1), (1, sh.H2)):
+            out.update({"gate_wep%d" % i: frags(w["g%d_w" % i], sh.GC, sh.GH), "gate_be%d" % i: f32(w["g%d_b" % i]),
+                        "gate_wbp%d" % i: frags(w["g%d_bias_w" % i], sh.GH, H), "gate_bb%d" % i: f32(w["g%d_bias_b" % i]),
+                        "gate_wsp%d" % i: frags(w["g%d_scale_w" % i], sh.GH, H), "gate_bs%d" % i: f32(w["g%d_scale_b" % i])})
+    assert all(v.dtype in (np.float32, np.uint16) for v in out.values())
+    return {k: np.ascontiguousarray(out[k]).reshape(-1).view(np.uint8) for k in PACKED_IDS if k in out}
+
+
+@functools.lru_cache(maxsize=None)
+def packed_ref(name, seed):
+    """np_packed of weights(name, seed), once per shape.  Shared between the tests: never written to."""
+    p = np_packed(weights(name, seed), SHAPES[name])
+    for v in p.values():
+        v.setflags(write=False)
+    return p
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------- golden bytes
+OPTIONAL = ("s_mean", "s_std", "a_mean", "a_std", "logstd")
+GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "policy_packed_sha256.json")
+GOLDEN_CASES = [n + v for n in SHAPES for v in ("", "/defaults")]      # "/defaults": created without the arrays of OPTIONAL
+
+
+def hash_floats(n, salt):
+    """n float32 in (-1, 1), none zero: odd multiples of 2^-24 from a 32-bit multiplicative hash of the index.  Integer arithmetic only and every value exact
+    in fp32, so the bits depend on no numpy version and no random generator"""
+    h = ((np.arange(1, n + 1, dtype=np.uint64) + np.uint64(0x9E3779B9 * (salt + 1) & 0xFFFFFFFF)) * np.uint64(2654435761)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(15)
+    h = (h * np.uint64(2246822519)) & np.uint64(0xFFFFFFFF)
+    h ^= h >> np.uint64(13)
+    return (((h >> np.uint64(8)).astype(np.int64) * 2 + 1 - 2 ** 24).astype(np.float64) / 2.0 ** 24).astype(np.float32)
+
+
+def golden_weights(case):
+    """the weights of a golden case: hash_floats per array (distinct salts), the standard deviations 1 + |.|, SPECIAL planted in every matrix at evenly spaced
+    flat positions"""
+    name, _, variant = case.partition("/")
+    sh = SHAPES[name]
+    shapes = dict(w1=(sh.S, sh.H1), b1=(sh.H1,), w2=(sh.H1, sh.H2), b2=(sh.H2,), w3=(sh.H2, sh.A), b3=(sh.A,), s_mean=(sh.S,), s_std=(sh.S,), a_mean=(sh.A,),
+                  a_std=(sh.A,), logstd=(sh.A,))
+    if sh.G:
+        shapes.update(gc_w=(sh.G, sh.GC), gc_b=(sh.GC,))
+        for i, H in ((0, sh.H1), (1, sh.H2)):
+            shapes.update({"g%d_w" % i: (sh.GC, sh.GH), "g%d_b" % i: (sh.GH,), "g%d_bias_w" % i: (sh.GH, H), "g%d_bias_b" % i: (H,),
+                           "g%d_scale_w" % i: (sh.GH, H), "g%d_scale_b" % i: (H,)})
+    w = {}
+    for salt, k in enumerate(PLAIN_KEYS + GATE_KEYS):
+        if k not in shapes or (variant == "defaults" and k in OPTIONAL):
+            continue
+        v = hash_floats(int(np.prod(shapes[k])), salt)
+        if k in ("s_std", "a_std"):
+            v = (1.0 + np.abs(v.astype(np.float64))).astype(np.float32)
+        if k in MATRICES:
+            every = v.size // len(SPECIAL)
+            v.view(np.uint32)[every // 2 + every * np.arange(len(SPECIAL))] = np.array(SPECIAL, np.uint32)
+        else:
+            assert np.all(v != 0)
+        w[k] = v.reshape(shapes[k])
+    if sh.G:
+        w["goal_dim"] = sh.G
+    return w
+
+
+def digest(p):
+    """what the golden file holds of a dict of packed arrays: size and SHA-256 per array"""
+    return {k: dict(bytes=int(v.size), sha256=hashlib.sha256(v.tobytes()).hexdigest()) for k, v in p.items()}
+
+
+def check_golden(lib, case):
+    """a fresh context and np_packed both give the bytes dm_policy_create gave when it still packed on the host"""
+    with open(GOLDEN_FILE) as fh:
+        want = json.load(fh)["cases"][case]
+    sh = SHAPES[case.partition("/")[0]]
+    w = golden_weights(case)
+    assert len(want) == 11 + (1 if sh.fused else 0) + (14 if sh.G else 0)
+    pol = Policy(w, lib_path=lib, s_clip=S_CLIP)
+    got = digest(packed(pol))
+    pol.close()
+    mine = digest(np_packed(w, sh))
+    for k in want:
+        assert got[k] == want[k], "%s: %s of a fresh context is not what the golden file holds" % (case, k)
+        assert mine[k] == want[k], "%s: %s of np_packed is not what the golden file holds" % (case, k)
+    assert got.keys() == want.keys() == mine.keys()
+
+
 def check_refresh(lib, on_gpu, name, mode):
     sh = SHAPES[name]
     wa, wb = weights(name, 1), weights(name, 2)
@@ -153,7 +309,8 @@ def check_refresh(lib, on_gpu, name, mode):
     pa, pb = Policy(wa, lib_path=lib, s_clip=S_CLIP), Policy(wb, lib_path=lib, s_clip=S_CLIP)
     info = pa.info()
     assert (info["K1"], info["N3"], info["fused"], info["gated"]) == (sh.K1, sh.N3, sh.fused, sh.G > 0)
-    want = packed(pb)
+    want = packed_ref(name, 2)
+    assert_same_bytes(packed(pb), want, "%s, created" % name)
     assert len(want) == 11 + (1 if sh.fused else 0) + (14 if sh.G else 0)
     if not sh.fused:
         with pytest.raises(RuntimeError, match="no fused weight stream"):
@@ -185,8 +342,8 @@ def check_partial(lib, on_gpu, name):
     """only logstd and b3 given: those two arrays become B's, every other array keeps A's bytes"""
     wa, wb = weights(name, 1), weights(name, 2)
     side = Side(on_gpu)
-    pa, pb = Policy(wa, lib_path=lib), Policy(wb, lib_path=lib)
-    a_bytes, b_bytes = packed(pa), packed(pb)
+    pa = Policy(wa, lib_path=lib)
+    a_bytes, b_bytes = packed(pa), packed_ref(name, 2)
     side.set(pa, dict(logstd=wb["logstd"], b3=wb["b3"]))
     got = packed(pa)
     assert_same_bytes(got, {k: (b_bytes[k] if k in ("logstd", "b3") else a_bytes[k]) for k in a_bytes}, name)
@@ -200,7 +357,9 @@ def check_partial(lib, on_gpu, name):
             assert np.array_equal(got2[k], b_bytes[k]), k
         elif k != "wfs":
             assert np.array_equal(got2[k], got[k]), k
-    pa.close(); pb.close()
+    # ... and every array, a gated stream's mix of A's gate tiles and B's layers included, is what the layout makes of that mix
+    assert_same_bytes(got2, np_packed({**wa, **{k: wb[k] for k in ("logstd", "b3", "w1", "w2", "w3")}}, SHAPES[name]), name + ", mixed")
+    pa.close()
 
 
 SPECIAL = (0x7FC00000, 0xFFC00001, 0x7F800001, 0x7FFFFFFF,      # NaNs: quiet, signed with a payload, signalling, all ones -> 0x7fc0, every one
@@ -210,7 +369,8 @@ SPECIAL_BF16 = (0x7FC0, 0x7FC0, 0x7FC0, 0x7FC0, 0x3F80, 0x3F82, 0xBF80, 0xBF82, 
 
 
 def check_nan_and_ties(lib, on_gpu, name, mode):
-    """NaNs and exact round-to-even ties in every matrix: the bytes must be the host packer's (P_B, created from the same arrays), and w1p holds the stated codes"""
+    """NaNs and exact round-to-even ties in every matrix: the bytes must be np_packed's, after a refresh and in a context created from the same arrays, and w1p
+    holds the stated codes"""
     sh = SHAPES[name]
     wb = dict(weights(name, 2))
     rng = np.random.default_rng(5)
@@ -223,7 +383,8 @@ def check_nan_and_ties(lib, on_gpu, name, mode):
             wb[k] = m; where[k] = flat
     side = Side(on_gpu)
     pa, pb = Policy(weights(name, 1), lib_path=lib), Policy(wb, lib_path=lib)
-    want = packed(pb)
+    want = np_packed(wb, sh)
+    assert_same_bytes(packed(pb), want, name + ", created")
     w1p = want["w1p"].view(np.uint16)
     for pos, code in zip(where["w1"], SPECIAL_BF16):
         assert w1p[frag_index(pos // sh.H1, pos % sh.H1, sh.K1)] == code
@@ -276,6 +437,11 @@ def check_refusals(lib, on_gpu):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- CPU emulator
+@pytest.mark.parametrize("case", GOLDEN_CASES)
+def test_create_packs_golden_bytes_emulator(emu_lib, case):
+    check_golden(emu_lib, case)
+
+
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name", list(SHAPES))
 def test_set_weights_equals_create_emulator(emu_lib, name, mode):
@@ -297,6 +463,12 @@ def test_set_weights_refusals_emulator(emu_lib):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------- GPU twins
+@pytest.mark.gpu
+@pytest.mark.parametrize("case", GOLDEN_CASES)
+def test_create_packs_golden_bytes_gpu(hip_lib, case):
+    check_golden(hip_lib, case)
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("mode", MODES)
 @pytest.mark.parametrize("name", list(SHAPES))
@@ -368,7 +540,7 @@ def test_set_weights_torch_between_two_forwards_on_one_stream(hip_lib):
     assert np.array_equal(a2.cpu().numpy(), want)
     assert np.abs(a2.cpu().numpy() - new_ref).max() < 2e-3
     assert np.abs(new_ref - old_ref).max() > 2e-2                                           # ... and the two differ by far more than the tolerance
-    assert_same_bytes(packed(pol), packed(fresh), "after set_weights_torch")
+    assert_same_bytes(packed(pol), np_packed(w_new, SHAPES["small"]), "after set_weights_torch")      # (the widths of "small"; no normalisers: the defaults)
     # the argument checks of set_weights_torch
     with pytest.raises(ValueError, match="w1 must be a contiguous float32"):
         pol.set_weights_torch(dict(w1=lin[0].weight.t()), layout="out_in")                  # right shape for in_out, but a transposed view

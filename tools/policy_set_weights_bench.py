@@ -1,7 +1,7 @@
 """What a weight refresh of a device policy costs at the reference widths (S = 197, A = 28, 1024 / 512; plain and gated with goal_dim 3, gate 128 / 64), for
 parameters that live in torch tensors on the GPU in torch.nn.Linear layout ([out, in]):
 
- (a) rebuild: the tensors to the host, dm_policy_destroy + dm_policy_create(_gated) (host packers, a dozen allocations, the upload) and the first forward
+ (a) rebuild: the tensors to the host, dm_policy_destroy + dm_policy_create(_gated) (a dozen allocations, the fp32 arrays staged to the device, one k_policy_pack launch) and the first forward
      afterwards, which regrows the activation buffers behind a stream synchronise -- the only route before dm_policy_set_weights;
  (b) refresh: Policy.set_weights_torch(layout="out_in") and the same forward, enqueued back to back on one stream and timed as ONE event interval, so a host
      synchronisation inside the refresh would show as a gap (host_enqueue_us is the host's time for the two calls; it returns before the work is done).
