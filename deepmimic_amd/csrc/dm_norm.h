@@ -126,7 +126,8 @@ struct dm_normalizer {
     float *mean_f = nullptr, *inv_std_f = nullptr, *stage = nullptr; int stage_rows = 0;
     int *group_id = nullptr, *grp_start = nullptr, *grp_len = nullptr, *grp_idx = nullptr;
     // ONE stream per normaliser: `stage`, `partial` and `pending` are single buffers that every call reuses, ordered only by the stream the calls are issued
-    // on.  The stream of the last record is remembered; a call that arrives on another one first waits for the old stream's work.
+    // on.  The stream of the last call is remembered; a call that arrives on another one first waits for the old stream's work: every entry
+    // point that reads or writes a buffer of the handle goes through order_on (record, update, set, get, normalize, bind).
     rt_stream last_stream = 0; bool used = false;
     void order_on(rt_stream s) { if (used && s != last_stream) rt_sync(last_stream); last_stream = s; used = true; }
     ~dm_normalizer() { for (void* p : {(void*)state, (void*)pending, (void*)partial, (void*)mean_f, (void*)inv_std_f, (void*)stage, (void*)group_id, (void*)grp_start, (void*)grp_len, (void*)grp_idx}) if (p) rt_free(p); }
@@ -220,6 +221,7 @@ int dm_norm_set(dm_normalizer* h, const double* mean, const double* std_, int64_
     if (!h || !mean || !std_) return fail("null argument");
     DevGuard guard(h->device_id);
     rt_stream stream = (rt_stream)hip_stream;
+    h->order_on(stream);                                // (count < 0 reads state[0]: an update() on the old stream has to have written it)
     const int size = h->size;
     // set_mean_std (learning/normalizer.py:79-93): mean_sq = std^2 + mean^2; count < 0 keeps the current count (TFNormalizer.load sets it)
     std::vector<double> st(1 + 3 * (size_t)size); std::vector<float> mf(size), sf(size);
@@ -238,8 +240,10 @@ int dm_norm_get(dm_normalizer* h, double* mean, double* std_, double* mean_sq, i
     if (!h) return fail("null argument");
     DevGuard guard(h->device_id);
     const int size = h->size;
+    rt_stream stream = (rt_stream)hip_stream;
+    h->order_on(stream);
     std::vector<double> st(1 + 3 * (size_t)size);
-    if (rt_d2h(st.data(), h->state, sizeof(double) * st.size(), (rt_stream)hip_stream)) return fail("copy failed");
+    if (rt_d2h(st.data(), h->state, sizeof(double) * st.size(), stream)) return fail("copy failed");
     if (count) *count = (int64_t)st[0];
     if (mean) memcpy(mean, &st[1], sizeof(double) * size);
     if (mean_sq) memcpy(mean_sq, &st[1 + size], sizeof(double) * size);
@@ -255,7 +259,9 @@ int dm_norm_normalize(dm_normalizer* h, const float* x_dev, int n, float* out_de
     if (total > 0x7fffffffLL) return fail("dm_norm_normalize: too many elements for one call");
     const float clip = (h->clip > 0 && std::isfinite(h->clip)) ? (float)h->clip : std::numeric_limits<float>::infinity();
     const int vec_ok = (((uintptr_t)x_dev | (uintptr_t)out_dev) & 15) == 0 ? 1 : 0;
-    RT_LAUNCH4(dmn::k_norm_apply, (int)((total + dmn::kQuads * 4 * dmn::kThreads - 1) / (dmn::kQuads * 4 * dmn::kThreads)), (rt_stream)hip_stream, x_dev, (int)total, h->size, (const float*)h->mean_f, (const float*)h->inv_std_f, clip, out_dev, vec_ok);
+    rt_stream stream = (rt_stream)hip_stream;
+    h->order_on(stream);                                // (mean_f / inv_std_f are written by update() and set())
+    RT_LAUNCH4(dmn::k_norm_apply, (int)((total + dmn::kQuads * 4 * dmn::kThreads - 1) / (dmn::kQuads * 4 * dmn::kThreads)), stream, x_dev, (int)total, h->size, (const float*)h->mean_f, (const float*)h->inv_std_f, clip, out_dev, vec_ok);
 #ifndef DM_EMU
     hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
 #endif
@@ -270,6 +276,7 @@ int dm_policy_bind_obs_normalizer(dm_policy* p, dm_normalizer* h, int first_colu
     if (first_column < 0 || first_column + h->size > p->pd.S) return fail("dm_policy_bind_obs_normalizer: the normaliser's columns do not fit the policy's state_dim");
     if (p->device_id != h->device_id) return fail("dm_policy_bind_obs_normalizer: policy and normaliser live on different devices");
     DevGuard guard(p->device_id);
+    h->order_on((rt_stream)hip_stream);
     float* dm = const_cast<float*>(p->pd.s_mean) + first_column; float* ds = const_cast<float*>(p->pd.s_inv_std) + first_column;
 #ifdef DM_EMU
     memcpy(dm, h->mean_f, sizeof(float) * h->size); memcpy(ds, h->inv_std_f, sizeof(float) * h->size);
