@@ -11,7 +11,8 @@ of `TorchVecEnv.step`:
 Behind a step that is not done stands values[t + 1]; behind a done step val_fail / val_succ (terminate Fail / Succ) or term_values[t] (Null: episode timer,
 clip end).  A window cut at T is bootstrapped from values[T] like a Null end -- the one deviation from the reference, which stores whole paths only.
 `mask` is 0 for the steps of an episode that ended invalid inside the window (the reference's driver discards it).  The arithmetic is fp64 in the
-reference's association with one rounding to fp32.  Advantage (returns - values[:T]), value clipping and advantage normalisation stay the caller's."""
+reference's association with one rounding to fp32.  The advantage (returns - values[:T]), its normalisation, the value clipping and the minibatches
+are `deepmimic_amd.ppo_batch`'s."""
 from __future__ import annotations
 
 import ctypes as C
@@ -65,12 +66,13 @@ def td_lambda_returns_torch(rewards, values, term_values, terminate, done, valid
 
 
 def critic_returns_torch(critic, obs, goals, terminal_obs, terminal_goal, terminate, done, valid, rewards, gamma: float, td_lambda: float,
-                         lib_path: Optional[str] = None):
+                         lib_path: Optional[str] = None, return_values: bool = False):
     """TD(lambda) targets of a stacked rollout straight from a `deepmimic_amd.heads.Critic`: obs [T + 1, N, S] (row T: the observation after the last step),
     goals [T + 1, N, G] or None, terminal_obs [T, N, S] / terminal_goal [T, N, G] (info["terminal_obs"] / info["terminal_goal"] of every step), the flags and
     rewards [T, N].  Two critic launches -- values on obs, and term_values on terminal_obs under row_mask = done, so tiles without a finished episode cost
     nothing -- then dm_td_lambda_returns with the critic's val_fail / val_succ.  The Fail / Succ override is td_lambda_returns' own rule, so the values stay
-    the net's (clipped) output.  Returns (returns [T, N] float32, mask [T, N] int32); all on torch's current stream."""
+    the net's (clipped) output.  Returns (returns [T, N] float32, mask [T, N] int32), and the values [T + 1, N] behind them as a third item if
+    `return_values` (what `ppo_batch.advantages_torch` takes); all on torch's current stream."""
     import torch
     T = int(rewards.shape[0])
     if int(obs.shape[0]) != T + 1:
@@ -78,4 +80,5 @@ def critic_returns_torch(critic, obs, goals, terminal_obs, terminal_goal, termin
     done_i = done.to(torch.int32) if done.dtype == torch.bool else done
     values = critic.eval_torch(obs, goals)
     term_values = critic.eval_torch(terminal_obs, terminal_goal, row_mask=done_i, fill=0.0)
-    return td_lambda_returns_torch(rewards, values, term_values, terminate, done_i, valid, gamma, td_lambda, critic.val_fail, critic.val_succ, lib_path=lib_path)
+    ret, mask = td_lambda_returns_torch(rewards, values, term_values, terminate, done_i, valid, gamma, td_lambda, critic.val_fail, critic.val_succ, lib_path=lib_path)
+    return (ret, mask, values) if return_values else (ret, mask)

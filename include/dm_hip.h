@@ -571,6 +571,43 @@ int dm_td_lambda_returns(int device_id, int T, int N, const float* rewards_dev, 
                          const int32_t* terminate_dev, const int32_t* done_dev, const int32_t* valid_dev, double gamma, double td_lambda,
                          double val_fail, double val_succ, float* returns_dev, int32_t* mask_dev, void* hip_stream);
 
+/* ---- PPO training batches from a device-resident rollout: what PPOAgent._train_step (learning/ppo_agent.py:141-232) does between the returns and the first
+ * optimiser step.  Stateless like dm_td_lambda_returns: DEVICE pointers, time-major T x N arrays addressed by the flat index i = t * N + n, asynchronous on
+ * hip_stream of device device_id, no allocation and no synchronisation inside; a refused call launches nothing.
+ *
+ * dm_ppo_advantages.  returns T x N and mask T x N (NULL: all 1) as dm_td_lambda_returns wrote them; values: the first T rows of its (T + 1) x N values
+ * array; exp_flags T x N as dm_policy_forward_ex wrote them (NULL: every step explored).  Sample i is VALID where mask[i] != 0 and EXP where it is valid and
+ * exp_flags[i] != 0.  All arithmetic is fp64 on the fp32 inputs with one rounding to fp32 at a store:
+ *   counts_out int32[2] = {n_valid, n_exp};  valid_idx_out / exp_idx_out int32[T * N]: the flat indices of the valid / exp samples in ascending order
+ *   (entries from the count on are left untouched);
+ *   stats_out double[2] = {mean, std} of a_i = returns[i] - values[i] over the exp samples: std is the population standard deviation taken in two passes
+ *   (the mean, then the squared deviations; never E[x^2] - E[x]^2); both are 0 when n_exp == 0;
+ *   adv_out T x N = clip((a_i - mean) / (std + adv_eps), -norm_adv_clip, +norm_adv_clip) on exp samples, exactly 0 elsewhere (ppo_agent.py:166-172:
+ *   ADV_EPS = 1e-5, NormAdvClip 5);  targets_out T x N = clip(returns[i], val_min, val_max) for every i (:167; infinite bounds: no clip).
+ * Sums and the compaction go through per-workgroup partials in `workspace` (dm_ppo_workspace_bytes(T, N) bytes, the caller's, 8-byte aligned like
+ * stats_out) folded in a fixed order by further launches: no atomics, no workgroup waits on another one, and two calls on one input are bit-identical.
+ * Refused: T < 1, N < 1, T * N > 2^31 - 1, a NULL pointer other than mask / exp_flags, a workspace that is too small, adv_eps < 0, norm_adv_clip <= 0,
+ * val_min > val_max. */
+int64_t dm_ppo_workspace_bytes(int T, int N);          /* < 0: refused (dm_last_error) */
+int dm_ppo_advantages(int device_id, int T, int N, const float* returns_dev, const float* values_dev, const int32_t* mask_dev, const int32_t* exp_flags_dev,
+                      double adv_eps, double norm_adv_clip, double val_min, double val_max, float* adv_out, float* targets_out, int32_t* valid_idx_out,
+                      int32_t* exp_idx_out, int32_t* counts_out, double* stats_out, void* workspace, int64_t workspace_bytes, void* hip_stream);
+/* dm_ppo_gather: rows of a shuffled pass over one of the two lists, one launch for up to 8 columns.  idx_dev: valid_idx_out or exp_idx_out; count_dev: the
+ * list's DEVICE-resident counter (&counts_out[0] or &counts_out[1]) -- the host never reads it.  A column is a (T * N) x width array of 4-byte elements
+ * (float or int32; width = the product of the trailing dimensions, >= 1) and dst is rows x width.  For j in [0, rows): position p = first + j, pass = p / count,
+ * slot = p % count, source row = idx[perm(count, seed, epoch, pass)(slot)] -- a list shorter than the positions asked of it wraps like np.mod(batch, num_idx)
+ * (ppo_agent.py:186-193), and every wrap and every epoch sees a fresh shuffle (:190, 211).  picked_out int32[rows] (NULL: not wanted) receives the source rows.
+ * count == 0: dst is left untouched and picked_out gets -1.
+ * perm is a keyed bijection on [0, count), evaluated per row (nothing is stored or sorted): k = max(1, bit_length(count - 1)), h = ceil(k / 2), m = 2^h - 1;
+ * x = (L, R) = (x >> h, x & m); six rounds (L, R) <- (R, L xor (F & m)), F = word 0 of Philox4x32-10(counter = (R, round, epoch, pass mod 2^32),
+ * key = (seed & 0xffffffff, seed >> 32)); y = (L << h) | R, and while y >= count the six rounds are applied to y again (deepmimic_amd/ppo_batch.py
+ * reference_permutation is the same in numpy).
+ * Rows are copied as dwords, coalesced; 16 bytes per lane only where src, dst and width * 4 are all multiples of 16.  The source rows are not bounds-checked:
+ * idx must hold row numbers of the columns passed.  Refused: a NULL idx / count / column pointer, first < 0, rows < 1, ncols outside 1 .. 8, width < 1. */
+typedef struct dm_ppo_column { const void* src; void* dst; int32_t width; } dm_ppo_column;
+int dm_ppo_gather(int device_id, const int32_t* idx_dev, const int32_t* count_dev, int64_t first, int rows, uint64_t seed, uint32_t epoch, int ncols,
+                  const dm_ppo_column* cols, int32_t* picked_out, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
