@@ -451,6 +451,13 @@ class BatchEnv:
         self._chk(self.lib.dm_amp_expert(self.h, int(n), _dp(tt), _dp(gh), _fp(o), 0))
         return o
 
+    def amp_expert_draw_device(self, n: int, call: int, out_ptr: int, ground_h_ptr: int = 0, clips_out_ptr: int = 0, times_out_ptr: int = 0):
+        """include/dm_hip.h dm_amp_expert_draw: n expert observations whose clips and clip times are drawn ON THE DEVICE, exactly the draws of `amp_expert` /
+        `amp_expert_clips` at their call `call`; raw device pointers (ints), asynchronous on the ctx stream.  `call` is the caller's counter: the ctx's own is left alone."""
+        vp = lambda p: C.c_void_p(int(p)) if p else None
+        self.lib.dm_amp_expert_draw.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self._chk(self.lib.dm_amp_expert_draw(self.h, int(n), C.c_uint64(int(call) & (2 ** 64 - 1)), vp(ground_h_ptr), vp(out_ptr), vp(clips_out_ptr), vp(times_out_ptr)))
+
     def step_device(self, actions_ptr, states_ptr, rewards_ptr, term_ptr, valid_ptr, end_ptr,
                     timestep: float = 1.0 / 600, n_updates: int = 20, auto_reset=False, open_loop=False, amp_ptr=0, end_early=None):
         """Same as step() on raw device pointers (ints), asynchronous on the ctx stream."""

@@ -361,6 +361,8 @@ struct CtxBase {
     // the ctx's own output buffers: the five step outputs, the AMP observations on request
     StepOut dev_out(bool amp) const { return StepOut{d_states, d_rewards, d_term, d_valid, d_end, amp ? d_amp : nullptr}; }
     int amp_size = 0; float* d_amp = nullptr; uint64_t expert_calls = 0;
+    // dm_amp_expert_draw: the clip tables on the device (setup) and the ctx's scratch for the drawn clip ids / sample times, grown on demand like d_ids
+    const double *d_clip_cdf = nullptr, *d_clip_dur = nullptr; double* d_draw_times = nullptr; int* d_draw_clips = nullptr; int draw_cap = 0;
     int goal_size = 0; float* d_goals = nullptr;            // RecordGoal of the last emit (goal scenes)
     float *term_states = nullptr, *term_goals = nullptr;    // dm_set_terminal_outputs: the caller's device buffers (N x S, N x goal_size) for the rows of envs a DM_AUTO_RESET launch resets; null = unbound
     virtual int goal_state(double* out, const double* in) = 0; virtual int clips(int* out, const int* in) = 0; virtual int need_new_action(int* out) = 0;
@@ -533,6 +535,7 @@ struct CtxT : CtxBase {
         md.num_clips = h.num_clips;
         md.clip_start = up<int>(h.clip_start); md.clip_dur = up<double>(h.clip_dur); md.clip_loop = up<int>(h.clip_loop);
         md.clip_delta = up<Real>(h.clip_delta); md.clip_cdf = up<double>(h.clip_cdf);
+        d_clip_cdf = md.clip_cdf; d_clip_dur = md.clip_dur;
         if (c.scene_goal || h.num_clips > 1 || c.enable_rand_rot_reset) {
             if (!c.scene_amp) return fail("goal scenes, multi-clip datasets and enable_rand_rot_reset ride on the AMP instantiation of the kernels: scene_amp must be set");
             st.goal = (double*)dalloc(sizeof(double) * (size_t)N * GS_WIDTH);
@@ -1439,3 +1442,4 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_norm.h"          // (after dm_scene_load.h: <map>; after dm_policy_host.h: dm_policy)
 #include "dm_returns.h"       // TD(lambda) returns over a device-resident rollout
 #include "dm_ppo_batch.h"     // PPO advantages, sample lists and shuffled minibatch gathers over a device-resident rollout
+#include "dm_replay.h"        // AMP discriminator data: device replay stores and expert draws (after dm_ppo_batch.h: feistel_perm)

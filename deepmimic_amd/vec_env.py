@@ -43,6 +43,7 @@ class TorchVecEnv:
         # the launches go to the caller's CURRENT torch stream (looked up at every call): ordered against the caller's work on both sides
         # without events (torch's default stream has the null handle; BatchEnv.set_stream maps it to the legacy default stream)
         self._stream_handle = None
+        self.expert_draw_calls = 0                                  # amp_expert_draw's own call counter (the context's is the host routes')
 
     def _enter(self):
         h = int(self.torch.cuda.current_stream(self.device).cuda_stream)
@@ -93,6 +94,27 @@ class TorchVecEnv:
             if self.terminal_goal is not None:
                 info["terminal_goal"] = self.terminal_goal
         return self.obs, self.reward, (self.episode_end != 0) | (self.valid == 0), info
+
+    def amp_expert_draw(self, n: int, out=None, return_draws: bool = False):
+        """n expert AMP observations (amp_agent.py:244-249: one per agent observation) whose clips and clip times are drawn on the device, on torch's current
+        stream, no host read: an (n, amp_size) float32 tensor (`out` if given), and with `return_draws` the int32 clip ids and float64 clip times behind it.
+        Call k of this method draws what call k of `BatchEnv.amp_expert` / `amp_expert_clips` draws on a context of the same seed; it keeps its own counter."""
+        t = self.torch
+        n, w = int(n), self.env.amp_size
+        if n < 1:
+            raise ValueError("n must be >= 1")
+        if out is None:
+            out = t.empty((n, w), dtype=t.float32, device=self.device)
+        elif out.device != self.device or out.dtype != t.float32 or not out.is_contiguous() or out.numel() != n * w:
+            raise ValueError("out must be a contiguous float32 (n, amp_size) tensor on %s" % self.device)
+        clips = t.empty(n, dtype=t.int32, device=self.device) if return_draws else None
+        times = t.empty(n, dtype=t.float64, device=self.device) if return_draws else None
+        self._enter()
+        self.env.amp_expert_draw_device(n, self.expert_draw_calls, out.data_ptr(), clips_out_ptr=clips.data_ptr() if return_draws else 0,
+                                        times_out_ptr=times.data_ptr() if return_draws else 0)
+        self._leave()
+        self.expert_draw_calls += 1
+        return (out, clips, times) if return_draws else out
 
     def close(self):
         self.env.close()

@@ -206,6 +206,17 @@ int dm_amp_expert(dm_ctx* ctx, int n, const double* times, const double* ground_
 /* Multi-clip variant (SampleExpertMotion, SceneImitateAMP.cpp:115-138 with a cClipsController): clips[i] = dataset clip of sample i;
  * clips NULL -> drawn by weight (and times ~ U[0, that clip's duration)) from the ctx generator.  Host pointers. */
 int dm_amp_expert_clips(dm_ctx* ctx, int n, const int32_t* clips, const double* times, const double* ground_h, float* out);
+/* The same draws made ON THE DEVICE: n expert observations whose clip ids and sample times a small kernel (k_amp_expert_draw) writes into scratch the context owns
+ * (grown on demand by doubling; only a call that grows it allocates, which waits for the device, and no block -- the outgrown ones included -- is freed before dm_destroy:
+ * after one call with a very large n, 12 bytes per sample of the largest n, at most twice that with the outgrown blocks, stay with the context), consumed by the launch
+ * behind dm_amp_expert_clips.  Every pointer is a device pointer; asynchronous on
+ * the context's current stream, no host read, no synchronisation.  Sample i draws exactly what the host routes draw with their counter at `call`:
+ *   clip: u = rand01(seed, env_id_offset + 0x434C50, call, i) searched in the clip cdf (dm_clip_table); time: clip duration * rand01(seed, env_id_offset + 0x414D50, call, i);
+ *   a single-clip scene draws no clip and its time is the motion's duration * rand01(seed, env_id_offset + 0x414D50, call, i)     (dm_amp_expert with times NULL).
+ * `call` is the CALLER's counter: the context's own counter is neither read nor advanced.  ground_h_dev NULL -> 0.  clips_out_dev int32[n] / times_out_dev double[n]
+ * (either may be NULL) receive the draws.  out_dev n x dm_amp_obs_size().  Refused: a context without AMP observations, n < 1, out_dev NULL. */
+int dm_amp_expert_draw(dm_ctx* ctx, int n, uint64_t call, const double* ground_h_dev /* NULL: 0 */, float* out_dev, int32_t* clips_out_dev /* may be NULL */,
+                       double* times_out_dev /* may be NULL */);
 
 /* ---- goal scenes (dm_scene_tables.scene_goal != 0)
  * RecordGoal for every env (SceneTargetAMP.cpp:195-223 / SceneHeadingAMP.cpp:150-166 / SceneHeadingAMPGetup.cpp:123-130 /
@@ -607,6 +618,35 @@ int dm_ppo_advantages(int device_id, int T, int N, const float* returns_dev, con
 typedef struct dm_ppo_column { const void* src; void* dst; int32_t width; } dm_ppo_column;
 int dm_ppo_gather(int device_id, const int32_t* idx_dev, const int32_t* count_dev, int64_t first, int rows, uint64_t seed, uint32_t epoch, int ncols,
                   const dm_ppo_column* cols, int32_t* picked_out, void* hip_stream);
+
+/* ---- replay stores for the AMP discriminator's data (deepmimic_amd/csrc/dm_replay.h, deepmimic_amd/replay.py): the reference's ReplayBufferRandStorage
+ * (learning/replay_buffer_rand_storage.py; learning/amp_agent.py:70-77, 216-227) on arrays that never leave HBM.  Stateless on the library side: the caller owns
+ * buf [capacity, width] of 4-byte elements (float or int32) and state, an int64[2] = {size, total} on the device; {0, 0} is a cleared store.  Asynchronous on
+ * hip_stream (NULL: the null stream) of device_id, no host read, no atomics; the same (state, seed, call, inputs) give the same bytes.
+ *
+ * dm_replay_append: n = min(*count_dev, max_rows), read on the device (count_dev NULL: n = max_rows; e.g. &counts_out[0] of dm_ppo_advantages with idx_dev =
+ * valid_idx_out).  With old = size and free = capacity - old, list row j < n has the rank q = j when n <= capacity and q = perm(n, seed, call, 0x494E43)(j)
+ * otherwise (a rollout larger than the store keeps a uniformly chosen subset), and goes to the slot
+ *     old + q                                     q < free                  (free slots first)
+ *     perm(old, seed, call, 0x564943)(q - free)   free <= q < capacity      (distinct old rows, as np.random.choice(curr_size, remainder, replace=False))
+ *     nowhere                                     q >= capacity             (dropped)
+ * perm(count, seed, epoch, pass) is the keyed bijection of dm_ppo_gather above.  Source row idx_dev[j] of src_dev (idx_dev NULL: row j) is copied to its slot, and,
+ * when packed_out [max_rows, width] is given, to packed_out[j] for every j < n, dropped rows included (the dense rows a normaliser records).  slots_out int32[max_rows]
+ * (NULL: not wanted) receives the slot, -1 for a dropped row.  Rows j >= n of both outputs are not touched.  All slots of one call are distinct.  The new state,
+ * size = min(old + n, capacity) and total += n, is written by a one-thread launch behind the copy.  Rows are copied as dwords, coalesced; 16 bytes per lane only
+ * where buf, src, packed_out and width * 4 are all multiples of 16.  The source rows are not bounds-checked.
+ *
+ * dm_replay_sample: with size = state[0], destination row r of dst_dev [rows, width] reads slot mulhi32(w, size), w = word 0 of Philox4x32-10(counter =
+ * (r, call, 0x534D50, 0), key = (seed & 0xffffffff, seed >> 32)): with replacement, as np.random.randint(0, curr_size, n).  picked_out int32[rows] (NULL: not
+ * wanted) receives the slots.  size == 0: dst is left untouched and picked_out gets -1.
+ *
+ * Refused: a NULL buf / state / src / dst; capacity, width, max_rows or rows < 1; capacity * width, max_rows * width or rows * width above 2^31 - 1; a pointer that
+ * is not 4-byte aligned; state not 8-byte aligned; no HIP device, or a device_id it does not have. */
+int dm_replay_append(int device_id, void* buf_dev, int capacity, int width, int64_t* state_dev, const void* src_dev, const int32_t* idx_dev /* NULL: row j = j */,
+                     const int32_t* count_dev /* NULL: n = max_rows */, int max_rows, uint64_t seed, uint32_t call, void* packed_out /* NULL, or [max_rows, width] */,
+                     int32_t* slots_out /* NULL, or [max_rows] */, void* hip_stream);
+int dm_replay_sample(int device_id, const void* buf_dev, int width, const int64_t* state_dev, int rows, uint64_t seed, uint32_t call, void* dst_dev /* [rows, width] */,
+                     int32_t* picked_out /* NULL or [rows] */, void* hip_stream);
 
 #ifdef __cplusplus
 }
