@@ -11,6 +11,7 @@ from typing import Optional, Sequence
 
 import numpy as np
 
+from .binding import check, declare, u64, vp
 from .model import AMP_SCENES, BALL_ANG_DAMPING, BALL_FRICTION, BALL_LIN_DAMPING, BALL_MASS, SceneTables
 from .model import amp_local_root as _model_amp_local_root
 
@@ -80,9 +81,7 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         raise RuntimeError("%s does not match this binding (ABI version / struct layout): rebuild with __graft_entry__.build()" % path)
     if lib.dm_is_emulator() and os.environ.get("DM_ALLOW_EMULATOR") != "1":
         raise RuntimeError("%s is the CPU emulator build (test infrastructure); deepmimic_amd runs on the HIP library only" % path)
-    lib.dm_last_error.restype = C.c_char_p
-    lib.dm_motion_duration.restype = C.c_double
-    lib.dm_motion_duration.argtypes = [C.c_void_p]
+    declare(lib)
     _libs[path] = lib
     return lib
 
@@ -222,8 +221,7 @@ class BatchEnv:
                 self.reset()
 
     def _chk(self, rc):
-        if rc != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, rc)
 
     def close(self):
         if getattr(self, "h", None):
@@ -454,9 +452,7 @@ class BatchEnv:
     def amp_expert_draw_device(self, n: int, call: int, out_ptr: int, ground_h_ptr: int = 0, clips_out_ptr: int = 0, times_out_ptr: int = 0):
         """include/dm_hip.h dm_amp_expert_draw: n expert observations whose clips and clip times are drawn ON THE DEVICE, exactly the draws of `amp_expert` /
         `amp_expert_clips` at their call `call`; raw device pointers (ints), asynchronous on the ctx stream.  `call` is the caller's counter: the ctx's own is left alone."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        self.lib.dm_amp_expert_draw.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self._chk(self.lib.dm_amp_expert_draw(self.h, int(n), C.c_uint64(int(call) & (2 ** 64 - 1)), vp(ground_h_ptr), vp(out_ptr), vp(clips_out_ptr), vp(times_out_ptr)))
+        self._chk(self.lib.dm_amp_expert_draw(self.h, int(n), u64(call), vp(ground_h_ptr), vp(out_ptr), vp(clips_out_ptr), vp(times_out_ptr)))
 
     def step_device(self, actions_ptr, states_ptr, rewards_ptr, term_ptr, valid_ptr, end_ptr,
                     timestep: float = 1.0 / 600, n_updates: int = 20, auto_reset=False, open_loop=False, amp_ptr=0, end_early=None):
@@ -464,7 +460,6 @@ class BatchEnv:
         end_early = auto_reset if end_early is None else end_early
         self._check_auto_reset(auto_reset)
         flags = DM_DEVICE_PTRS | (DM_AUTO_RESET if auto_reset else 0) | (DM_OPEN_LOOP if open_loop else 0) | (DM_END_EPISODE_EARLY if end_early else 0)
-        vp = lambda p: C.c_void_p(p) if p else None
         if amp_ptr:
             self._chk(self.lib.dm_step_batch_amp(self.h, vp(actions_ptr), C.c_double(timestep), int(n_updates), vp(states_ptr),
                                                  vp(rewards_ptr), vp(term_ptr), vp(valid_ptr), vp(end_ptr), vp(amp_ptr), flags))
@@ -476,7 +471,6 @@ class BatchEnv:
         """include/dm_hip.h dm_set_terminal_outputs: bind device buffers (raw pointers: N x S float32, and N x G float32 for a goal scene) that every
         auto-reset launch fills, for the envs it resets, with RecordState / RecordGoal of the moment the episode ended; (0, 0) unbinds.  Rows of envs that
         were not reset are left alone.  The caller keeps the buffers alive while they are bound."""
-        vp = lambda p: C.c_void_p(int(p)) if p else None
         self._chk(self.lib.dm_set_terminal_outputs(self.h, vp(term_states_ptr), vp(term_goals_ptr)))
 
     def set_stream(self, stream_handle: int):
@@ -588,8 +582,6 @@ class RefRand:
 
     def __init__(self, seed: int = 0, lib_path: Optional[str] = None):
         self.lib = load_library(lib_path)
-        for f in ("dm_refrand_double", "dm_refrand_exp", "dm_refrand_norm"):
-            getattr(self.lib, f).restype = C.c_double
         self.h = C.c_void_p()
         if self.lib.dm_refrand_create(C.c_ulong(int(seed) & (2 ** 64 - 1)), C.byref(self.h)) != 0:
             raise RuntimeError("dm_refrand_create failed")
@@ -667,16 +659,14 @@ class Comm:
         self.lib = load_library(lib_path)
         self.h = C.c_void_p()
         uid = None if unique_id is None else C.create_string_buffer(bytes(unique_id), 128)
-        if self.lib.dm_comm_create(uid, int(world), int(rank), int(device_id), C.byref(self.h)) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_comm_create(uid, int(world), int(rank), int(device_id), C.byref(self.h)))
         self.world, self.rank = world, rank
 
     @staticmethod
     def unique_id(lib_path: Optional[str] = None) -> bytes:
         lib = load_library(lib_path)
         buf = C.create_string_buffer(128)
-        if lib.dm_comm_unique_id(buf) != 0:
-            raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+        check(lib, lib.dm_comm_unique_id(buf))
         return buf.raw
 
     def gather(self, env: "BatchEnv", slot: int, send_ptr: int, recv_ptr: int, count: int):

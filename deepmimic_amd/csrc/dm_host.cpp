@@ -20,7 +20,7 @@
 #include <string>
 #include <random>
 #include <sstream>
-#include <limits>
+#include <initializer_list>
 #include <vector>
 
 #include "../../include/dm_hip.h"
@@ -84,6 +84,22 @@ static int launch_status(int rc) {
     return le == hipSuccess ? 0 : fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
 }
 #endif
+// what an entry point that takes a device_id checks before its DevGuard; `who`: its name, for the message
+static int valid_device(const char* who, int device_id) {
+#ifndef DM_EMU
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
+    if (device_id < 0 || device_id >= ndev) return fail(std::string(who) + ": invalid device_id");
+#endif
+    (void)who; (void)device_id;
+    return 0;
+}
+// rows of `width` 4-byte elements may be copied 16 bytes per lane: every row of every array starts on a 16-byte boundary (a null base counts as aligned)
+static int rows_vec16(int width, std::initializer_list<const void*> bases) {
+    uintptr_t all = 0;
+    for (const void* b : bases) all |= (uintptr_t)b;
+    return ((all & 15) == 0 && width % 4 == 0) ? 1 : 0;
+}
 
 // ---------------------------------------------------------------- host-side (double) model description
 enum { JD_TYPE = 0, JD_PARENT, JD_AX, JD_AY, JD_AZ, JD_ATX, JD_ATY, JD_ATZ, JD_LL0, JD_LL1, JD_LL2, JD_LH0, JD_LH1, JD_LH2,
@@ -904,11 +920,7 @@ int dm_create(const dm_create_info* info, const dm_scene_tables* tables, dm_ctx*
 
     int mc = info->max_contacts > 0 ? info->max_contacts : 20;
     if (mc > 20) return fail("max_contacts must be <= 20");
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (info->device_id < 0 || info->device_id >= ndev) return fail("invalid device_id");
-#endif
+    if (valid_device("dm_create", info->device_id)) return -1;
     DevGuard guard(info->device_id);
     CtxBase* c = (precision == 64) ? (CtxBase*)new CtxT<double>() : (CtxBase*)new CtxT<float>();
     c->device_id = info->device_id; c->N = info->num_envs; c->seed = info->seed; c->precision = precision; c->max_contacts = mc; c->env_off = info->env_id_offset;
@@ -1228,11 +1240,10 @@ int dm_bench_rollout(dm_ctx* ctx, int warmup, int steps, double timestep, int n_
     float ms = 0; HIPCHK(hipEventElapsedTime(&ms, e0, e1));
     (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
     if (elapsed_ms) *elapsed_ms = ms;
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
 #else
     if (elapsed_ms) *elapsed_ms = 0;
 #endif
-    return 0;
+    return launch_status(0);
 }
 
 // ---------------------------------------------------------------- the reference's random generator (host side, N = 1 drop-in route)

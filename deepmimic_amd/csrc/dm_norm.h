@@ -139,11 +139,7 @@ int dm_norm_create(int device_id, int size, const int32_t* group_ids, double eps
     if (!out) return fail("null argument");
     if (size < 1 || size > (1 << 20)) return fail("dm_norm_create: size out of range");
     if (!(eps > 0)) return fail("dm_norm_create: eps must be positive (learning/normalizer.py: 0.02)");
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail("invalid device_id");
-#endif
+    if (valid_device("dm_norm_create", device_id)) return -1;
     DevGuard guard(device_id);
     // groups (learning/normalizer.py:124-139): NULL ids = one NORM_GROUP_SINGLE group; members of a group id > 0 in index order
     std::vector<int> gid(size, 0), gs(size, 0), gl(size, 0), gi;
@@ -193,10 +189,7 @@ int dm_norm_record(dm_normalizer* h, const float* x, int n, int flags, void* hip
     if (nb > h->partial_blocks) { rt_sync(stream); if (h->partial) rt_free(h->partial); h->partial = nullptr; h->partial_blocks = 0; void* p = nullptr; if (rt_malloc(&p, sizeof(double) * (size_t)nb * 2 * h->size)) return fail("device allocation failed"); h->partial = (double*)p; h->partial_blocks = nb; }
     RT_LAUNCH4(dmn::k_norm_partial, nb, stream, xd, n, h->size, rows_per_group, h->partial);
     RT_LAUNCH(dmn::k_norm_fold, 2 * h->size, stream, (const double*)h->partial, nb, n, h->size, h->pending);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    return 0;
+    return launch_status(0);
 }
 
 int dm_norm_pending(dm_normalizer* h, double** dev_ptr, int* len) {
@@ -211,10 +204,7 @@ int dm_norm_update(dm_normalizer* h, void* hip_stream) {
     rt_stream stream = (rt_stream)hip_stream;
     h->order_on(stream);
     RT_LAUNCH4(dmn::k_norm_update, 1, stream, h->state, h->pending, h->size, (const int*)h->group_id, (const int*)h->grp_start, (const int*)h->grp_len, (const int*)h->grp_idx, h->eps, h->mean_f, h->inv_std_f);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    return 0;
+    return launch_status(0);
 }
 
 int dm_norm_set(dm_normalizer* h, const double* mean, const double* std_, int64_t count, void* hip_stream) {
@@ -262,10 +252,7 @@ int dm_norm_normalize(dm_normalizer* h, const float* x_dev, int n, float* out_de
     rt_stream stream = (rt_stream)hip_stream;
     h->order_on(stream);                                // (mean_f / inv_std_f are written by update() and set())
     RT_LAUNCH4(dmn::k_norm_apply, (int)((total + dmn::kQuads * 4 * dmn::kThreads - 1) / (dmn::kQuads * 4 * dmn::kThreads)), stream, x_dev, (int)total, h->size, (const float*)h->mean_f, (const float*)h->inv_std_f, clip, out_dev, vec_ok);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    return 0;
+    return launch_status(0);
 }
 
 // columns [first_column, first_column + size) of the policy's observation normaliser := this one (device-to-device, ordered on hip_stream): the actor then

@@ -200,11 +200,7 @@ static int policy_create(int device_id, const dm_policy_params* pp, const dm_pol
         if (!gp->gc_w || !gp->gc_b || !gp->g0_w || !gp->g0_b || !gp->g0_bias_w || !gp->g0_bias_b || !gp->g0_scale_w || !gp->g0_scale_b ||
             !gp->g1_w || !gp->g1_b || !gp->g1_bias_w || !gp->g1_bias_b || !gp->g1_scale_w || !gp->g1_scale_b) return fail("dm_policy_create_gated: null gate weights");
     }
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail("invalid device_id");
-#endif
+    if (valid_device(gp ? "dm_policy_create_gated" : "dm_policy_create", device_id)) return -1;
     DevGuard guard(device_id);
     dm_policy* p = new dm_policy(); p->device_id = device_id;
     dmp::PolicyDev& d = p->pd; memset(&d, 0, sizeof(d));

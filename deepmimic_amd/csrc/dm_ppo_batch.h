@@ -207,6 +207,10 @@ DMP_DEV uint32_t feistel_perm(uint32_t x, uint32_t count, uint32_t seed_lo, uint
 }
 
 struct alignas(16) Q4 { uint32_t x, y, z, w; };  // one 16-byte load / store
+// one wavefront copies a tile of n = rows * w elements (dwords, or 16-byte quads): element e is column e % w of tile row e / w, read from source row srow[.]
+template <typename E> DMP_DEV void gather_tile(const E* src, E* dst, const int* srow, unsigned w, unsigned n, unsigned l) {
+    for (unsigned e = l; e < n; e += 64u) { const unsigned r = e / w; dst[e] = src[(size_t)srow[r] * w + (e - r * w)]; }
+}
 struct GatherCol { const uint32_t* src; uint32_t* dst; int width, vec; };      // vec: both bases and width * 4 are multiples of 16
 struct GatherArgs {
     const int* idx; const int* count; long long first; int rows; uint32_t seed_lo, seed_hi, epoch; int ncols; int* picked;
@@ -233,14 +237,12 @@ __global__ void __launch_bounds__(64) k_ppo_gather(GatherArgs g) {
     if (count <= 0) return;
     for (int c = 0; c < g.ncols; ++c) {
         const GatherCol col = g.col[c];
-        if (col.vec) {                            // 16 bytes per lane; element e of the tile = quad (e % w4) of tile row e / w4
-            const unsigned w4 = (unsigned)col.width / 4u, n = (unsigned)nr * w4;
-            const Q4* src = reinterpret_cast<const Q4*>(col.src); Q4* dst = reinterpret_cast<Q4*>(col.dst) + (size_t)j0 * w4;
-            for (unsigned e = (unsigned)l; e < n; e += 64u) { const unsigned r = e / w4; dst[e] = src[(size_t)srow[r] * w4 + (e - r * w4)]; }
+        if (col.vec) {                            // 16 bytes per lane
+            const unsigned w4 = (unsigned)col.width / 4u;
+            gather_tile(reinterpret_cast<const Q4*>(col.src), reinterpret_cast<Q4*>(col.dst) + (size_t)j0 * w4, srow, w4, (unsigned)nr * w4, (unsigned)l);
         } else {
-            const unsigned w = (unsigned)col.width, n = (unsigned)nr * w;
-            const uint32_t* src = col.src; uint32_t* dst = col.dst + (size_t)j0 * w;
-            for (unsigned e = (unsigned)l; e < n; e += 64u) { const unsigned r = e / w; dst[e] = src[(size_t)srow[r] * w + (e - r * w)]; }
+            const unsigned w = (unsigned)col.width;
+            gather_tile(col.src, col.dst + (size_t)j0 * w, srow, w, (unsigned)nr * w, (unsigned)l);
         }
     }
 }
@@ -267,11 +269,7 @@ int dm_ppo_advantages(int device_id, int T, int N, const float* returns_dev, con
     if (!(val_min <= val_max)) return fail("dm_ppo_advantages: val_min must be <= val_max (infinite bounds: no clipping)");
     if (workspace_bytes < dm_ppo_workspace_bytes(T, N)) return fail("dm_ppo_advantages: workspace too small (dm_ppo_workspace_bytes)");
     if ((((uintptr_t)workspace | (uintptr_t)stats_out) & 7) != 0) return fail("dm_ppo_advantages: workspace and stats_out must be 8-byte aligned");
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail("invalid device_id");
-#endif
+    if (valid_device("dm_ppo_advantages", device_id)) return -1;
     DevGuard guard(device_id);
     dmb::AdvArgs p;
     p.total = T * N; p.returns = returns_dev; p.values = values_dev; p.mask = mask_dev; p.exp_flags = exp_flags_dev;
@@ -284,10 +282,7 @@ int dm_ppo_advantages(int device_id, int T, int N, const float* returns_dev, con
     RT_LAUNCH4(dmb::k_ppo_compact, p.groups, stream, p);
     RT_LAUNCH4(dmb::k_ppo_std, 1, stream, p);
     RT_LAUNCH4(dmb::k_ppo_apply, p.groups, stream, p);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    return 0;
+    return launch_status(0);
 }
 
 int dm_ppo_gather(int device_id, const int32_t* idx_dev, const int32_t* count_dev, int64_t first, int rows, uint64_t seed, uint32_t epoch, int ncols,
@@ -303,22 +298,15 @@ int dm_ppo_gather(int device_id, const int32_t* idx_dev, const int32_t* count_de
         if ((((uintptr_t)cols[c].src | (uintptr_t)cols[c].dst) & 3) != 0) return fail("dm_ppo_gather: columns are arrays of 4-byte elements (misaligned pointer)");
         g.col[c].src = (const uint32_t*)cols[c].src; g.col[c].dst = (uint32_t*)cols[c].dst; g.col[c].width = cols[c].width;
         // 16 bytes per lane only where every row of both arrays starts on a 16-byte boundary (S = 227 rows are 908 B: dwords)
-        g.col[c].vec = ((((uintptr_t)cols[c].src | (uintptr_t)cols[c].dst) & 15) == 0 && cols[c].width % 4 == 0) ? 1 : 0;
+        g.col[c].vec = rows_vec16(cols[c].width, {cols[c].src, cols[c].dst});
     }
     for (int c = ncols; c < dmb::kMaxCols; ++c) { g.col[c].src = nullptr; g.col[c].dst = nullptr; g.col[c].width = 0; g.col[c].vec = 0; }
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail("invalid device_id");
-#endif
+    if (valid_device("dm_ppo_gather", device_id)) return -1;
     DevGuard guard(device_id);
     g.idx = idx_dev; g.count = count_dev; g.first = first; g.rows = rows; g.seed_lo = (uint32_t)(seed & 0xffffffffu); g.seed_hi = (uint32_t)(seed >> 32);
     g.epoch = epoch; g.ncols = ncols; g.picked = picked_out;
     RT_LAUNCH(dmb::k_ppo_gather, (rows + dmb::kGatherRows - 1) / dmb::kGatherRows, (rt_stream)hip_stream, g);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    return 0;
+    return launch_status(0);
 }
 
 }  // extern "C"

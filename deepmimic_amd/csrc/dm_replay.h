@@ -1,6 +1,7 @@
 // The data side of AMP discriminator training on the device: the two random-storage replay buffers of the reference's AMPAgent (learning/amp_agent.py:70-77, 216-227,
 // learning/replay_buffer_rand_storage.py) and the expert draws in front of k_amp_expert (amp_agent.py:244-249).  Included at the end of dm_host.cpp behind dm_ppo_batch.h,
-// whose feistel_perm and runtime shim it uses.
+// whose feistel_perm and gather_tile it uses; the device check, the launch status and the 16-byte rule are the runtime shim's (dm_host.cpp: valid_device, launch_status,
+// rows_vec16).
 //
 // The store is stateless on the library side.  The caller owns buf [capacity, width] of 4-byte elements and state, an int64[2] = {size, total} on the device; {0, 0} is a
 // cleared store.  No atomics, no workgroup waits on another one: every slot is a function of (state, seed, call, list position).
@@ -42,7 +43,7 @@ constexpr uint32_t kPassVictim = 0x564943u, kPassIncoming = 0x494E43u, kCtrSampl
 
 #ifdef DM_EMU
 typedef dmb::Q4 Quad;                            // one 16-byte load / store
-#else
+#else                                            // (not dmb::Q4 on the device: with the struct k_replay_append's unrolled copy allocates registers differently, ~1300 other lines)
 typedef uint32_t Quad __attribute__((ext_vector_type(4)));
 #endif
 
@@ -140,14 +141,12 @@ __global__ void __launch_bounds__(64) k_replay_sample(SampleArgs g) {
     }
     __syncthreads();
     if (size <= 0) return;
-    if (g.vec) {                                  // 16 bytes per lane; element e of the tile = quad (e % w4) of tile row e / w4
-        const unsigned w4 = (unsigned)g.width / 4u, n = (unsigned)nr * w4;
-        const dmb::Q4* src = reinterpret_cast<const dmb::Q4*>(g.buf); dmb::Q4* dst = reinterpret_cast<dmb::Q4*>(g.dst) + (size_t)j0 * w4;
-        for (unsigned e = (unsigned)l; e < n; e += 64u) { const unsigned r = e / w4; dst[e] = src[(size_t)srow[r] * w4 + (e - r * w4)]; }
+    if (g.vec) {                                  // 16 bytes per lane
+        const unsigned w4 = (unsigned)g.width / 4u;
+        dmb::gather_tile(reinterpret_cast<const dmb::Q4*>(g.buf), reinterpret_cast<dmb::Q4*>(g.dst) + (size_t)j0 * w4, srow, w4, (unsigned)nr * w4, (unsigned)l);
     } else {
-        const unsigned w = (unsigned)g.width, n = (unsigned)nr * w;
-        const uint32_t* src = g.buf; uint32_t* dst = g.dst + (size_t)j0 * w;
-        for (unsigned e = (unsigned)l; e < n; e += 64u) { const unsigned r = e / w; dst[e] = src[(size_t)srow[r] * w + (e - r * w)]; }
+        const unsigned w = (unsigned)g.width;
+        dmb::gather_tile(g.buf, g.dst + (size_t)j0 * w, srow, w, (unsigned)nr * w, (unsigned)l);
     }
 }
 
@@ -193,16 +192,6 @@ int dm_amp_expert_draw(dm_ctx* ctx, int n, uint64_t call, const double* ground_h
     return launch_status(c->amp_expert_clips(n, nc > 1 ? c->d_draw_clips : nullptr, c->d_draw_times, ground_h_dev, out_dev));
 }
 
-static int replay_device(const char* who, int device_id) {
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail(std::string(who) + ": invalid device_id");
-#endif
-    (void)who; (void)device_id;
-    return 0;
-}
-
 int dm_replay_append(int device_id, void* buf_dev, int capacity, int width, int64_t* state_dev, const void* src_dev, const int32_t* idx_dev, const int32_t* count_dev,
                      int max_rows, uint64_t seed, uint32_t call, void* packed_out, int32_t* slots_out, void* hip_stream) {
     if (!buf_dev || !state_dev || !src_dev) return fail("dm_replay_append: null argument (only idx, count, packed_out and slots_out may be NULL)");
@@ -214,12 +203,12 @@ int dm_replay_append(int device_id, void* buf_dev, int capacity, int width, int6
     if ((((uintptr_t)buf_dev | (uintptr_t)src_dev | (uintptr_t)packed_out | (uintptr_t)idx_dev | (uintptr_t)count_dev | (uintptr_t)slots_out) & 3) != 0)
         return fail("dm_replay_append: rows, lists and counts are arrays of 4-byte elements (misaligned pointer)");
     if (((uintptr_t)state_dev & 7) != 0) return fail("dm_replay_append: state must be 8-byte aligned");
-    if (replay_device("dm_replay_append", device_id)) return -1;
+    if (valid_device("dm_replay_append", device_id)) return -1;
     DevGuard guard(device_id);
     dmq::AppendArgs a;
     a.buf = (uint32_t*)buf_dev; a.src = (const uint32_t*)src_dev; a.packed = (uint32_t*)packed_out; a.idx = idx_dev; a.count = count_dev; a.state = (const long long*)state_dev;
     a.slots = slots_out; a.capacity = capacity; a.width = width; a.max_rows = max_rows;
-    a.vec = ((((uintptr_t)buf_dev | (uintptr_t)src_dev | (uintptr_t)packed_out) & 15) == 0 && width % 4 == 0) ? 1 : 0;
+    a.vec = rows_vec16(width, {buf_dev, src_dev, packed_out});
     a.seed_lo = (uint32_t)(seed & 0xffffffffu); a.seed_hi = (uint32_t)(seed >> 32); a.call = call;
     rt_stream stream = (rt_stream)hip_stream;
     RT_LAUNCH(dmq::k_replay_append, (max_rows + dmq::kAppendRows - 1) / dmq::kAppendRows, stream, a);
@@ -235,11 +224,11 @@ int dm_replay_sample(int device_id, const void* buf_dev, int width, const int64_
     if ((long long)rows * width > 0x7fffffffLL) return fail("dm_replay_sample: rows * width exceeds 2^31 - 1 elements");
     if ((((uintptr_t)buf_dev | (uintptr_t)dst_dev | (uintptr_t)picked_out) & 3) != 0) return fail("dm_replay_sample: rows are arrays of 4-byte elements (misaligned pointer)");
     if (((uintptr_t)state_dev & 7) != 0) return fail("dm_replay_sample: state must be 8-byte aligned");
-    if (replay_device("dm_replay_sample", device_id)) return -1;
+    if (valid_device("dm_replay_sample", device_id)) return -1;
     DevGuard guard(device_id);
     dmq::SampleArgs g;
     g.buf = (const uint32_t*)buf_dev; g.state = (const long long*)state_dev; g.dst = (uint32_t*)dst_dev; g.picked = picked_out; g.rows = rows; g.width = width;
-    g.vec = ((((uintptr_t)buf_dev | (uintptr_t)dst_dev) & 15) == 0 && width % 4 == 0) ? 1 : 0;
+    g.vec = rows_vec16(width, {buf_dev, dst_dev});
     g.seed_lo = (uint32_t)(seed & 0xffffffffu); g.seed_hi = (uint32_t)(seed >> 32); g.call = call;
     RT_LAUNCH(dmq::k_replay_sample, (rows + dmq::kSampleRows - 1) / dmq::kSampleRows, (rt_stream)hip_stream, g);
     return launch_status(0);

@@ -78,20 +78,13 @@ int dm_td_lambda_returns(int device_id, int T, int N, const float* rewards_dev, 
     if (T < 1 || N < 1) return fail("dm_td_lambda_returns: T and N must be >= 1");
     if (!rewards_dev || !values_dev || !term_values_dev || !terminate_dev || !done_dev || !returns_dev) return fail("dm_td_lambda_returns: null argument (only valid_dev and mask_dev may be NULL)");
     if ((long long)(T + 1) * N > 0x7fffffffLL) return fail("dm_td_lambda_returns: too many elements for one call");
-#ifndef DM_EMU
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail("no HIP device available: libdm_hip.so has no CPU fallback");
-    if (device_id < 0 || device_id >= ndev) return fail("invalid device_id");
-#endif
+    if (valid_device("dm_td_lambda_returns", device_id)) return -1;
     DevGuard guard(device_id);
     dmr::Args a;
     a.T = T; a.N = N; a.rewards = rewards_dev; a.values = values_dev; a.term_values = term_values_dev; a.terminate = terminate_dev; a.done = done_dev; a.valid = valid_dev;
     a.gamma = gamma; a.lambda = td_lambda; a.val_fail = val_fail; a.val_succ = val_succ; a.returns = returns_dev; a.mask = mask_dev;
     RT_LAUNCH(dmr::k_td_lambda, (N + 63) / 64, (rt_stream)hip_stream, a);
-#ifndef DM_EMU
-    hipError_t le = hipGetLastError(); if (le != hipSuccess) return fail(std::string("kernel launch failed: ") + hipGetErrorString(le));
-#endif
-    return 0;
+    return launch_status(0);
 }
 
 }  // extern "C"

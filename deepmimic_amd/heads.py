@@ -18,6 +18,7 @@ from typing import Optional
 
 import numpy as np
 
+from .binding import check, stream_handle, tensor_arg, vp
 from .policy import Policy, is_gated
 
 VALUE, STYLE = 0, 1          # include/dm_hip.h DM_SCALAR_HEAD_VALUE / DM_SCALAR_HEAD_STYLE
@@ -42,8 +43,6 @@ class _ScalarNet:
         self.lib = self.net.lib
         if not hasattr(self.lib, "dm_policy_eval_scalar"):
             raise RuntimeError("libdm_hip: this library has no dm_policy_eval_scalar (rebuild it)")
-        self.lib.dm_policy_eval_scalar.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-        self.lib.dm_policy_scalar_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
         self.device_id, self.S, self.gated = self.net.device_id, self.net.S, self.net.gated
 
     @staticmethod
@@ -56,9 +55,8 @@ class _ScalarNet:
         raise NotImplementedError
 
     def _eval(self, head: _ScalarHead, states_ptr, n, out_ptr, goals_ptr, goal_dim, raw_ptr, stream):
-        vp = lambda p: C.c_void_p(int(p)) if p else None
-        if self.lib.dm_policy_eval_scalar(self.net.h, vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), C.byref(head), vp(out_ptr), vp(raw_ptr), vp(stream)) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_eval_scalar(self.net.h, vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), C.byref(head), vp(out_ptr), vp(raw_ptr),
+                                                       vp(stream)))
 
     def eval_device(self, states_ptr: int, n: int, out_ptr: int, goals_ptr: int = 0, goal_dim: int = 0, raw_ptr: int = 0, row_mask_ptr: int = 0, fill: float = 0.0,
                     stream: int = 0, **rows):
@@ -78,20 +76,15 @@ class _ScalarNet:
                 return None
             if dtype == torch.int32 and x.dtype == torch.bool:
                 x = x.to(torch.int32)
-            want = lead + ((width,) if width is not None else ())
-            if not isinstance(x, torch.Tensor) or x.device != dev or x.dtype != dtype or tuple(x.shape) != want:
-                raise ValueError("%s must be a %s tensor of shape %s on %s" % (name, dtype, want, dev))
-            return x.contiguous()
+            return tensor_arg(name, x, dev, dtype, [lead + ((width,) if width is not None else ())], contiguous=False).contiguous()
         G = 0 if goals is None else int(goals.shape[-1])
         s = flat("states", states, torch.float32, self.S - G); g = flat("goals", goals, torch.float32, G)
         m = flat("row_mask", row_mask, torch.int32)
         per_row = {k + "_ptr": flat(k, v, torch.int32 if k == "terminate" else torch.float32) for k, v in rows.items()}
         out = torch.empty(lead, dtype=torch.float32, device=dev); y = torch.empty(lead, dtype=torch.float32, device=dev) if raw else None
         if n:
-            if stream is None:
-                stream = torch.cuda.current_stream(dev)
             self.eval_device(s.data_ptr(), n, out.data_ptr(), 0 if g is None else g.data_ptr(), G, 0 if y is None else y.data_ptr(), 0 if m is None else m.data_ptr(),
-                             fill, int(getattr(stream, "cuda_stream", stream)), **{k: (0 if t is None else t.data_ptr()) for k, t in per_row.items()})
+                             fill, stream_handle(dev, stream), **{k: (0 if t is None else t.data_ptr()) for k, t in per_row.items()})
         return (out, y) if raw else out
 
     def eval_host(self, states, goals=None, row_mask=None, fill: float = 0.0, **rows):
@@ -109,8 +102,7 @@ class _ScalarNet:
         """dm_policy_scalar_info: the dm_policy_path id that served the last eval (-1 before any), its rows, head kind and whether it was masked; plus the
         context's own dm_policy_info under "net" """
         out = (C.c_int32 * 4)()
-        if self.lib.dm_policy_scalar_info(self.net.h, out) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_scalar_info(self.net.h, out))
         return dict(path=int(out[0]), rows=int(out[1]), kind=int(out[2]), masked=bool(out[3]), net=self.net.info())
 
     # new weights into the live context: the actor's calls on the underlying context (keys of the constructor; a_mean / a_std / logstd do not exist here)

@@ -12,6 +12,7 @@ from typing import Optional
 
 import numpy as np
 
+from .binding import check, stream_handle, tensor_arg, u32, u64, vp
 from .core import load_library
 
 
@@ -55,8 +56,6 @@ class Policy:
 
     def __init__(self, weights: dict, device_id: int = 0, s_clip: float = 0.0, lib_path: Optional[str] = None):
         self.lib = load_library(lib_path)
-        self.lib.dm_policy_forward.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64,
-                                               C.c_uint32, C.c_int, C.c_void_p]
         w = {k: (None if weights.get(k) is None else np.ascontiguousarray(weights[k], dtype=np.float32)) for k in
              ("w1", "b1", "w2", "b2", "w3", "b3", "s_mean", "s_std", "a_mean", "a_std", "logstd")}
         self.S, self.H1 = w["w1"].shape
@@ -88,8 +87,7 @@ class Policy:
             rc = self.lib.dm_policy_create_gated(int(device_id), C.byref(pp), C.byref(gp), C.byref(self.h))
         else:
             rc = self.lib.dm_policy_create(int(device_id), C.byref(pp), C.byref(self.h))
-        if rc != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, rc)
 
     @classmethod
     def from_checkpoint(cls, prefix: str, state_dim: Optional[int] = None, **kw):
@@ -106,22 +104,15 @@ class Policy:
     def forward_device(self, states_ptr: int, n: int, actions_ptr: int, logp_ptr: int = 0, sample: bool = False, seed: int = 0,
                        step: int = 0, env_id_offset: int = 0, stream: int = 0):
         """raw device pointers (e.g. torch.Tensor.data_ptr()); asynchronous on `stream` (a hipStream_t handle, 0 = null stream)."""
-        vp = lambda p: C.c_void_p(p) if p else None
-        if self.lib.dm_policy_forward(self.h, vp(states_ptr), int(n), vp(actions_ptr), vp(logp_ptr), int(bool(sample)),
-                                      C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(step) & 0xFFFFFFFF), int(env_id_offset), vp(stream)) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_forward(self.h, vp(states_ptr), int(n), vp(actions_ptr), vp(logp_ptr), int(bool(sample)), u64(seed), u32(step),
+                                                   int(env_id_offset), vp(stream)))
 
     def forward_device_ex(self, states_ptr: int, n: int, actions_ptr: int, goals_ptr: int = 0, goal_dim: int = 0, logp_ptr: int = 0, exp_flags_ptr: int = 0,
                           exp_rate: float = 1.0, sample: bool = False, seed: int = 0, step: int = 0, env_id_offset: int = 0, stream: int = 0):
         """`_decide_action` of learning/pg_agent.py:214-221 for a batch (include/dm_hip.h dm_policy_forward_ex): goal block as its own input,
         per-row exploration coin with probability `exp_rate`, EXP flags out"""
-        vp = lambda p: C.c_void_p(p) if p else None
-        self.lib.dm_policy_forward_ex.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_double, C.c_int,
-                                                  C.c_uint64, C.c_uint32, C.c_int, C.c_void_p]
-        if self.lib.dm_policy_forward_ex(self.h, vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(actions_ptr), vp(logp_ptr), vp(exp_flags_ptr),
-                                         C.c_double(exp_rate), int(bool(sample)), C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(step) & 0xFFFFFFFF),
-                                         int(env_id_offset), vp(stream)) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_forward_ex(self.h, vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(actions_ptr), vp(logp_ptr), vp(exp_flags_ptr),
+                                                      C.c_double(exp_rate), int(bool(sample)), u64(seed), u32(step), int(env_id_offset), vp(stream)))
 
     def forward_host_ex(self, states, goals=None, exp_rate=1.0, sample=False, seed=0, step=0, env_id_offset=0):
         """emulator-build convenience for forward_device_ex: returns (actions, logp, exp_flags)"""
@@ -145,9 +136,7 @@ class Policy:
         dm_policy_path id and row count of the last forward call (path -1 before any); gated / goal_dim: a gated context and the goal columns its
         gate reads (the launch is then (path, gated)); gated_fused: the fused stream it holds is the gated one (k_policy_fused<.., true>)"""
         out = (C.c_int32 * 8)()
-        self.lib.dm_policy_info.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
-        if self.lib.dm_policy_info(self.h, out) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_info(self.h, out))
         return dict(K1=int(out[0]), N3=int(out[1]), fused=bool(out[2]), path=int(out[3]), rows=int(out[4]), gated=bool(out[5]), goal_dim=int(out[6]),
                     gated_fused=bool(out[7]))
 
@@ -175,9 +164,7 @@ class Policy:
         if self.gated or any(k in ptrs for k in GATE_KEYS):       # (a gate for a plain context: the library refuses it)
             G, GC, GH = self.gate_dims if self.gated else (int(ptrs.get("goal_dim", 0)), 0, 0)
             gp = C.byref(_GateParams(G, GC, GH, *[fp(k) for k in GATE_KEYS]))
-        self.lib.dm_policy_set_weights.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
-        if self.lib.dm_policy_set_weights(self.h, C.byref(pp), gp, int(flags), C.c_void_p(stream) if stream else None) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_set_weights(self.h, C.byref(pp), gp, int(flags), vp(stream)))
 
     def set_weights(self, weights: dict):
         """host arrays under the constructor's keys (and GATE_KEYS); a missing key keeps what the context holds.  Staged through a device temporary; synchronous."""
@@ -207,25 +194,18 @@ class Policy:
                 continue
             if k not in want:
                 raise ValueError("set_weights: unknown key %s" % k)
-            if not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or tuple(t.shape) != want[k] or not t.is_contiguous():
-                raise ValueError("%s must be a contiguous float32 %s tensor on %s" % (k, want[k], dev))
-            ptrs[k] = t.data_ptr()
-        if stream is None:
-            stream = torch.cuda.current_stream(dev)
-        self.set_weights_device(ptrs, layout == "out_in", int(getattr(stream, "cuda_stream", stream)))
+            ptrs[k] = tensor_arg(k, t, dev, torch.float32, [want[k]]).data_ptr()
+        self.set_weights_device(ptrs, layout == "out_in", stream_handle(dev, stream))
 
     def read_packed(self, name: str) -> np.ndarray:
         """the bytes (uint8) of one packed device array as the kernels read it (PACKED_IDS: w1p .. logstd, wfs, gate_*); synchronises the device.
         RuntimeError where the context holds no such array (wfs on widths without the fused kernel, gate_* on a plain context)."""
         if not hasattr(self.lib, "dm_policy_read_packed"):
             raise RuntimeError("libdm_hip: this library has no dm_policy_read_packed (rebuild it)")
-        self.lib.dm_policy_read_packed.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_size_t, C.POINTER(C.c_size_t)]
         n = C.c_size_t(0)
-        if self.lib.dm_policy_read_packed(self.h, PACKED_IDS[name], None, 0, C.byref(n)) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_read_packed(self.h, PACKED_IDS[name], None, 0, C.byref(n)))
         out = np.zeros(n.value, np.uint8)
-        if self.lib.dm_policy_read_packed(self.h, PACKED_IDS[name], out.ctypes.data_as(C.c_void_p), out.nbytes, C.byref(n)) != 0:
-            raise RuntimeError("libdm_hip: %s" % self.lib.dm_last_error().decode())
+        check(self.lib, self.lib.dm_policy_read_packed(self.h, PACKED_IDS[name], out.ctypes.data, out.nbytes, C.byref(n)))
         return out
 
     def close(self):

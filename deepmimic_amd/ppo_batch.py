@@ -22,6 +22,7 @@ from typing import Optional
 
 import numpy as np
 
+from .binding import check, stream_handle, tensor_arg, u32, u64, vp
 from .core import load_library
 from .streams import philox4x32_10
 
@@ -32,22 +33,11 @@ class _Column(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", C.c_int32)]
 
 
-_ADV_ARGTYPES = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 4 + [C.c_double] * 4 + [C.c_void_p] * 7 + [C.c_int64, C.c_void_p]
-_GATHER_ARGTYPES = [C.c_int, C.c_void_p, C.c_void_p, C.c_int64, C.c_int, C.c_uint64, C.c_uint32, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
-
-
-def _vp(p):
-    return C.c_void_p(int(p)) if p else None
-
-
 def workspace_bytes(T: int, N: int, lib_path: Optional[str] = None) -> int:
     """scratch bytes `advantages_device` needs at this shape (the caller allocates them, 8-byte aligned)"""
     lib = load_library(lib_path)
-    lib.dm_ppo_workspace_bytes.restype = C.c_int64
-    lib.dm_ppo_workspace_bytes.argtypes = [C.c_int, C.c_int]
     n = lib.dm_ppo_workspace_bytes(int(T), int(N))
-    if n < 0:
-        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+    check(lib, n < 0)
     return int(n)
 
 
@@ -56,27 +46,21 @@ def advantages_device(T: int, N: int, returns_ptr: int, values_ptr: int, mask_pt
                       workspace_ptr: int, workspace_nbytes: int, stream: int = 0, device_id: int = 0, lib_path: Optional[str] = None):
     """Raw device pointers (ints; mask_ptr and exp_flags_ptr may be 0), asynchronous on the HIP stream `stream` (0 = the null stream) of `device_id`."""
     lib = load_library(lib_path)
-    lib.dm_ppo_advantages.argtypes = _ADV_ARGTYPES
-    rc = lib.dm_ppo_advantages(int(device_id), int(T), int(N), _vp(returns_ptr), _vp(values_ptr), _vp(mask_ptr), _vp(exp_flags_ptr), float(adv_eps),
-                               float(norm_adv_clip), float(val_min), float(val_max), _vp(adv_ptr), _vp(targets_ptr), _vp(valid_idx_ptr), _vp(exp_idx_ptr),
-                               _vp(counts_ptr), _vp(stats_ptr), _vp(workspace_ptr), int(workspace_nbytes), _vp(stream))
-    if rc != 0:
-        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+    check(lib, lib.dm_ppo_advantages(int(device_id), int(T), int(N), vp(returns_ptr), vp(values_ptr), vp(mask_ptr), vp(exp_flags_ptr), float(adv_eps),
+                                      float(norm_adv_clip), float(val_min), float(val_max), vp(adv_ptr), vp(targets_ptr), vp(valid_idx_ptr), vp(exp_idx_ptr),
+                                      vp(counts_ptr), vp(stats_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
 
 
 def gather_device(idx_ptr: int, count_ptr: int, first: int, rows: int, seed: int, epoch: int, columns, picked_ptr: int = 0, stream: int = 0, device_id: int = 0,
                   lib_path: Optional[str] = None):
     """`columns`: a sequence of (src_ptr, dst_ptr, width) -- src a [T * N, width] array of 4-byte elements, dst [rows, width]; one launch for all of them."""
     lib = load_library(lib_path)
-    lib.dm_ppo_gather.argtypes = _GATHER_ARGTYPES
     columns = list(columns)
     cols = (_Column * max(1, len(columns)))()
     for c, (src, dst, width) in zip(cols, columns):
         c.src, c.dst, c.width = (int(src) or None), (int(dst) or None), int(width)
-    rc = lib.dm_ppo_gather(int(device_id), _vp(idx_ptr), _vp(count_ptr), int(first), int(rows), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                           C.c_uint32(int(epoch) & 0xFFFFFFFF), len(columns), C.cast(cols, C.c_void_p), _vp(picked_ptr), _vp(stream))
-    if rc != 0:
-        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+    check(lib, lib.dm_ppo_gather(int(device_id), vp(idx_ptr), vp(count_ptr), int(first), int(rows), u64(seed), u32(epoch), len(columns), C.cast(cols, C.c_void_p),
+                                  vp(picked_ptr), vp(stream)))
 
 
 class PPOBatch:
@@ -119,7 +103,7 @@ class PPOBatch:
         src = torch.empty(int(rows), dtype=torch.int32, device=dev) if picked else None
         k = 0 if which == "valid" else 1
         gather_device((self.valid_idx, self.exp_idx)[k].data_ptr(), self.counts.data_ptr() + 4 * k, first, rows, seed, epoch, cols,
-                      picked_ptr=src.data_ptr() if picked else 0, stream=int(torch.cuda.current_stream(dev).cuda_stream), device_id=dev.index or 0,
+                      picked_ptr=src.data_ptr() if picked else 0, stream=stream_handle(dev), device_id=dev.index or 0,
                       lib_path=self.lib_path)
         return outs + [src] if picked else outs
 
@@ -150,16 +134,11 @@ def advantages_torch(returns, values, mask=None, exp_flags=None, adv_eps: float 
     dev = returns.device
     if dev.type != "cuda":
         raise ValueError("advantages_torch needs GPU tensors (deepmimic_amd has no CPU path)")
-
-    def check(name, x, shapes, dtype):
-        if x.device != dev or x.dtype != dtype or tuple(x.shape) not in shapes or not x.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, " or ".join(str(s) for s in shapes), dev))
-
-    check("returns", returns, [(T, N)], torch.float32); check("values", values, [(T, N), (T + 1, N)], torch.float32)
+    tensor_arg("returns", returns, dev, torch.float32, [(T, N)]); tensor_arg("values", values, dev, torch.float32, [(T, N), (T + 1, N)])
     if mask is not None:
-        check("mask", mask, [(T, N)], torch.int32)
+        tensor_arg("mask", mask, dev, torch.int32, [(T, N)])
     if exp_flags is not None:
-        check("exp_flags", exp_flags, [(T, N)], torch.int32)
+        tensor_arg("exp_flags", exp_flags, dev, torch.int32, [(T, N)])
     adv = torch.empty((T, N), dtype=torch.float32, device=dev); targets = torch.empty((T, N), dtype=torch.float32, device=dev)
     valid_idx = torch.empty(T * N, dtype=torch.int32, device=dev); exp_idx = torch.empty(T * N, dtype=torch.int32, device=dev)
     counts = torch.empty(2, dtype=torch.int32, device=dev); stats = torch.empty(2, dtype=torch.float64, device=dev)
@@ -168,7 +147,7 @@ def advantages_torch(returns, values, mask=None, exp_flags=None, adv_eps: float 
     advantages_device(T, N, returns.data_ptr(), values.data_ptr(), mask.data_ptr() if mask is not None else 0,
                       exp_flags.data_ptr() if exp_flags is not None else 0, adv_eps, norm_adv_clip, val_min, val_max, adv.data_ptr(), targets.data_ptr(),
                       valid_idx.data_ptr(), exp_idx.data_ptr(), counts.data_ptr(), stats.data_ptr(), work.data_ptr(), nbytes,
-                      stream=int(torch.cuda.current_stream(dev).cuda_stream), device_id=dev.index or 0, lib_path=lib_path)
+                      stream=stream_handle(dev), device_id=dev.index or 0, lib_path=lib_path)
     return PPOBatch(adv, targets, valid_idx, exp_idx, counts, stats, lib_path=lib_path)
 
 

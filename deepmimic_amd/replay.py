@@ -11,45 +11,30 @@ Slots are a function of (state, seed, call, list position) alone: no atomics, th
 is the only call that synchronises.  `reference_append_slots` and `reference_sample_slots` are the numpy statements the tests hold the kernels to."""
 from __future__ import annotations
 
-import ctypes as C
 import math
 from typing import Optional
 
 import numpy as np
 
+from .binding import check, stream_handle, u32, u64, vp
 from .core import load_library
 from .ppo_batch import reference_permutation
 from .streams import philox4x32_10
 
 PASS_VICTIM, PASS_INCOMING, CTR_SAMPLE = 0x564943, 0x494E43, 0x534D50          # dm_replay.h kPassVictim, kPassIncoming, kCtrSample
 
-_APPEND_ARGTYPES = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-_SAMPLE_ARGTYPES = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_uint64, C.c_uint32, C.c_void_p, C.c_void_p, C.c_void_p]
-
-
-def _vp(p):
-    return C.c_void_p(int(p)) if p else None
-
-
 def append_device(buf_ptr: int, capacity: int, width: int, state_ptr: int, src_ptr: int, idx_ptr: int, count_ptr: int, max_rows: int, seed: int, call: int,
                   packed_ptr: int = 0, slots_ptr: int = 0, stream: int = 0, device_id: int = 0, lib_path: Optional[str] = None):
     """Raw device pointers (ints; idx_ptr, count_ptr, packed_ptr and slots_ptr may be 0), asynchronous on the HIP stream `stream` (0 = the null stream) of `device_id`."""
     lib = load_library(lib_path)
-    lib.dm_replay_append.argtypes = _APPEND_ARGTYPES
-    rc = lib.dm_replay_append(int(device_id), _vp(buf_ptr), int(capacity), int(width), _vp(state_ptr), _vp(src_ptr), _vp(idx_ptr), _vp(count_ptr), int(max_rows),
-                              C.c_uint64(int(seed) & (2 ** 64 - 1)), C.c_uint32(int(call) & 0xFFFFFFFF), _vp(packed_ptr), _vp(slots_ptr), _vp(stream))
-    if rc != 0:
-        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+    check(lib, lib.dm_replay_append(int(device_id), vp(buf_ptr), int(capacity), int(width), vp(state_ptr), vp(src_ptr), vp(idx_ptr), vp(count_ptr), int(max_rows),
+                                     u64(seed), u32(call), vp(packed_ptr), vp(slots_ptr), vp(stream)))
 
 
 def sample_device(buf_ptr: int, width: int, state_ptr: int, rows: int, seed: int, call: int, dst_ptr: int, picked_ptr: int = 0, stream: int = 0, device_id: int = 0,
                   lib_path: Optional[str] = None):
     lib = load_library(lib_path)
-    lib.dm_replay_sample.argtypes = _SAMPLE_ARGTYPES
-    rc = lib.dm_replay_sample(int(device_id), _vp(buf_ptr), int(width), _vp(state_ptr), int(rows), C.c_uint64(int(seed) & (2 ** 64 - 1)),
-                              C.c_uint32(int(call) & 0xFFFFFFFF), _vp(dst_ptr), _vp(picked_ptr), _vp(stream))
-    if rc != 0:
-        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+    check(lib, lib.dm_replay_sample(int(device_id), vp(buf_ptr), int(width), vp(state_ptr), int(rows), u64(seed), u32(call), vp(dst_ptr), vp(picked_ptr), vp(stream)))
 
 
 class DeviceReplayStore:
@@ -74,9 +59,6 @@ class DeviceReplayStore:
         self.state = torch.zeros(2, dtype=torch.int64, device=self.device)
         self.append_calls = self.sample_calls = 0
 
-    def _stream(self):
-        return int(self.torch.cuda.current_stream(self.device).cuda_stream)
-
     def append(self, src, idx=None, count=None, max_rows=None, packed=None, slots: bool = False):
         """Rows of `src` (contiguous, leading shape [T, N] or [rows]) go into the store on torch's current stream.  idx: int32 list of source rows (None: row j = j);
         count: int32 tensor of one element on the device, the length of the list (None: max_rows); max_rows: the most rows the call can take (None: len(idx), or
@@ -100,7 +82,7 @@ class DeviceReplayStore:
         out = t.full((max_rows,), -1, dtype=t.int32, device=self.device) if slots else None
         append_device(self.buf.data_ptr(), self.capacity, self.width, self.state.data_ptr(), src.data_ptr(), idx.data_ptr() if idx is not None else 0,
                       count.data_ptr() if count is not None else 0, max_rows, self.seed, self.append_calls, packed_ptr=packed.data_ptr() if packed is not None else 0,
-                      slots_ptr=out.data_ptr() if slots else 0, stream=self._stream(), device_id=self.device.index or 0, lib_path=self.lib_path)
+                      slots_ptr=out.data_ptr() if slots else 0, stream=stream_handle(self.device), device_id=self.device.index or 0, lib_path=self.lib_path)
         self.append_calls += 1
         return out
 
@@ -123,7 +105,7 @@ class DeviceReplayStore:
             raise ValueError("out must be a contiguous %s tensor of [rows, width] on %s" % (self.dtype, self.device))
         src = t.empty(rows, dtype=t.int32, device=self.device) if picked else None
         sample_device(self.buf.data_ptr(), self.width, self.state.data_ptr(), rows, self.seed, self.sample_calls, out.data_ptr(), picked_ptr=src.data_ptr() if picked else 0,
-                      stream=self._stream(), device_id=self.device.index or 0, lib_path=self.lib_path)
+                      stream=stream_handle(self.device), device_id=self.device.index or 0, lib_path=self.lib_path)
         self.sample_calls += 1
         return (out, src) if picked else out
 

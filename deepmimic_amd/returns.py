@@ -15,12 +15,10 @@ reference's association with one rounding to fp32.  The advantage (returns - val
 are `deepmimic_amd.ppo_batch`'s."""
 from __future__ import annotations
 
-import ctypes as C
 from typing import Optional
 
+from .binding import check, stream_handle, tensor_arg, vp
 from .core import load_library
-
-_ARGTYPES = [C.c_int, C.c_int, C.c_int] + [C.c_void_p] * 6 + [C.c_double] * 4 + [C.c_void_p] * 3
 
 
 def td_lambda_returns(T: int, N: int, rewards_ptr: int, values_ptr: int, term_values_ptr: int, terminate_ptr: int, done_ptr: int, valid_ptr: int,
@@ -28,12 +26,8 @@ def td_lambda_returns(T: int, N: int, rewards_ptr: int, values_ptr: int, term_va
                       stream: int = 0, device_id: int = 0, lib_path: Optional[str] = None):
     """Raw device pointers (ints; valid_ptr and mask_ptr may be 0), asynchronous on the HIP stream `stream` (0 = the null stream) of `device_id`."""
     lib = load_library(lib_path)
-    lib.dm_td_lambda_returns.argtypes = _ARGTYPES
-    vp = lambda p: C.c_void_p(int(p)) if p else None
-    rc = lib.dm_td_lambda_returns(int(device_id), int(T), int(N), vp(rewards_ptr), vp(values_ptr), vp(term_values_ptr), vp(terminate_ptr), vp(done_ptr), vp(valid_ptr),
-                                  float(gamma), float(td_lambda), float(val_fail), float(val_succ), vp(returns_ptr), vp(mask_ptr), vp(stream))
-    if rc != 0:
-        raise RuntimeError("libdm_hip: %s" % lib.dm_last_error().decode())
+    check(lib, lib.dm_td_lambda_returns(int(device_id), int(T), int(N), vp(rewards_ptr), vp(values_ptr), vp(term_values_ptr), vp(terminate_ptr), vp(done_ptr), vp(valid_ptr),
+                                         float(gamma), float(td_lambda), float(val_fail), float(val_succ), vp(returns_ptr), vp(mask_ptr), vp(stream)))
 
 
 def td_lambda_returns_torch(rewards, values, term_values, terminate, done, valid, gamma: float, td_lambda: float, val_fail: float, val_succ: float,
@@ -49,19 +43,15 @@ def td_lambda_returns_torch(rewards, values, term_values, terminate, done, valid
         raise ValueError("td_lambda_returns_torch needs GPU tensors (deepmimic_amd has no CPU path)")
     if done.dtype == torch.bool:
         done = done.to(torch.int32)
-
-    def check(name, x, shape, dtype):
-        if x.device != dev or x.dtype != dtype or tuple(x.shape) != shape or not x.is_contiguous():
-            raise ValueError("%s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, dev))
-
-    check("rewards", rewards, (T, N), torch.float32); check("values", values, (T + 1, N), torch.float32); check("term_values", term_values, (T, N), torch.float32)
-    check("terminate", terminate, (T, N), torch.int32); check("done", done, (T, N), torch.int32)
+    f32, i32 = torch.float32, torch.int32
+    tensor_arg("rewards", rewards, dev, f32, [(T, N)]); tensor_arg("values", values, dev, f32, [(T + 1, N)]); tensor_arg("term_values", term_values, dev, f32, [(T, N)])
+    tensor_arg("terminate", terminate, dev, i32, [(T, N)]); tensor_arg("done", done, dev, i32, [(T, N)])
     if valid is not None:
-        check("valid", valid, (T, N), torch.int32)
+        tensor_arg("valid", valid, dev, i32, [(T, N)])
     returns = torch.empty((T, N), dtype=torch.float32, device=dev); mask = torch.empty((T, N), dtype=torch.int32, device=dev)
     td_lambda_returns(T, N, rewards.data_ptr(), values.data_ptr(), term_values.data_ptr(), terminate.data_ptr(), done.data_ptr(),
                       valid.data_ptr() if valid is not None else 0, gamma, td_lambda, val_fail, val_succ, returns.data_ptr(), mask.data_ptr(),
-                      stream=int(torch.cuda.current_stream(dev).cuda_stream), device_id=dev.index or 0, lib_path=lib_path)
+                      stream=stream_handle(dev), device_id=dev.index or 0, lib_path=lib_path)
     return returns, mask
 
 

@@ -11,6 +11,7 @@ from __future__ import annotations
 
 from typing import Dict, Tuple
 
+from .binding import stream_handle, tensor_arg
 from .core import BatchEnv
 from .model import SceneTables
 
@@ -46,7 +47,7 @@ class TorchVecEnv:
         self.expert_draw_calls = 0                                  # amp_expert_draw's own call counter (the context's is the host routes')
 
     def _enter(self):
-        h = int(self.torch.cuda.current_stream(self.device).cuda_stream)
+        h = stream_handle(self.device)
         if h != self._stream_handle:
             self.env.set_stream(h); self._stream_handle = h
 
@@ -77,9 +78,7 @@ class TorchVecEnv:
         cSceneSimChar::CheckValidEpisode failed, a link velocity beyond 100 -- the reference's driver ends and DISCARDS such an episode,
         DeepMimic.py:62-80 / learning/rl_agent.py end_episode; info["valid"] tells the two apart).  A learner that bootstraps across a row with
         done == False can therefore never stitch two episodes together."""
-        t = self.torch
-        if actions.device != self.device or actions.dtype != t.float32 or tuple(actions.shape) != (self.n, self.act_dim) or not actions.is_contiguous():
-            raise ValueError("actions must be a contiguous float32 (N, A) tensor on %s" % self.device)
+        tensor_arg("actions", actions, self.device, self.torch.float32, [(self.n, self.act_dim)])
         self._enter()
         self._launch(actions.data_ptr(), self.updates, True)
         self._leave()
@@ -191,9 +190,7 @@ class TorchVecEnvGroups:
         return self.obs
 
     def _check_actions(self, actions):
-        t = self.torch
-        if actions.device != self.device or actions.dtype != t.float32 or tuple(actions.shape) != (self.n, self.act_dim) or not actions.is_contiguous():
-            raise ValueError("actions must be the contiguous float32 (N, A) tensor of the whole batch on %s" % self.device)
+        tensor_arg("actions", actions, self.device, self.torch.float32, [(self.n, self.act_dim)])       # the whole batch's tensor
 
     def step_group(self, g: int, actions):
         """Control step of group g, asynchronous on `stream(g)`.  `actions`: the WHOLE batch's (N, A) tensor (the group reads its rows) written on

@@ -3,6 +3,8 @@ import ctypes
 import os
 import re
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -10,6 +12,15 @@ def declared_functions():
     src = open(os.path.join(ROOT, "include", "dm_hip.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     return sorted(set(re.findall(r"\b(dm_[a-z_]+)\s*\(", src)))
+
+
+def declared_parameter_counts():
+    """{function: number of parameters} of every prototype in include/dm_hip.h (`(void)` is none)"""
+    src = open(os.path.join(ROOT, "include", "dm_hip.h")).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+    protos = re.findall(r"\b(dm_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src)
+    return {name: 0 if args.strip() in ("", "void") else args.count(",") + 1 for name, args in protos}
 
 
 def test_header_declares_the_boundary():
@@ -29,7 +40,6 @@ def test_create_without_gpu_fails_loudly(hip_lib):
     """No CPU fallback: on a box without a HIP device dm_create must return an error, not compute on the host."""
     import torch
     if torch.cuda.is_available():
-        import pytest
         pytest.skip("a GPU is visible")
     from deepmimic_amd import model
     from deepmimic_amd.core import BatchEnv
@@ -61,3 +71,58 @@ def test_binding_mirrors_the_header_structs(emu_lib, tmp_path):
     lib = core.load_library(emu_lib)
     sizes = (C.c_int32 * 2)()
     assert lib.dm_abi_version() == ver and lib.dm_struct_sizes(sizes) == 0 and (sizes[0], sizes[1]) == (s_info, s_tab)
+
+
+def test_binding_signatures_match_the_header(emu_lib):
+    """deepmimic_amd/binding.py SIGNATURES is written by hand: every name is a prototype of include/dm_hip.h with as many parameters, and load_library has declared
+    it on the library before any Policy / DeviceNormalizer / store exists (a 64-bit address passed as a Python int needs its argtypes from the first call on)"""
+    from deepmimic_amd import binding, core
+    counts = declared_parameter_counts()
+    assert counts["dm_last_error"] == 0 and counts["dm_motion_duration"] == 1 and counts["dm_td_lambda_returns"] == 16        # (the parser)
+    lib = core.load_library(emu_lib)
+    for name, (argtypes, restype) in binding.SIGNATURES.items():
+        assert name in counts, "%s is not declared in include/dm_hip.h" % name
+        assert len(argtypes) == counts[name], "%s: %d argtypes, the header declares %d parameters" % (name, len(argtypes), counts[name])
+        f = getattr(lib, name)
+        assert f.argtypes is not None and list(f.argtypes) == list(argtypes), "%s has no argtypes after load_library" % name
+        if restype is not None:
+            assert f.restype is restype, name
+
+
+@pytest.mark.gpu
+def test_invalid_device_id_is_refused_by_name_gpu(hip_lib):
+    """every learner-side entry point that takes a device_id refuses one that names no device, under its own name and before anything is launched: the output
+    buffers keep their bytes.  One row of width 2 (T = N = 1)."""
+    import numpy as np
+    import torch
+    from deepmimic_amd import ppo_batch as pb
+    from deepmimic_amd import returns as rt
+    from deepmimic_amd.normalizer import DeviceNormalizer
+    from deepmimic_amd.policy import Policy, random_weights
+    f32 = lambda *shape: torch.zeros(shape, device="cuda")
+    i32 = lambda *shape: torch.ones(shape, dtype=torch.int32, device="cuda")
+    sent_f = lambda *shape: torch.full(shape, -77.0, device="cuda")
+    sent_i = lambda *shape: torch.full(shape, -77, dtype=torch.int32, device="cuda")
+    rewards, values, term_values, terminate, done = f32(1, 1), f32(2, 1), f32(1, 1), i32(1, 1), i32(1, 1)
+    returns, mask = sent_f(1, 1), sent_i(1, 1)
+    adv, targets, valid_idx, exp_idx, counts = sent_f(1, 1), sent_f(1, 1), sent_i(1), sent_i(1), sent_i(2)
+    stats = torch.full((2,), -77.0, dtype=torch.float64, device="cuda")
+    nbytes = pb.workspace_bytes(1, 1, hip_lib)
+    work = torch.full(((nbytes + 7) // 8,), -77.0, dtype=torch.float64, device="cuda")
+    idx, count, src, dst = torch.zeros(1, dtype=torch.int32, device="cuda"), i32(1), f32(1, 2), sent_f(1, 2)
+    weights = random_weights(2, 1, H1=64, H2=64)
+    for dev in (-1, torch.cuda.device_count()):
+        with pytest.raises(RuntimeError, match="dm_td_lambda_returns: invalid device_id"):
+            rt.td_lambda_returns(1, 1, rewards.data_ptr(), values.data_ptr(), term_values.data_ptr(), terminate.data_ptr(), done.data_ptr(), 0, 0.95, 0.95, 0.0, 1.0,
+                                 returns.data_ptr(), mask.data_ptr(), device_id=dev, lib_path=hip_lib)
+        with pytest.raises(RuntimeError, match="dm_ppo_advantages: invalid device_id"):
+            pb.advantages_device(1, 1, rewards.data_ptr(), values.data_ptr(), 0, 0, 1e-5, 5.0, -np.inf, np.inf, adv.data_ptr(), targets.data_ptr(), valid_idx.data_ptr(),
+                                 exp_idx.data_ptr(), counts.data_ptr(), stats.data_ptr(), work.data_ptr(), nbytes, device_id=dev, lib_path=hip_lib)
+        with pytest.raises(RuntimeError, match="dm_ppo_gather: invalid device_id"):
+            pb.gather_device(idx.data_ptr(), count.data_ptr(), 0, 1, 1, 0, [(src.data_ptr(), dst.data_ptr(), 2)], device_id=dev, lib_path=hip_lib)
+        with pytest.raises(RuntimeError, match="dm_norm_create: invalid device_id"):
+            DeviceNormalizer(2, device_id=dev, lib_path=hip_lib)
+        with pytest.raises(RuntimeError, match="dm_policy_create: invalid device_id"):
+            Policy(weights, device_id=dev, lib_path=hip_lib)
+    for name, t in dict(returns=returns, mask=mask, adv=adv, targets=targets, valid_idx=valid_idx, exp_idx=exp_idx, counts=counts, stats=stats, work=work, dst=dst).items():
+        assert (t == -77).all(), name
