@@ -565,6 +565,10 @@ struct EnvSim {
         if (l < m.J) {
             if (par < 0) Rl = quat_to_rot(ldq(pose + 3));
             else if (jt == JT_SPHERICAL) { Rl = quat_to_rot(ldq(pose + off)); wl = ld3(vel + off); }
+            // the integrator never wraps a revolute angle, and dm_sincos is measured for |x| <= 1e4 only (dm_math.h).  A joint with limits (every revolute joint of the
+            // shipped characters: tests/test_math_device.py) is held at [lim_lo, lim_hi] by its limit rows, |limit| <= 2 pi, and leaves them by less than one substep
+            // at the velocity clamp, 2 max_ang_vel dt < 1 rad.  A revolute joint WITHOUT limits (lim_lo > lim_hi) is bounded by that clamp alone, 200 rad/s, i.e. inside
+            // the domain for 50 s of one-way spinning; past it dm_sincos degrades smoothly (2^-23 |x| of quadrant slop), it does not fail.
             else if (jt == JT_REVOLUTE) { Rl = rot_z(pose[off]); wl.z = vel[off]; }
         }
         for (int d = 0; d <= m.max_depth; ++d) {

@@ -62,8 +62,12 @@ DM_HD double dm_max(double a, double b) { return fmax(a, b); }
 DM_HD int dm_min(int a, int b) { return a < b ? a : b; }
 DM_HD int dm_max(int a, int b) { return a > b ? a : b; }
 
-// sin and cos together.  fp32: Cody-Waite reduction by pi/2 + fdlibm kernel polynomials (|err| < 1 ulp for |x| < 1e4),
-// ~25 instructions instead of two libm calls; fp64: libm.
+// sin and cos together.  fp32: Cody-Waite reduction by pi/2 + fdlibm kernel polynomials, ~25 instructions instead of two libm calls; fp64: libm.
+// Accuracy of the fp32 version, for |x| <= 1e4 (|k| <= 6400), with u = 2^-24, y the exact sin or cos and r = x - k pi/2 the exact reduced argument:
+//     |err| <= u (2 |y| + 3 |r| + 2 r^2 + |k| 4.5e-8)  <=  5.1 u = 3.1e-7 ABSOLUTE    (tests/test_math_device.py enforces the left form, on the emulator and on gfx950; worst seen 1.39 u on both)
+// (three roundings of the reduction, the first of a value of size |r| + |k| 4.37e-8, and 6e-17 |k| that the three constants leave of pi / 2; the polynomial's last rounding and its inner terms).  It is NOT a bound in
+// ulps of the result: next to a zero of y the term u |k| 4.37e-8 (1.7e-11 at |x| = 1e4) remains, tens of ulps of a result of 1e-5.  Beyond the domain the error
+// grows smoothly -- the quadrant pick x * (2 / pi) is off by 2 u |x|, which lets |r| pass pi / 4 by as much -- until (int)kf is undefined from |x| = 3.4e9 on.
 DM_HD void dm_sincos(double x, double& sn, double& cs) { sn = sin(x); cs = cos(x); }
 DM_HD void dm_sincos(float x, float& sn, float& cs) {
     const float kf = rintf(x * 0.636619772367581343f);
@@ -148,6 +152,10 @@ template <typename T> DM_HD M3<T> rot_y(T th) {
 // rotation vector (axis * angle) of a unit quaternion, angle normalised to [-pi,pi]; zero below `eps` on
 // |sin(theta/2)|.  Same function as cMathUtil::QuaternionToAxisAngle (theta*axis) but evaluated with atan2 so that
 // it stays accurate in fp32 for small angles (2*acos(w) loses all precision there).
+// For w >= 0 the error is relative (a few u of the angle).  For w < 0 it is ABSOLUTE: 2 atan2(s, w) lies in (pi, 2 pi] and the wrap subtracts a rounded 2 pi, so
+// about ulp(2 pi) = 4.8e-7 rad (fp32) remains however small the rotation is -- 17 % of a 3e-6 rad rotation stored with w ~ -1.  Accepted, not standardised away:
+// the caller that matters is the PD error of spd_rhs_pre (dm_device.h), where 5e-7 rad times Kp <= 1000 is 5e-4 N m against torque limits of 50 .. 200, and
+// standardising first would change the bits of every step kernel.  tests/test_math_device.py holds both regimes to their bounds.
 template <typename T> DM_HD V3<T> quat_to_rotvec(const Q4<T>& q, T eps) {
     T s = dm_sqrt(q.x * q.x + q.y * q.y + q.z * q.z);
     if (!(s > eps)) return mk3((T)0, (T)0, (T)0);

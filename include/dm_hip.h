@@ -648,6 +648,37 @@ int dm_replay_append(int device_id, void* buf_dev, int capacity, int width, int6
 int dm_replay_sample(int device_id, const void* buf_dev, int width, const int64_t* state_dev, int rows, uint64_t seed, uint32_t call, void* dst_dev /* [rows, width] */,
                      int32_t* picked_out /* NULL or [rows] */, void* hip_stream);
 
+/* ---- a probe for the device math helpers (deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
+ * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
+ * pointers.  The kernel narrows the inputs the op reads to float (f64 == 0) or keeps them double (f64 != 0), calls the helper in that type, and widens the result
+ * (exact); outputs the op does not produce are written as 0, rows >= n are not touched.  Quaternions are (w, x, y, z), matrices row-major.
+ *     op                       reads                                                    writes
+ *     SINCOS                   x = in[0]                                                sin, cos
+ *     ROT_Y, ROT_Z             angle = in[0]                                            3 x 3
+ *     NORMALIZE_ANGLE          angle = in[0]                                            angle
+ *     QMUL                     a = in[0..3], b = in[4..7]                               a (x) b
+ *     QNORMALIZE, QSTANDARDIZE q = in[0..3]                                             quaternion
+ *     QROT                     q = in[0..3], v = in[4..6]                               vector
+ *     QUAT_TO_ROT              q = in[0..3] (any norm > 0)                              3 x 3
+ *     QUAT_TO_ROTVEC           q = in[0..3], eps = in[4]                                vector
+ *     QUAT_THETA, CALC_HEADING q = in[0..3]                                             angle
+ *     QUAT_EXP, EXP_MAP_TO_QUAT  v = in[0..2]                                           quaternion
+ *     QUAT_DIFF_MUL            q = in[0..3], omega = in[4..6]                           quaternion
+ *     QSLERP                   a = in[0..3], b = in[4..7], t = in[8], one_minus_eps = in[9]   quaternion
+ *     CROSS                    a = in[0..2], b = in[3..5]                               a x b
+ *     CROSS_ADD                c = in[0..2], a = in[3..5], b = in[6..8]                 c + a x b
+ *     M3_V3, TMUL              A = in[0..8], v = in[9..11]                              A v, A^T v
+ *     M3_M3                    A = in[0..8], B = in[9..17]                              A B
+ * It pins the helpers' source as dm_host.o compiles it; the copies inlined into the step kernels are built under other flags (dm_math_probe.h).
+ * Needs no dm_ctx; asynchronous on hip_stream of device device_id.  Refused, nothing is launched: n < 1, a NULL pointer, an op outside [0, DM_MOP_COUNT),
+ * no HIP device or a device_id it does not have. */
+#define DM_MATH_PROBE_IN 18
+#define DM_MATH_PROBE_OUT 12
+enum { DM_MOP_SINCOS = 0, DM_MOP_ROT_Y, DM_MOP_ROT_Z, DM_MOP_NORMALIZE_ANGLE, DM_MOP_QMUL, DM_MOP_QNORMALIZE, DM_MOP_QSTANDARDIZE, DM_MOP_QROT, DM_MOP_QUAT_TO_ROT,
+       DM_MOP_QUAT_TO_ROTVEC, DM_MOP_QUAT_THETA, DM_MOP_QUAT_EXP, DM_MOP_EXP_MAP_TO_QUAT, DM_MOP_QUAT_DIFF_MUL, DM_MOP_QSLERP, DM_MOP_CALC_HEADING, DM_MOP_CROSS,
+       DM_MOP_CROSS_ADD, DM_MOP_M3_V3, DM_MOP_TMUL, DM_MOP_M3_M3, DM_MOP_COUNT };
+int dm_math_probe(int device_id, int op, int f64, int n, const double* in_dev, double* out_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif
