@@ -38,6 +38,8 @@ SIGNATURES = {
     "dm_ppo_gather": ([_i, _p, _p, _i64, _i, _u64, _u32, _i, _p, _p, _p], None),
     "dm_replay_append": ([_i, _p, _i, _i, _p, _p, _p, _p, _i, _u64, _u32, _p, _p, _p], None),
     "dm_replay_sample": ([_i, _p, _i, _p, _i, _u64, _u32, _p, _p, _p], None),
+    "dm_episode_workspace_bytes": ([_i], _i64),
+    "dm_episode_stats": ([_i, _i, _i] + [_p] * 10 + [_i, _i, _p, _i64, _p], None),
     "dm_math_probe": ([_i, _i, _i, _i, _p, _p, _p], None),
 }
 

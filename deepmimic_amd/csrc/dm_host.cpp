@@ -1454,4 +1454,5 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_returns.h"       // TD(lambda) returns over a device-resident rollout
 #include "dm_ppo_batch.h"     // PPO advantages, sample lists and shuffled minibatch gathers over a device-resident rollout
 #include "dm_replay.h"        // AMP discriminator data: device replay stores and expert draws (after dm_ppo_batch.h: feistel_perm)
+#include "dm_episode.h"       // episode returns, lengths and end-cause totals over a device-resident rollout (after dm_ppo_batch.h: its workgroup width and tree)
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs

@@ -13,14 +13,19 @@ from typing import Dict, Tuple
 
 from .binding import stream_handle, tensor_arg
 from .core import BatchEnv
+from .episodes import EpisodeStats, decode_block, merge_blocks
 from .model import SceneTables
 
 
 class TorchVecEnv:
     def __init__(self, tables: SceneTables, num_envs: int, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
-                 updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, **env_kwargs):
+                 updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
+                 episode_bin_steps: int = 1, **env_kwargs):
         """terminal_obs (default on): keep `terminal_obs` / `terminal_goal` tensors bound to the context (BatchEnv.set_terminal_outputs), handed out as
-        info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent."""
+        info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent.
+        episode_stats (default off: no extra launch, no extra key): `step` runs deepmimic_amd.episodes.EpisodeStats.update behind the step launch on the same
+        stream and hands out info["episode_return"] / info["episode_length"]; `episode_totals()` reads the totals (and a length histogram of `episode_bins`
+        bins of `episode_bin_steps` steps)."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -45,6 +50,10 @@ class TorchVecEnv:
         # without events (torch's default stream has the null handle; BatchEnv.set_stream maps it to the legacy default stream)
         self._stream_handle = None
         self.expert_draw_calls = 0                                  # amp_expert_draw's own call counter (the context's is the host routes')
+        self.stats = None
+        if episode_stats:
+            self.stats = EpisodeStats(self.n, self.device, bins=episode_bins, bin_steps=episode_bin_steps, lib_path=env_kwargs.get("lib_path"))
+            self.episode_return = torch.zeros(self.n, **f32); self.episode_length = torch.zeros(self.n, **i32)
 
     def _enter(self):
         h = stream_handle(self.device)
@@ -65,6 +74,8 @@ class TorchVecEnv:
         self.env.reset()
         self._launch(0, 0, False)                                   # RecordState of the reset state, no update
         self._leave()
+        if self.stats is not None:
+            self.stats.reset_carry()                                # episodes in flight are dropped, not counted
         return self.obs
 
     def step(self, actions) -> Tuple["object", "object", "object", Dict[str, "object"]]:
@@ -74,6 +85,8 @@ class TorchVecEnv:
         scene, the goal) such an env had when its episode ended -- the path-end state a critic bootstraps a timer end from, learning/ppo_agent.py:251-266 --
         is info["terminal_obs"] / info["terminal_goal"]: (N, S) / (N, G) tensors whose row i is meaningful where done[i] is set in THIS step (other
         rows keep what an earlier step left there).  deepmimic_amd.returns.td_lambda_returns turns a stacked rollout of these into critic targets.
+        With `episode_stats`, info["episode_return"] / info["episode_length"] are the running return and length of the episode each env's step belongs to, this
+        step included: the finished episode's figures where done[i] is set (deepmimic_amd/episodes.py).
         `done` = every env that was reset inside the launch: episode_end (cDeepMimicCore::IsEpisodeEnd) OR an INVALID episode (valid == 0:
         cSceneSimChar::CheckValidEpisode failed, a link velocity beyond 100 -- the reference's driver ends and DISCARDS such an episode,
         DeepMimic.py:62-80 / learning/rl_agent.py end_episode; info["valid"] tells the two apart).  A learner that bootstraps across a row with
@@ -92,7 +105,17 @@ class TorchVecEnv:
             info["terminal_obs"] = self.terminal_obs
             if self.terminal_goal is not None:
                 info["terminal_goal"] = self.terminal_goal
-        return self.obs, self.reward, (self.episode_end != 0) | (self.valid == 0), info
+        done = (self.episode_end != 0) | (self.valid == 0)
+        if self.stats is not None:
+            self.stats.update(self.reward, self.terminate, done, self.valid, out=(self.episode_return, self.episode_length))
+            info["episode_return"], info["episode_length"] = self.episode_return, self.episode_length
+        return self.obs, self.reward, done, info
+
+    def episode_totals(self) -> dict:
+        """figures of the episodes finished since construction or the last `stats.clear_totals()` (episodes.decode_block): one device-to-host copy"""
+        if self.stats is None:
+            raise RuntimeError("episode_totals needs episode_stats=True")
+        return self.stats.totals()
 
     def amp_expert_draw(self, n: int, out=None, return_draws: bool = False):
         """n expert AMP observations (amp_agent.py:244-249: one per agent observation) whose clips and clip times are drawn on the device, on torch's current
@@ -128,7 +151,8 @@ class TorchVecEnvGroups:
     as in a `TorchVecEnv` of the whole batch (draws are keyed by the global env id; tests/test_vec_env.py)."""
 
     def __init__(self, tables: SceneTables, num_envs: int, groups: int = 2, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
-                 updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, **env_kwargs):
+                 updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
+                 episode_bin_steps: int = 1, **env_kwargs):
         import torch
         from .groups import EnvGroups
         self.torch = torch
@@ -154,6 +178,13 @@ class TorchVecEnvGroups:
             e.set_terminal_outputs(self.terminal_obs[r].data_ptr(), self.terminal_goal[r].data_ptr() if self.terminal_goal is not None else 0)
         # the contexts' own streams (created back to back: distinct hardware queues), visible to torch as external streams
         self.streams = [torch.cuda.ExternalStream(e.own_stream(), device=self.device) for e in self.g.envs]
+        # episode statistics as in TorchVecEnv: one EpisodeStats per group, on its rows of whole-batch carries and on its stream; totals merged in group order
+        self.stats = None
+        if episode_stats:
+            self.episode_return = torch.zeros(self.n, **f32); self.episode_length = torch.zeros(self.n, **i32)
+            self._acc_return = torch.zeros(self.n, dtype=torch.float64, device=self.device); self._acc_len = torch.zeros(self.n, **i32)
+            self.stats = [EpisodeStats(self.g.count[g], self.device, bins=episode_bins, bin_steps=episode_bin_steps,
+                                       lib_path=env_kwargs.get("lib_path"), carry=(self._acc_return[self.rows(g)], self._acc_len[self.rows(g)])) for g in range(self.G)]
 
     def rows(self, g: int) -> slice:
         return self.g.rows(g)
@@ -178,7 +209,14 @@ class TorchVecEnvGroups:
             info["terminal_obs"] = self.terminal_obs[r]
             if self.terminal_goal is not None:
                 info["terminal_goal"] = self.terminal_goal[r]
+        if self.stats is not None:
+            info["episode_return"], info["episode_length"] = self.episode_return[r], self.episode_length[r]
         return info
+
+    def _episode_update(self, g, done):
+        """group g's EpisodeStats.update on its rows; the caller has made `stream(g)` torch's current stream"""
+        r = self.rows(g)
+        self.stats[g].update(self.reward[r], self.terminate[r], done, self.valid[r], out=(self.episode_return[r], self.episode_length[r]))
 
     def reset(self):
         self.g.reset()
@@ -186,6 +224,9 @@ class TorchVecEnvGroups:
         for g in range(self.G):
             self.streams[g].wait_stream(cur)      # reads of self.obs the caller still has queued on its stream come first (write-after-read)
             self._launch(g, 0, 0, False)
+            if self.stats is not None:
+                with self.torch.cuda.stream(self.streams[g]):
+                    self.stats[g].reset_carry()   # episodes in flight are dropped, not counted
         self._join()
         return self.obs
 
@@ -201,6 +242,8 @@ class TorchVecEnvGroups:
         r = self.rows(g)
         with t.cuda.stream(self.streams[g]):
             done = (self.episode_end[r] != 0) | (self.valid[r] == 0)
+            if self.stats is not None:
+                self._episode_update(g, done)
         return self.obs[r], self.reward[r], done, self._info(r)
 
     def _join(self):
@@ -215,8 +258,19 @@ class TorchVecEnvGroups:
         for g in range(self.G):
             self.streams[g].wait_stream(cur)
             self._launch(g, actions.data_ptr(), self.updates, True)
+            if self.stats is not None:
+                r = self.rows(g)
+                with self.torch.cuda.stream(self.streams[g]):
+                    self._episode_update(g, (self.episode_end[r] != 0) | (self.valid[r] == 0))
         self._join()
         return self.obs, self.reward, (self.episode_end != 0) | (self.valid == 0), self._info(slice(None))
+
+    def episode_totals(self) -> dict:
+        """as TorchVecEnv.episode_totals: the groups' blocks merged in group order (the current stream waits for the groups' streams first)"""
+        if self.stats is None:
+            raise RuntimeError("episode_totals needs episode_stats=True")
+        self._join()
+        return decode_block(merge_blocks([s.raw() for s in self.stats]), self.stats[0].bin_steps)
 
     def close(self):
         self.g.close()

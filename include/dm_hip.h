@@ -648,7 +648,45 @@ int dm_replay_append(int device_id, void* buf_dev, int capacity, int width, int6
 int dm_replay_sample(int device_id, const void* buf_dev, int width, const int64_t* state_dev, int rows, uint64_t seed, uint32_t call, void* dst_dev /* [rows, width] */,
                      int32_t* picked_out /* NULL or [rows] */, void* hip_stream);
 
-/* ---- a probe for the device math helpers (deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
+/* ---- episode returns, lengths and end-cause totals over a device-resident rollout (deepmimic_amd/csrc/dm_episode.h, deepmimic_amd/episodes.py): what the reference's
+ * learner logs as Train_Return / Test_Return -- path.calc_return() of the finished, valid paths (learning/path.py:45-46, learning/rl_agent.py:351-365, 456-466); a path
+ * with a non-finite value is never stored (learning/replay_buffer.py:102-112), an invalid episode is discarded by the driver.  Stateless like dm_td_lambda_returns:
+ * DEVICE pointers, time-major T x N arrays (rewards float; terminate, done, valid int32, valid NULL = every episode valid), the caller owns every byte of state,
+ * asynchronous on hip_stream of device device_id, no allocation, no host read and no synchronisation inside; a refused call launches nothing.  T = 1 is the per-step
+ * use, T = the rollout length the per-iteration use.
+ *
+ * Per env column n, forward in time, on the carry acc_return[n] (double) / acc_len[n] (int32), both in/out ({0, 0}: no episode in flight):
+ *   step t:  acc_return += (double)rewards[t] (fp64, in time order, no contraction), acc_len += 1;  then ep_return_out[t] = (float)acc_return and
+ *            ep_len_out[t] = acc_len (each NULL = not wanted): the running return and length of the episode step t belongs to, step t included -- at a done step the
+ *            finished episode's figures; one rounding to fp32, at the store.
+ *   where done[t] != 0 the episode finishes with class c = 3 (invalid) if valid[t] == 0 or acc_return is not finite (an fp64 sum of fp32 rewards is non-finite exactly
+ *            when a reward was: path.check_vals), else c = terminate[t] if that is 1 (Fail) or 2 (Succ), else c = 0 (Null: episode timer, clip end -- the rule of
+ *            dm_td_lambda_returns); then both accumulators of the column go to zero.
+ * After the call the carry holds the accumulators behind step T - 1: an episode that began before the window is counted with what the carry held, one still running
+ * at T stays in the carry and is not counted.
+ *
+ * totals_dev (NULL = not wanted): DM_EP_TOTALS_WORDS 8-byte words, ADDED TO by every call; a window starts from the initial block, all zero bits except
+ * ret_min = +inf and ret_max = -inf.  int64 words: DM_EP_EPISODES + c, DM_EP_STEPS + c (sum of the lengths), DM_EP_LEN_MAX + c for c in 0 .. 3, and
+ * DM_EP_STEPS_SEEN (+= T * N per call).  fp64 words, c in 0 .. 2 only (class 3 keeps counts: its returns may be NaN and are what the reference throws away):
+ * DM_EP_RET_SUM + c, DM_EP_RET_SQ + c (sum of squares), DM_EP_RET_MIN + c, DM_EP_RET_MAX + c, all of the fp64 acc_return, not of the rounded float.
+ * hist_dev (NULL = not wanted; then bins and bin_steps are ignored): int64[bins], added to: a finished episode of class < 3 and length L adds 1 to bin
+ * min((L - 1) / bin_steps, bins - 1).
+ * Each workgroup folds its columns' totals by a fixed tree and writes one partial block to work_dev (dm_episode_workspace_bytes(N) bytes, the caller's); a second
+ * one-workgroup launch behind it folds the partials in workgroup order into totals_dev.  Histogram counts are integer atomic adds.  No floating-point atomic, no
+ * workgroup waits on another one: integer results are exact, every fp64 sum has one order for given (T, N), two calls on the same inputs give the same bytes.  With
+ * totals_dev NULL the second launch is skipped; with totals_dev and hist_dev both NULL work_dev may be NULL.
+ * Refused: T < 1, N < 1, T * N > 2^31 - 1; a NULL rewards / terminate / done / acc_return / acc_len; hist_dev with bins < 1 or bin_steps < 1; totals or a histogram
+ * with work_bytes < dm_episode_workspace_bytes(N); acc_return, totals, hist or (where used) the workspace not 8-byte aligned; no HIP device or a device_id it does not have. */
+enum { DM_EP_EPISODES = 0, DM_EP_STEPS = 4, DM_EP_LEN_MAX = 8, DM_EP_RET_SUM = 12, DM_EP_RET_SQ = 15, DM_EP_RET_MIN = 18, DM_EP_RET_MAX = 21, DM_EP_STEPS_SEEN = 24,
+       DM_EP_TOTALS_WORDS = 25 };
+enum { DM_EP_NULL = 0, DM_EP_FAIL = 1, DM_EP_SUCC = 2, DM_EP_INVALID = 3 };      /* the episode classes c */
+int64_t dm_episode_workspace_bytes(int N);             /* < 0: refused (dm_last_error) */
+int dm_episode_stats(int device_id, int T, int N, const float* rewards_dev, const int32_t* terminate_dev, const int32_t* done_dev,
+                     const int32_t* valid_dev /* NULL: all valid */, double* acc_return_dev /* [N] in/out */, int32_t* acc_len_dev /* [N] in/out */,
+                     float* ep_return_out /* NULL or [T, N] */, int32_t* ep_len_out /* NULL or [T, N] */, void* totals_dev /* NULL or DM_EP_TOTALS_WORDS words, in/out */,
+                     int64_t* hist_dev /* NULL or [bins], in/out */, int bins, int bin_steps, void* work_dev, int64_t work_bytes, void* hip_stream);
+
+/* ---- a probe for the device math helpers(deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
  * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
  * pointers.  The kernel narrows the inputs the op reads to float (f64 == 0) or keeps them double (f64 != 0), calls the helper in that type, and widens the result
  * (exact); outputs the op does not produce are written as 0, rows >= n are not touched.  Quaternions are (w, x, y, z), matrices row-major.
