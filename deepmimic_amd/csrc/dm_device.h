@@ -67,6 +67,8 @@ template <typename T> static inline T dm_med3(T lo, T x, T hi) { return x < lo ?
 // (bit l of MASK) ? a : b for a compile-time lane mask
 template <uint64_t MASK, typename T> static inline T lane_sel(T a, T b, int l, uint64_t) { return ((MASK >> (l & 63)) & 1ull) ? a : b; }
 template <int R, typename T> static inline T row_sel_c(T oldv, T newv, int l, uint32_t) { return l == R ? newv : oldv; }
+// bit J of the 64-bit chain mask (lo, hi) ? v : 0 for a compile-time dof J
+template <int J, typename T> static inline T chain_keep(T v, uint32_t lo, uint32_t hi) { return ((((J < 32) ? lo : hi) >> (J & 31)) & 1u) ? v : (T)0; }
 template <typename Real, int N> struct RowFile {       // per-lane array indexed by a wave-uniform runtime index
     Real v[N];
     inline Real get(int r) const { return v[r]; }
@@ -159,6 +161,15 @@ template <uint64_t MASK> __device__ __forceinline__ float lane_sel(float a, floa
     return out;
 }
 template <uint64_t MASK> __device__ __forceinline__ double lane_sel(double a, double b, int l, uint64_t) { return ((MASK >> (l & 63)) & 1ull) ? a : b; }
+// bit J of the per-lane 64-bit chain mask (lo, hi) ? v : 0 for a compile-time dof J.  fp32: the bit, sign-extended to a word (v_bfe_i32), ANDed onto the
+// value's bits (v & 0 is +0.0f, what the select stores): two VALU and no VCC round trip, against v_and + v_cmp_ne + v_cndmask and the wait states behind the
+// VCC write.  The field extract is an asm: written in C++ (shift pair or sbfe builtin) the optimizer canonicalises `sext(bit) & v` back into compare + select.
+template <int J> __device__ __forceinline__ float chain_keep(float v, uint32_t lo, uint32_t hi) {
+    int keep;
+    asm("v_bfe_i32 %0, %1, %2, 1" : "=v"(keep) : "v"((J < 32) ? lo : hi), "n"(J & 31));
+    return __int_as_float(__float_as_int(v) & keep);
+}
+template <int J> __device__ __forceinline__ double chain_keep(double v, uint32_t lo, uint32_t hi) { return ((((J < 32) ? lo : hi) >> (J & 31)) & 1u) ? v : 0.0; }
 // lane R takes `newv`: the select mask is an SGPR pair made on the scalar unit from `one` (s_lshl + s_mov) instead of a v_cmp; `one` is
 // re-made opaque per sweep, or the 64 masks are hoisted out of the iteration loop and spilled (then every row reloads its pair by v_readlane)
 template <int R> __device__ __forceinline__ float row_sel_c(float oldv, float newv, int, uint32_t one) {
@@ -723,9 +734,7 @@ struct EnvSim {
                 if constexpr (j < ND) {
                     const R4 r0 = da[p & 1][c]; const R2 r1 = db[p & 1][c];
                     v = r0[0] * Lq.x + r0[1] * Lq.y + r0[2] * Lq.z + r0[3] * Pm.x + r1[0] * Pm.y + r1[1] * Pm.z;
-                    if (j == k) v += dk;
-                    const bool on = (((j < 32) ? lo : hi) >> (j & 31)) & 1u;
-                    v = on ? v : (Real)0;
+                    v = chain_keep<j>(v, lo, hi);
                     DM_OPAQUE_V(v);
                 }
                 v2[c] = v;
@@ -733,6 +742,12 @@ struct EnvSim {
             if (2 * p <= k) *reinterpret_cast<R2*>(&row[2 * p]) = v2;
             DM_SCHED_FENCE();      // one pair per scheduling region (without the fence: profiles/r06_ab_lds_lookahead.json)
         });
+        // the diagonal term: the lane adds Kd dt to its own entry H_kk once, behind the loop (the chain bit of j == k is always set, so the word stored above is the
+        // unmasked dot product and this is the add on the operands `if (j == k) v += dk` had inside the loop, at 3 VALU for each of the 34 entries of every lane).
+        // In every phase, dk == 0 included: the stored word is the result of the same add.  LDS operations of one wave complete in order and the sync() of the
+        // caller follows.  dk is pinned as the rounded product it was inside the loop: left to the optimizer, `row[k] + diag_scale * kd` contracts into one v_fmac.
+        Real dkr = dk; DM_OPAQUE_V(dkr);
+        row[k] = row[k] + dkr;
         } else {
 #pragma unroll
         for (int p = 0; p < NP2; ++p) {

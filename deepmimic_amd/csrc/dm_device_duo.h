@@ -512,18 +512,24 @@ struct DuoSim {
         sync();
     }
 #endif
-    DM_DEV void dynamics(int iset, Real diag_scale) {
+    // recs_in_place: the caller states that dofrec[k][0..5] of THIS pose stand (built by the dynamics() of the same R and p; nothing else writes those words: word 6 is
+    // v*, word 7 the bias force) -- the two divergent passes over the dof kinds are skipped.  DuoSim::update says so for its first substep, which runs at the pose of its
+    // stable-PD phase.  After a park inside the update loop (k_env_step_duo: kin_pre(false) behind park) the next dynamics() is a phase-0 call, which rebuilds the
+    // records: a skipped pass never meets records of another pose.
+    DM_DEV void dynamics(int iset, Real diag_scale, bool recs_in_place = false) {
         const int D = m.D;
 #ifndef DM_EMU
         if constexpr (sizeof(Real) == 4) {
-            subtree_mfma(iset);
-            for (int k = hl; k < D; k += HW) b.dyn_dofrec(k);
-            sync();
+            subtree_mfma(iset);                                             // (ends with a sync())
+            if (!recs_in_place) {
+                for (int k = hl; k < D; k += HW) b.dyn_dofrec(k);
+                sync();
+            }
         } else
 #endif
         {
             b.dyn_links(iset);
-            for (int k = hl; k < D; k += HW) b.dyn_dofrec(k);
+            if (!recs_in_place) for (int k = hl; k < D; k += HW) b.dyn_dofrec(k);
             sync();
             b.dyn_subtree();
             sync();
@@ -624,8 +630,18 @@ _Pragma("unroll") \
         // rows 3..33 in order, statically expanded: the lane id of each broadcast is an immediate (DPP form of half_bcast_c).  The
         // entries of the own row on and right of the diagonal are zeroed once, so a step is mul, broadcast, FMA for every lane -- no
         // per-step lane compares -- and the lane's own scaling by 1/L_kk moves behind the loop (row k is final once step k is reached)
-#pragma unroll
-        for (int p = 0; p < NP2; ++p) { if (!(2 * p < own)) h2[p][0] = 0; if (!(2 * p + 1 < own)) h2[p][1] = 0; }
+        // (own = hl + 3: entry j of the row is kept by the lanes hl > j - 3 of either half, a compile-time lane mask -- the form of back_substitute's column, against
+        // a compare of the lane-dependent `own` per entry.  Lane 31 of a half owns no row and keeps its zeros either way.)
+        {
+            uint64_t z = 0; DM_OPAQUE_S(z);
+            static_for<0, ND>([&](auto jc) {
+                constexpr int j = decltype(jc)::value;
+                if constexpr (j >= 3) {
+                    constexpr uint64_t keep = (~((1ull << (j - 2)) - 1ull)) & 0xffffffffull;
+                    h2[j >> 1][j & 1] = lane_sel<(keep << 32) | keep>(h2[j >> 1][j & 1], (Real)0, wl, z);
+                }
+            });
+        }
 #define DM_DUO_FWD(k) { const Real xk = half_bcast_c<(k) - 3>(x * dinv, half); x -= h2[(k) >> 1][(k) & 1] * xk; }
         static_assert(ND == 34, "the expansion below covers rows 3..33");
         DM_DUO_FWD(3) DM_DUO_FWD(4) DM_DUO_FWD(5) DM_DUO_FWD(6) DM_DUO_FWD(7) DM_DUO_FWD(8) DM_DUO_FWD(9) DM_DUO_FWD(10)
@@ -1051,15 +1067,14 @@ _Pragma("unroll") \
 #pragma unroll
                 for (int p = 0; p < NP2X; ++p) DM_OPAQUE_V(y2[p]);
                 duo_gram32<NP2X>(y2, g);
-#pragma unroll
-                for (int r = 0; r < 32; ++r) arow.set(r, g[r] * inv_adiag);
+                // Row r of A scaled, with the diagonal zeroed (see below) by the select of the lambda update: an immediate SGPR-pair mask, one VALU per row
+                uint32_t one0 = 1u; DM_OPAQUE_S(one0);
+                static_for<0, 32>([&](auto rc) { constexpr int r = decltype(rc)::value; arow.set(r, half_sel_c<r>(g[r] * inv_adiag, (Real)0, hl, one0)); });
             }
             b.mark(10);
             // Projected Gauss-Seidel on t = lambda + q (the pre-clamp target of a row): visiting row r leaves t_r unchanged
             // (A_rr = 1 after the row scaling) and moves every other t_c by -A_cr delta, so with a zeroed diagonal the column
             // update is one uniform FMA and the row's own `lambda + q` add disappears.
-#pragma unroll
-            for (int r = 0; r < 32; ++r) if (hl == r) arow.set(r, (Real)0);
             Real t = (brow - cvec) * inv_adiag;
             Real fric = m.friction; DM_OPAQUE_S(fric);
             const int nrm_lane = is_fric ? NL + ((hl - RN) >> 1) : 0;
@@ -1069,9 +1084,13 @@ _Pragma("unroll") \
             const int Ra = lane_bcast(R, 0), Rb = lane_bcast(R, 32);
             int Rv = Ra > Rb ? Ra : Rb, lv = hl;
             uint32_t fmask = (1u << lane_bcast(RN, 0)) | (1u << lane_bcast(RN, 32));
+            // the row at which this lane refreshes its friction bounds (none for the other rows' lanes).  The sweep compares an opaque copy: of a loop-invariant
+            // `is_fric && r == RN` the compiler evaluates all 32 rows in front of the iteration loop (32 v_cmp + 32 s_and_b64, 64 SGPRs of masks, half of them spilled
+            // to VGPR lanes) for blocks of which at most two run per sweep
+            const int rn_fric = is_fric ? RN : -1;
 #define DM_DUO_PGS_ROW(r)                                                                                              \
             {                                                                                                          \
-                if (__builtin_expect((fmask >> (r)) & 1u, 0)) { const Real ln = wave_shfl(lam, half * 32 + nrm_lane); if (is_fric && (r) == RN) { if constexpr (C::OBJ) hi = mu_row * ln; else hi = fric * ln; lo = -hi; } } \
+                if (__builtin_expect((fmask >> (r)) & 1u, 0)) { const Real ln = wave_shfl(lam, half * 32 + nrm_lane); if (rnf == (r)) { if constexpr (C::OBJ) hi = mu_row * ln; else hi = fric * ln; lo = -hi; } } \
                 const Real nl = dm_med3(lo, t, hi);                                                                    \
                 const Real delta = half_bcast_c<(r)>(nl - lam, half);                                                  \
                 t -= arow.get(r) * delta;                                                                              \
@@ -1086,7 +1105,8 @@ _Pragma("unroll") \
             if (Rv > kPrioSweepHi) dm_setprio<3>(); else if (Rv > kPrioSweepLo) dm_setprio<kPrioSweepMid>(); else dm_setprio<kPrioSweepBase>();
             for (int it = 0; it < m.solver_iters; ++it) {
                 uint32_t one = 1u;
-                DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one);
+                int rnf = rn_fric;
+                DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one); DM_OPAQUE_V(rnf);
                 DM_DUO_PGS_BLK(0) DM_DUO_PGS_BLK(1) DM_DUO_PGS_BLK(2) DM_DUO_PGS_BLK(3)
                 DM_DUO_PGS_BLK(4) DM_DUO_PGS_BLK(5) DM_DUO_PGS_BLK(6) DM_DUO_PGS_BLK(7)
             }
@@ -1149,7 +1169,7 @@ _Pragma("unroll") \
                 prio_low();
             }
             b.mark(ph == 0 ? 1 : 5);
-            dynamics(ph == 0 ? 0 : 1, ph == 0 ? rdt : (Real)0);
+            dynamics(ph == 0 ? 0 : 1, ph == 0 ? rdt : (Real)0, ph == 1);      // (ph 1: the records of phase 0's pose)
             b.mark(ph == 0 ? 2 : 6);
             if (ph == 0) {
                 b.spd_rhs_pre(rdt);
