@@ -1088,29 +1088,47 @@ _Pragma("unroll") \
             // `is_fric && r == RN` the compiler evaluates all 32 rows in front of the iteration loop (32 v_cmp + 32 s_and_b64, 64 SGPRs of masks, half of them spilled
             // to VGPR lanes) for blocks of which at most two run per sweep
             const int rn_fric = is_fric ? RN : -1;
-#define DM_DUO_PGS_ROW(r)                                                                                              \
+#define DM_DUO_PGS_ROW(r, TESTED)                                                                                      \
             {                                                                                                          \
-                if (__builtin_expect((fmask >> (r)) & 1u, 0)) { const Real ln = wave_shfl(lam, half * 32 + nrm_lane); if (rnf == (r)) { if constexpr (C::OBJ) hi = mu_row * ln; else hi = fric * ln; lo = -hi; } } \
+                if constexpr (TESTED) if (__builtin_expect((fmask >> (r)) & 1u, 0)) { const Real ln = wave_shfl(lam, half * 32 + nrm_lane); if (rnf == (r)) { if constexpr (C::OBJ) hi = mu_row * ln; else hi = fric * ln; lo = -hi; } } \
                 const Real nl = dm_med3(lo, t, hi);                                                                    \
                 const Real delta = half_bcast_c<(r)>(nl - lam, half);                                                  \
                 t -= arow.get(r) * delta;                                                                              \
                 lam = half_sel_c<(r)>(lam, nl, lv, one);                                                               \
             }
-#define DM_DUO_PGS_BLK(b4) if ((b4) * 4 < Rv) { DM_DUO_PGS_ROW((b4) * 4) DM_DUO_PGS_ROW((b4) * 4 + 1) DM_DUO_PGS_ROW((b4) * 4 + 2) DM_DUO_PGS_ROW((b4) * 4 + 3) }
+#define DM_DUO_PGS_ROW4(b4, TESTED) DM_DUO_PGS_ROW((b4) * 4, TESTED) DM_DUO_PGS_ROW((b4) * 4 + 1, TESTED) DM_DUO_PGS_ROW((b4) * 4 + 2, TESTED) DM_DUO_PGS_ROW((b4) * 4 + 3, TESTED)
+            // (a block past the pair's rows ends the iteration: the blocks behind it need no test of their own)
+#define DM_DUO_PGS_BLK(b4) if ((b4) * 4 >= Rv) break; DM_DUO_PGS_ROW4(b4, ((HOT >> ((b4) >> 1)) & 1u) != 0)
             // Wave priority by load while the sweep runs (round 4, profiles/r04_ab_setprio.json: +3.0 % on the headline, outputs bit-identical): the sweep
             // is one dependent chain per row that issues little; raised above the SIMD's other wave it stops waiting behind that wave's throughput
             // phases, and a pair with more rows than the median (16) -- the waves a one-round launch waits for -- outranks a lighter one.
             // The priority is per wave and lasts until it is set back after the sweep.  (Keeping it through all phases, thresholds 10..24,
             // or 3 for every wave measured the same or less; a never-raised control build measured +-0.)
             if (Rv > kPrioSweepHi) dm_setprio<3>(); else if (Rv > kPrioSweepLo) dm_setprio<kPrioSweepMid>(); else dm_setprio<kPrioSweepBase>();
-            for (int it = 0; it < m.solver_iters; ++it) {
-                uint32_t one = 1u;
-                int rnf = rn_fric;
-                DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one); DM_OPAQUE_V(rnf);
-                DM_DUO_PGS_BLK(0) DM_DUO_PGS_BLK(1) DM_DUO_PGS_BLK(2) DM_DUO_PGS_BLK(3)
-                DM_DUO_PGS_BLK(4) DM_DUO_PGS_BLK(5) DM_DUO_PGS_BLK(6) DM_DUO_PGS_BLK(7)
-            }
+            // The refresh rows of a pair are the same in every iteration, so which visits need the refresh test is decided once per sweep, not once per visit: the
+            // sweep is instantiated per set HOT of 8-row groups whose visits carry the test (bit g: rows 8 g .. 8 g + 7), and the
+            // visits of the other groups issue no scalar test and no branch.  A not-taken s_cbranch costs this wave about 20 cycles, not the 4 of its issue slot
+            // (tools/sweep_visit_probe.hip, profiles/sweep_visit_probe.json).  A choice per block of four inside the iteration costs more than it saves: NOTES.md.
+            // The copies made opaque at the top of each iteration stay (NOTES.md: without them the compiler hoists 32 masks and 32 predicates out of the loop).
+            auto sweep = [&](auto hotc) {
+                constexpr unsigned HOT = decltype(hotc)::value;
+                for (int it = 0; it < m.solver_iters; ++it) {
+                    uint32_t one = 1u;
+                    int rnf = rn_fric;
+                    DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one); DM_OPAQUE_V(rnf);
+                    do {
+                        DM_DUO_PGS_BLK(0) DM_DUO_PGS_BLK(1) DM_DUO_PGS_BLK(2) DM_DUO_PGS_BLK(3)
+                        DM_DUO_PGS_BLK(4) DM_DUO_PGS_BLK(5) DM_DUO_PGS_BLK(6) DM_DUO_PGS_BLK(7)
+                    } while (0);
+                }
+            };
+            // (the biped + free body classes keep the one all-tested instantiation: with four loop copies their spilled VGPRs rise from 18 to 30)
+            if (C::OBJ || (fmask >> 16) != 0u) sweep(std::integral_constant<unsigned, 0xFu>());
+            else if ((fmask & 0xFFu) != 0u && (fmask & 0xFF00u) != 0u) sweep(std::integral_constant<unsigned, 0x3u>());
+            else if ((fmask & 0xFF00u) != 0u) sweep(std::integral_constant<unsigned, 0x2u>());
+            else sweep(std::integral_constant<unsigned, 0x1u>());
 #undef DM_DUO_PGS_BLK
+#undef DM_DUO_PGS_ROW4
 #undef DM_DUO_PGS_ROW
             dm_setprio<kPrioChain>();
             if (hl >= R) lam = 0;
