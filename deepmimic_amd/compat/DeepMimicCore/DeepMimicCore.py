@@ -40,6 +40,7 @@ if _ROOT not in sys.path:
     sys.path.insert(0, _ROOT)
 
 from deepmimic_amd import model as _model  # noqa: E402
+from deepmimic_amd import time_warp as _time_warp  # noqa: E402
 from deepmimic_amd.core import BatchEnv as _BatchEnv  # noqa: E402
 from deepmimic_amd.core import RefRand as _RefRand  # noqa: E402
 
@@ -305,15 +306,11 @@ class cDeepMimicCore(object):
     # env state at every action boundary; the stepping kernels do not know about it
     def _build_time_warper(self):
         self._tw = None
-        c = self._tables.cfg
-        if c.scene != "imitate_amp" or not getattr(c, "enable_test_time_warp", True):
+        size = _time_warp.buffer_size(self._tables.cfg, self._tables.query_rate)      # None: BuildTimeWarper builds none (scene, flag, no finite episode length)
+        if size is None:
             return
-        ends = [x for x in (c.time_lim_max, c.time_end_lim_max) if x is not None]
-        max_time = max(ends) if ends else np.inf
-        if not np.isfinite(max_time):
-            return                                                   # BuildTimeWarper only builds it for a finite episode length
         # (multi-clip datasets since round 4: the kinematic side is the clip the env was reset to, cClipsController's active motion)
-        self._tw = {"size": int(np.ceil(self._tables.query_rate * max_time)) + 2, "sim": [], "kin": [], "samplers": {}}
+        self._tw = {"size": size, "sim": [], "kin": [], "samplers": {}}
 
     def _tw_sample(self, st=None):
         if self._tw is None or self._mode != self.eModeTest:

@@ -3083,6 +3083,50 @@ __global__ void __launch_bounds__(64) k_amp_expert(ModelDev<Real> m, const doubl
     } else sim.amp_expert(times[b], ground_h ? (Real)ground_h[b] : (Real)0, o);
 }
 
+// One sample of the test-mode time-warp score of `--scene imitate_amp` per env (cSceneImitateAMP::UpdateTimeWarper / BuildTimeWarpData, scenes/SceneImitateAMP.cpp:
+// 417-480): the joint world positions (cKinTree::CalcJointPos = s.p[j] after kinematics()) of the simulated and of the kinematic character, root-relative, the root's
+// own slot holding (0, root height, 0).  The caller owns the state (include/dm_hip.h dm_time_warp_sample): samples [N][2][capacity][3J] (0 sim, 1 kin), count[N] and
+// one overflow word.  restart (null: every env) != 0: the env's buffer starts over with TWO identical rows -- ResetTimeWarper adds one, and the PreUpdate of the
+// first update behind a reset one more, NeedNewAction being true there.  A row past `capacity` is not written: count stays, the overflow word is set (the reference
+// throws in cDynamicTimeWarper::AddSample0).  Reads the env record only; the kinematic side is the env's own clip of a multi-clip dataset, as in k_amp_expert.
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_time_warp_sample(ModelDev<Real> m, EnvState<Real> st, Real* samples, int* count, const int* restart, int capacity, int* overflow) {
+    __shared__ Lds<Real, C> lds;
+    const int e = blockIdx.x, l = threadIdx.x;
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.load(st, e);
+    const int dim = 3 * m.J;
+    const bool fresh = !restart || restart[e] != 0;
+    int n = fresh ? 0 : count[e];
+    n = n < 0 ? 0 : (n > capacity ? capacity : n);
+    const int reps = fresh ? 2 : 1;
+    Real* blk = samples + (size_t)e * 2 * capacity * dim;
+    for (int side = 0; side < 2; ++side) {
+        if (side == 0) sim.kinematics(lds.pose, lds.vel, sim.zero3());
+        else {
+            Real* kp = sim.scratch(); Real* kv = kp + C::NP;
+            if (st.goal && m.num_clips > 1) {
+                const ModelDev<Real> mc = sim.model_of_clip((int)st.goal[(size_t)e * GS_WIDTH + GS_CLIP]);
+                EnvSim<Real, C> cs(mc, lds, l);
+                cs.li = sim.li;
+                cs.kin_sample(lds.clk[CLK_KIN], kp, kv);
+            } else sim.kin_sample(lds.clk[CLK_KIN], kp, kv);
+            sim.kinematics(kp, kv, sim.zero3());
+        }
+        if (l < m.J) {
+            const V3<Real> root = ld3(lds.p[0]);
+            const V3<Real> v = (l == 0) ? mk3((Real)0, root.y, (Real)0) : ld3(lds.p[l]) - root;
+            for (int r = 0; r < reps; ++r)
+                if (n + r < capacity) st3(blk + ((size_t)side * capacity + n + r) * dim + 3 * l, v);
+        }
+        sim.sync();
+    }
+    if (l == 0) {
+        if (n + reps > capacity) *overflow = 1;
+        count[e] = (n + reps > capacity) ? capacity : n + reps;
+    }
+}
+
 // component taps for parity tests: SPD torque for the stored state / one substep with the stored torque
 template <typename Real, typename C>
 __global__ void __launch_bounds__(64) k_env_probe(ModelDev<Real> m, EnvState<Real> st, DebugTaps<Real> dbg, int what, double dt) {

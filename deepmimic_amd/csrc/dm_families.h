@@ -47,7 +47,7 @@ enum { SV_PLAIN = 0, SV_AMP = 1, SV_TAPS = 2, SV_V2 = 3, SV_COUNT };      // SV_
     F(23, 1, ClsBipedObj, SV_V2)        \
     F(24, 2, ClsBipedObj, SV_AMP)
 
-// the reset / query / probe family: M(class) for every class, E(class) for the classes with an AMP expert of their own (every class runs its base class's)
+// the reset / query / probe family: M(class) for every class, E(class) for the classes with an AMP expert and a time-warp sampler of their own (every class runs its base class's)
 #define DM_MISC_FAMILY 11
 #define DM_MISC_CLASSES(M) M(ClsBiped) M(ClsBipedObj) M(ClsLarge) M(ClsLargeTree) M(ClsBipedTree)
 #define DM_EXPERT_CLASSES(E) E(ClsBiped) E(ClsLarge)

@@ -321,22 +321,23 @@ struct LaunchTable {
     decltype(&launch_query<Real, ClsBiped>) query[kNumCls];
     decltype(&launch_probe<Real, ClsBiped>) probe[kNumCls];
     decltype(&launch_amp_expert<Real, ClsBiped>) expert[kNumCls];
+    decltype(&launch_time_warp_sample<Real, ClsBiped>) tw_sample[kNumCls];
     int base[kNumCls];
-    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, base{} {
+    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, base{} {
 #define DM_ROW(id, pack, Cls, V) if (!step[k##Cls][V][pack - 1].launch) step[k##Cls][V][pack - 1] = {id, &launch_step_family<Real, id>};      // (of two rows for one combination the first is dispatched)
         DM_STEP_FAMILIES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls) reset[k##Cls] = &launch_reset<Real, Cls>; query[k##Cls] = &launch_query<Real, Cls>; probe[k##Cls] = &launch_probe<Real, Cls>;
         DM_MISC_CLASSES(DM_ROW)
 #undef DM_ROW
-#define DM_ROW(Cls) expert[k##Cls] = &launch_amp_expert<Real, Cls>;
+#define DM_ROW(Cls) expert[k##Cls] = &launch_amp_expert<Real, Cls>; tw_sample[k##Cls] = &launch_time_warp_sample<Real, Cls>;
         DM_EXPERT_CLASSES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls, id, Base) base[k##Cls] = k##Base;
         DM_CLASSES(DM_ROW)
 #undef DM_ROW
         for (int c = 0; c < kNumCls; ++c) {
-            expert[c] = expert[base[c]];
+            expert[c] = expert[base[c]]; tw_sample[c] = tw_sample[base[c]];
             if (!reset[c] || !expert[c]) throw "dm_families.h: a class without reset / query / probe kernels, or whose base class has no AMP expert";      // (fails the build: the table is constexpr)
         }
     }
@@ -386,6 +387,7 @@ struct CtxBase {
     virtual int obj_state(double* out, const double* in) = 0;
     virtual int manifolds(double* out, const double* in) = 0;
     virtual int amp_expert_clips(int n, const int* clips_dev /* null: the model's own clip */, const double* times_dev, const double* gh_dev, float* out_dev) = 0;
+    virtual int time_warp_sample(void* samples_dev, int* count_dev, const int* restart_dev, int capacity, int* overflow_dev) = 0;      // dm_time_warp.h
     virtual int probe(int what, double dt) = 0;
     virtual int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) = 0;
     virtual int set_state(const double* pose, const double* vel, const double* tar, const double* kin, const double* clk, const int* flg) = 0;
@@ -677,6 +679,10 @@ struct CtxT : CtxBase {
         // slot is the env's own draw key (GS_KSEED, dm_set_env_keys), which a restored aux block must not re-key
         static_assert(GS_AUX0 + 7 == GS_KSEED, "the aux window ends where the draw key starts");
         return st.goal ? rows(st.goal, Win{(size_t)N, GS_WIDTH, GS_AUX0, 7, 8}, out, in, KeepPad) : no_goal();
+    }
+    int time_warp_sample(void* samples_dev, int* count_dev, const int* restart_dev, int capacity, int* overflow_dev) override {
+        launch_table<Real>().tw_sample[cls](N, stream, md, st, (Real*)samples_dev, count_dev, restart_dev, capacity, overflow_dev);      // (the sampler of the base class)
+        return 0;
     }
     int clips(int* out, const int* in) override {                     // N: GS_CLIP, the clip the env was reset to
         if (!st.goal) { if (in) return no_goal(); for (int e = 0; e < N; ++e) out[e] = 0; return 0; }
@@ -1455,4 +1461,5 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_ppo_batch.h"     // PPO advantages, sample lists and shuffled minibatch gathers over a device-resident rollout
 #include "dm_replay.h"        // AMP discriminator data: device replay stores and expert draws (after dm_ppo_batch.h: feistel_perm)
 #include "dm_episode.h"       // episode returns, lengths and end-cause totals over a device-resident rollout (after dm_ppo_batch.h: its workgroup width and tree)
+#include "dm_time_warp.h"     // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs

@@ -41,6 +41,10 @@ template <typename Real, typename C>
 void launch_amp_expert(unsigned grid, rt_stream s, const ModelDev<Real>& m, const double* times, const double* ground_h, float* out, const int* clips) {
     RT_LAUNCH((k_amp_expert<Real, C>), grid, s, m, times, ground_h, out, clips);
 }
+template <typename Real, typename C>
+void launch_time_warp_sample(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, Real* samples, int* count, const int* restart, int capacity, int* overflow) {
+    RT_LAUNCH((k_time_warp_sample<Real, C>), grid, s, m, st, samples, count, restart, capacity, overflow);
+}
 
 // this object's family (dm_families.h): the reset / query / probe family expands its class lists, any other id instantiates the launcher of its row
 #if DM_TU_F64
@@ -54,7 +58,9 @@ typedef float TuReal;
     template void launch_reset<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, const double*, const double*); \
     template void launch_query<TuReal, C>(DM_STEP_ARGS);                                                                                                 \
     template void launch_probe<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const DebugTaps<TuReal>&, int, double);
-#define DM_INST_EXPERT(C) template void launch_amp_expert<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const double*, const double*, float*, const int*);
+#define DM_INST_EXPERT(C)                                                                                                                                 \
+    template void launch_amp_expert<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const double*, const double*, float*, const int*);            \
+    template void launch_time_warp_sample<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, TuReal*, int*, const int*, int, int*);
 DM_MISC_CLASSES(DM_INST_MISC)
 DM_EXPERT_CLASSES(DM_INST_EXPERT)
 #else

@@ -137,7 +137,7 @@ class SceneConfig:
     enable_char_contact_fall: bool = True
     enable_rand_char_placement: bool = True
     enable_amp_obs_local_root: bool = False   # scenes/SceneImitateAMP.cpp:30,42 (`--scene imitate_amp` only)
-    enable_test_time_warp: bool = True        # :31,43; the test-mode time-warp score is not on the accelerated path
+    enable_test_time_warp: bool = True        # :31,43; the test-mode time-warp score: opt-in on the batched path (deepmimic_amd/time_warp.py, TorchVecEnv(time_warp=True)), on the host in the one-env drop-in
     time_lim_min: float = np.inf        # util/Timer.cpp:7-8
     time_lim_max: float = np.inf
     time_lim_exp: float = 1.0

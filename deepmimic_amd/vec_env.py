@@ -15,22 +15,32 @@ from .binding import stream_handle, tensor_arg
 from .core import BatchEnv
 from .episodes import EpisodeStats, decode_block, merge_blocks
 from .model import SceneTables
+from .time_warp import TimeWarp, buffer_size, why_no_warper
 
 
 class TorchVecEnv:
     def __init__(self, tables: SceneTables, num_envs: int, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
                  updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
-                 episode_bin_steps: int = 1, **env_kwargs):
+                 episode_bin_steps: int = 1, time_warp: bool = False, **env_kwargs):
         """terminal_obs (default on): keep `terminal_obs` / `terminal_goal` tensors bound to the context (BatchEnv.set_terminal_outputs), handed out as
         info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent.
         episode_stats (default off: no extra launch, no extra key): `step` runs deepmimic_amd.episodes.EpisodeStats.update behind the step launch on the same
         stream and hands out info["episode_return"] / info["episode_length"]; `episode_totals()` reads the totals (and a length histogram of `episode_bins`
-        bins of `episode_bin_steps` steps)."""
+        bins of `episode_bin_steps` steps).
+        time_warp (default off: no extra launch, no extra key; `--scene imitate_amp` with a finite episode length only, refused elsewhere): the test-mode return
+        of the reference, cSceneImitateAMP::CalcRewardTimeWarp (deepmimic_amd/time_warp.py).  `step` samples every env in front of the step launch, aligns the
+        envs whose episode ended behind it and hands out info["time_warp_return"]: float32 [N], the reward the reference's test mode pays at this step -- the
+        alignment cost plus 1 per sample the episode fell short of the buffer where done[i] is set in THIS step, 0 elsewhere.  `reward` stays what the launch
+        wrote.  With `episode_stats` as well the statistics accumulate time_warp_return IN PLACE OF reward (episode_return included), so that `episode_totals()`
+        is the reference's Test_Return for these scenes.  Memory: N * 2 * capacity * 3J * sizeof(Real) for the samples, capacity = ceil(30 * episode length) + 2
+        -- 0.89 GB for 4096 humanoids and 20 s episodes in fp32."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("TorchVecEnv needs a GPU device (deepmimic_amd has no CPU path)")
+        if time_warp and buffer_size(tables.cfg, tables.query_rate) is None:
+            raise ValueError("time_warp=True: " + why_no_warper(tables.cfg))
         with torch.cuda.device(self.device):
             torch.zeros(1, device=self.device)                     # torch's context first (one HIP runtime in the process)
             self.env = BatchEnv(tables, num_envs, device_id=self.device.index or 0, seed=seed, **env_kwargs)
@@ -54,6 +64,11 @@ class TorchVecEnv:
         if episode_stats:
             self.stats = EpisodeStats(self.n, self.device, bins=episode_bins, bin_steps=episode_bin_steps, lib_path=env_kwargs.get("lib_path"))
             self.episode_return = torch.zeros(self.n, **f32); self.episode_length = torch.zeros(self.n, **i32)
+        self.tw = None
+        if time_warp:
+            self.tw = TimeWarp(self.env, tables, device=self.device)
+            self.time_warp_return = torch.zeros(self.n, **f32)
+            self._tw_restart = torch.ones(self.n, **i32)            # envs reset since their last sample: all before the first step, `done` of the last step after it
 
     def _enter(self):
         h = stream_handle(self.device)
@@ -76,6 +91,8 @@ class TorchVecEnv:
         self._leave()
         if self.stats is not None:
             self.stats.reset_carry()                                # episodes in flight are dropped, not counted
+        if self.tw is not None:
+            self._tw_restart.fill_(1)                               # every env starts its sample buffer over at the next step
         return self.obs
 
     def step(self, actions) -> Tuple["object", "object", "object", Dict[str, "object"]]:
@@ -93,6 +110,8 @@ class TorchVecEnv:
         done == False can therefore never stitch two episodes together."""
         tensor_arg("actions", actions, self.device, self.torch.float32, [(self.n, self.act_dim)])
         self._enter()
+        if self.tw is not None:
+            self.tw.sample(self._tw_restart)                        # the state at entry of the control step (cRLSceneSimChar::PreUpdate)
         self._launch(actions.data_ptr(), self.updates, True)
         self._leave()
         info = {"terminate": self.terminate, "valid": self.valid}
@@ -106,8 +125,12 @@ class TorchVecEnv:
             if self.terminal_goal is not None:
                 info["terminal_goal"] = self.terminal_goal
         done = (self.episode_end != 0) | (self.valid == 0)
+        if self.tw is not None:
+            self._tw_restart.copy_(done)                            # (done is bool: its int32 form is both the alignment's selection and the next step's restart marks)
+            self.tw.align(self._tw_restart, out=(self.time_warp_return, None), stream=self._stream_handle)
+            info["time_warp_return"] = self.time_warp_return
         if self.stats is not None:
-            self.stats.update(self.reward, self.terminate, done, self.valid, out=(self.episode_return, self.episode_length))
+            self.stats.update(self.reward if self.tw is None else self.time_warp_return, self.terminate, done, self.valid, out=(self.episode_return, self.episode_length))
             info["episode_return"], info["episode_length"] = self.episode_return, self.episode_length
         return self.obs, self.reward, done, info
 
@@ -148,17 +171,21 @@ class TorchVecEnvGroups:
     another group meanwhile, the way double-buffered samplers do; the groups then drift apart in phase and fill each other's wave-time tail
     (closed loop with the on-device policy, 4096 humanoids: 2.14 M env-steps/s against 2.05 M with one launch per step, profiles/r04_policy_bench.json).
     `step(actions)` is the synchronous convenience: all groups, then the caller's current stream waits for them.  Env i follows the same trajectory
-    as in a `TorchVecEnv` of the whole batch (draws are keyed by the global env id; tests/test_vec_env.py)."""
+    as in a `TorchVecEnv` of the whole batch (draws are keyed by the global env id; tests/test_vec_env.py).
+    `time_warp=True` as in `TorchVecEnv`: each group samples and aligns its rows of whole-batch buffers (N * 2 * capacity * 3J * sizeof(Real) bytes) on its own
+    stream, info["time_warp_return"] is row for row what the ungrouped env hands out, and with `episode_stats` the statistics accumulate it in place of `reward`."""
 
     def __init__(self, tables: SceneTables, num_envs: int, groups: int = 2, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
                  updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
-                 episode_bin_steps: int = 1, **env_kwargs):
+                 episode_bin_steps: int = 1, time_warp: bool = False, **env_kwargs):
         import torch
         from .groups import EnvGroups
         self.torch = torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("TorchVecEnvGroups needs a GPU device (deepmimic_amd has no CPU path)")
+        if time_warp and buffer_size(tables.cfg, tables.query_rate) is None:
+            raise ValueError("time_warp=True: " + why_no_warper(tables.cfg))
         with torch.cuda.device(self.device):
             torch.zeros(1, device=self.device)
             self.g = EnvGroups(tables, num_envs, groups=groups, device_id=self.device.index or 0, seed=seed, **env_kwargs)
@@ -185,6 +212,14 @@ class TorchVecEnvGroups:
             self._acc_return = torch.zeros(self.n, dtype=torch.float64, device=self.device); self._acc_len = torch.zeros(self.n, **i32)
             self.stats = [EpisodeStats(self.g.count[g], self.device, bins=episode_bins, bin_steps=episode_bin_steps,
                                        lib_path=env_kwargs.get("lib_path"), carry=(self._acc_return[self.rows(g)], self._acc_len[self.rows(g)])) for g in range(self.G)]
+        # the time-warp return as in TorchVecEnv: one TimeWarp per group, on its rows of whole-batch sample buffers and on its stream
+        self.tw = None
+        if time_warp:
+            cap = buffer_size(tables.cfg, tables.query_rate)
+            self.time_warp_return = torch.zeros(self.n, **f32); self._tw_restart = torch.ones(self.n, **i32)
+            self._tw_samples = torch.zeros((self.n, 2, cap, 3 * self.g.J), dtype=torch.float64 if self.g.envs[0].precision == 64 else torch.float32, device=self.device)
+            self._tw_count = torch.zeros(self.n, **i32)
+            self.tw = [TimeWarp(self.g.envs[g], tables, device=self.device, buffers=(self._tw_samples[self.rows(g)], self._tw_count[self.rows(g)])) for g in range(self.G)]
 
     def rows(self, g: int) -> slice:
         return self.g.rows(g)
@@ -193,6 +228,8 @@ class TorchVecEnvGroups:
         return self.streams[g]
 
     def _launch(self, g, actions_ptr, n_updates, auto_reset):
+        if self.tw is not None and n_updates:
+            self.tw[g].sample(self._tw_restart[self.rows(g)])      # in front of the step launch, on the group's stream
         self.g.step_group_device(g, actions_ptr, self.obs.data_ptr(), self.reward.data_ptr(), self.terminate.data_ptr(), self.valid.data_ptr(),
                                  self.episode_end.data_ptr(), timestep=self.timestep, n_updates=n_updates, auto_reset=auto_reset,
                                  amp_ptr=self.amp_obs.data_ptr() if self.amp_obs is not None else 0)
@@ -211,12 +248,20 @@ class TorchVecEnvGroups:
                 info["terminal_goal"] = self.terminal_goal[r]
         if self.stats is not None:
             info["episode_return"], info["episode_length"] = self.episode_return[r], self.episode_length[r]
+        if self.tw is not None:
+            info["time_warp_return"] = self.time_warp_return[r]
         return info
 
     def _episode_update(self, g, done):
-        """group g's EpisodeStats.update on its rows; the caller has made `stream(g)` torch's current stream"""
+        """behind group g's step launch, on its rows: the time-warp return of the envs that ended, then EpisodeStats.update (on that return where there is one);
+        the caller has made `stream(g)` torch's current stream"""
         r = self.rows(g)
-        self.stats[g].update(self.reward[r], self.terminate[r], done, self.valid[r], out=(self.episode_return[r], self.episode_length[r]))
+        if self.tw is not None:
+            self._tw_restart[r].copy_(done)
+            self.tw[g].align(self._tw_restart[r], out=(self.time_warp_return[r], None), stream=self.streams[g].cuda_stream)
+        if self.stats is not None:
+            self.stats[g].update(self.reward[r] if self.tw is None else self.time_warp_return[r], self.terminate[r], done, self.valid[r],
+                                 out=(self.episode_return[r], self.episode_length[r]))
 
     def reset(self):
         self.g.reset()
@@ -224,9 +269,12 @@ class TorchVecEnvGroups:
         for g in range(self.G):
             self.streams[g].wait_stream(cur)      # reads of self.obs the caller still has queued on its stream come first (write-after-read)
             self._launch(g, 0, 0, False)
-            if self.stats is not None:
+            if self.stats is not None or self.tw is not None:
                 with self.torch.cuda.stream(self.streams[g]):
-                    self.stats[g].reset_carry()   # episodes in flight are dropped, not counted
+                    if self.stats is not None:
+                        self.stats[g].reset_carry()   # episodes in flight are dropped, not counted
+                    if self.tw is not None:
+                        self._tw_restart[self.rows(g)].fill_(1)
         self._join()
         return self.obs
 
@@ -242,7 +290,7 @@ class TorchVecEnvGroups:
         r = self.rows(g)
         with t.cuda.stream(self.streams[g]):
             done = (self.episode_end[r] != 0) | (self.valid[r] == 0)
-            if self.stats is not None:
+            if self.stats is not None or self.tw is not None:
                 self._episode_update(g, done)
         return self.obs[r], self.reward[r], done, self._info(r)
 
@@ -258,7 +306,7 @@ class TorchVecEnvGroups:
         for g in range(self.G):
             self.streams[g].wait_stream(cur)
             self._launch(g, actions.data_ptr(), self.updates, True)
-            if self.stats is not None:
+            if self.stats is not None or self.tw is not None:
                 r = self.rows(g)
                 with self.torch.cuda.stream(self.streams[g]):
                     self._episode_update(g, (self.episode_end[r] != 0) | (self.valid[r] == 0))

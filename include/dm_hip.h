@@ -686,6 +686,36 @@ int dm_episode_stats(int device_id, int T, int N, const float* rewards_dev, cons
                      float* ep_return_out /* NULL or [T, N] */, int32_t* ep_len_out /* NULL or [T, N] */, void* totals_dev /* NULL or DM_EP_TOTALS_WORDS words, in/out */,
                      int64_t* hist_dev /* NULL or [bins], in/out */, int bins, int bin_steps, void* work_dev, int64_t work_bytes, void* hip_stream);
 
+/* ---- the test-mode time-warp return of `--scene imitate_amp` for a batch of envs (deepmimic_amd/csrc/dm_time_warp.h, dm_device.h k_time_warp_sample,
+ * deepmimic_amd/time_warp.py): cSceneImitateAMP::CalcRewardTimeWarp (scenes/SceneImitateAMP.cpp:174-207, 417-480; util/DynamicTimeWarper.cpp:114-140), what the
+ * reference's learner logs as Test_Return for an AMP imitation policy.  Stateless like dm_replay_* and dm_episode_stats: the caller owns every byte, DEVICE pointers
+ * only, no allocation, no host read and no synchronisation inside; a refused call launches nothing.
+ *   samples   [N][2][capacity][3J] elements of the context's precision (dm_time_warp_dims: out[0] = bytes per element, 4 or 8; out[1] = 3J); [.][0] the simulated,
+ *             [.][1] the kinematic character; a row is BuildTimeWarpData: (0, root height, 0) for joint 0, joint position - root position for the others
+ *   count     int32[N], rows held per env;  overflow: one int32 word, set to 1 by an append that found no room (the reference throws there), never cleared here
+ * capacity is cSceneImitateAMP::BuildTimeWarper's buffer size, ceil(query rate * max(time_lim_max, time_end_lim_max)) + 2.
+ *
+ * dm_time_warp_sample: on the ctx's stream, in front of the step launch (the sample is the state at ENTRY of a control step, cRLSceneSimChar::PreUpdate).  Env i with
+ * restart_dev[i] != 0 (restart_dev NULL: every env) starts over: count = 0, then TWO identical rows (ResetTimeWarper adds one, the PreUpdate of the first update
+ * behind a reset one more, NeedNewAction being true there); any other env appends one row.  An append at count == capacity writes nothing, leaves count and sets
+ * *overflow_dev.  Nothing outside env i's block is written.  With a multi-clip dataset the kinematic side is env i's own clip.
+ * Refused: a NULL ctx / samples / count / overflow; capacity < 2; a context whose scene has no kinematic character to sample.
+ *
+ * dm_time_warp_align: needs no ctx; asynchronous on hip_stream of device device_id.  Per env i with select_dev[i] != 0 (select_dev NULL: every env) and n = count[i]:
+ *     cost(0, 0) = 0, the rest of row 0 and column 0 +inf, cost(a, b) = d(a, b) + min(cost(a-1, b-1), cost(a-1, b), cost(a, b-1)) for 1 <= a, b < n,
+ *     d(a, b) = (sum over the dim / 3 points p, in order, of |sim_a[p] - kin_b[p]|) / (dim / 3)
+ *     reward_out[i] = cost(n-1, n-1) + (capacity - n) * term_step_cost (one rounding to float), cost_out[i] = cost(n-1, n-1) (NULL: not wanted)
+ * n == 1: cost 0; n == 0 or select_dev[i] == 0: reward 0 and cost 0.  Distances in the element type (f64 == 0: float, else double), table values in fp64, no
+ * contraction, no atomics: two calls on the same inputs give the same bytes.  One wavefront per env; the kernel's shape is described in dm_time_warp.h.
+ * Refused: n_envs < 1; a NULL samples / count / reward_out; capacity < 2; dim not a positive multiple of 3; samples not aligned to its element, cost_out not 8-byte
+ * aligned; 8 capacity + 192 (dim | 1) sizeof(element) above 160 KB (the workgroup's LDS); no HIP device or a device_id it does not have. */
+int dm_time_warp_dims(const dm_ctx* ctx, int32_t* out /* [2] */);
+int dm_time_warp_sample(dm_ctx* ctx, void* samples_dev, int32_t* count_dev /* [N] in/out */, const int32_t* restart_dev /* NULL: all */, int capacity,
+                        int32_t* overflow_dev);
+int dm_time_warp_align(int device_id, int n_envs, int capacity, int dim, int f64, const void* samples_dev, const int32_t* count_dev,
+                       const int32_t* select_dev /* NULL: all */, double term_step_cost, float* reward_out_dev /* [N] */, double* cost_out_dev /* NULL or [N] */,
+                       void* hip_stream);
+
 /* ---- a probe for the device math helpers(deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
  * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
  * pointers.  The kernel narrows the inputs the op reads to float (f64 == 0) or keeps them double (f64 != 0), calls the helper in that type, and widens the result
