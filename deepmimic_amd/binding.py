@@ -44,6 +44,7 @@ SIGNATURES = {
     "dm_time_warp_sample": ([_p, _p, _p, _p, _i, _p], None),
     "dm_time_warp_align": ([_i, _i, _i, _i, _i, _p, _p, _p, _d, _p, _p, _p], None),
     "dm_math_probe": ([_i, _i, _i, _i, _p, _p, _p], None),
+    "dm_wave_probe": ([_i, _i, _i, _i, _i, _p, _p, _p], None),
 }
 
 

@@ -1463,3 +1463,27 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_episode.h"       // episode returns, lengths and end-cause totals over a device-resident rollout (after dm_ppo_batch.h: its workgroup width and tree)
 #include "dm_time_warp.h"     // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs
+
+// test support: one wave-level primitive of dm_device.h / dm_device_duo.h per launch.  The kernel (dm_wave_probe.h) is compiled into the object of DM_MISC_FAMILY, which
+// sees those headers; here only its launcher's declaration (dm_launch.h) and the argument checks.
+extern "C" int dm_wave_probe(int device_id, int op, int arg, int f64, int n_waves, const double* in_dev, double* out_dev, void* hip_stream) {
+    if (n_waves < 1 || n_waves > 65536) return fail("dm_wave_probe: n_waves must be in 1..65536");
+    if (!in_dev || !out_dev) return fail("dm_wave_probe: null argument");
+    if (op < 0 || op >= DM_WOP_COUNT) return fail("dm_wave_probe: unknown op");
+    bool ok = arg == 0;
+    switch (op) {
+    case DM_WOP_LANE_SEL: ok = arg >= 0 && arg < DM_WAVE_PROBE_MASK_CHUNKS; break;
+    case DM_WOP_ROW_FILE: ok = arg == 32 || arg == 40 || arg == 48 || arg == 56 || arg == 64; break;
+    case DM_WOP_GRAM32: ok = arg == 17 || arg == 20 || arg == 32; break;
+    case DM_WOP_GRAM64: ok = arg == 17 || arg == 32; break;
+    case DM_WOP_DUO_GRAM32: ok = arg == 17 || arg == 20; break;
+    case DM_WOP_XD_BLOCK: case DM_WOP_XD_TR_STAGE: ok = arg >= 0 && arg < 4; break;
+    default: break;
+    }
+    if (!ok) return fail("dm_wave_probe: this op has no variant `arg`");
+    if (valid_device("dm_wave_probe", device_id)) return -1;
+    DevGuard guard(device_id);
+    if (f64) launch_wave_probe<double>((unsigned)n_waves, (rt_stream)hip_stream, op, arg, in_dev, out_dev);
+    else launch_wave_probe<float>((unsigned)n_waves, (rt_stream)hip_stream, op, arg, in_dev, out_dev);
+    return launch_status(0);
+}

@@ -14,6 +14,9 @@
 #endif
 #include "dm_launch.h"
 #include "dm_device_duo.h"
+#if DM_TU_ID == DM_MISC_FAMILY
+#include "dm_wave_probe.h"    // test support: one wave-level primitive of the two headers above per launch (this object only)
+#endif
 
 namespace dmk {
 
@@ -63,6 +66,7 @@ typedef float TuReal;
     template void launch_time_warp_sample<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, TuReal*, int*, const int*, int, int*);
 DM_MISC_CLASSES(DM_INST_MISC)
 DM_EXPERT_CLASSES(DM_INST_EXPERT)
+template void launch_wave_probe<TuReal>(unsigned, rt_stream, int, int, const double*, double*);
 #else
 template void launch_step_family<TuReal, DM_TU_ID>(DM_STEP_ARGS);
 #endif

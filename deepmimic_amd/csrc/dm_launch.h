@@ -34,5 +34,8 @@ template <typename Real, typename C>
 void launch_amp_expert(unsigned grid, rt_stream s, const ModelDev<Real>& m, const double* times, const double* ground_h, float* out, const int* clips);
 template <typename Real, typename C>
 void launch_time_warp_sample(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, Real* samples, int* count, const int* restart, int capacity, int* overflow);
+// test support (dm_wave_probe.h, in the object of DM_MISC_FAMILY): one wave-level primitive of dm_device.h / dm_device_duo.h per launch, `grid` wavefronts
+template <typename Real>
+void launch_wave_probe(unsigned grid, rt_stream s, int op, int arg, const double* in, double* out);
 
 }  // namespace dmk

@@ -747,6 +747,44 @@ enum { DM_MOP_SINCOS = 0, DM_MOP_ROT_Y, DM_MOP_ROT_Z, DM_MOP_NORMALIZE_ANGLE, DM
        DM_MOP_CROSS_ADD, DM_MOP_M3_V3, DM_MOP_TMUL, DM_MOP_M3_M3, DM_MOP_COUNT };
 int dm_math_probe(int device_id, int op, int f64, int n, const double* in_dev, double* out_dev, void* hip_stream);
 
+/* ---- a probe for the wave-level primitives of the step kernels (the top of deepmimic_amd/csrc/dm_device.h and dm_device_duo.h; dm_wave_probe.h): TEST SUPPORT, nothing
+ * of the product calls it.  One launch of n_waves workgroups, one wavefront each, evaluates the primitive `op`; lane l of workgroup w reads
+ * in_dev[(w * 64 + l) * DM_WAVE_PROBE_IN ..] and writes out_dev[(w * 64 + l) * DM_WAVE_PROBE_OUT ..], doubles both, DEVICE pointers.  Values are narrowed to float
+ * (f64 == 0) or kept double on load and widened on store; columns and lanes an op does not write keep the caller's bytes.  "in0" / "in1" are the rows of lanes 0 / 1 of
+ * the workgroup (wave-uniform arguments).  `arg` selects among an op's compile-time variants and must be 0 where none is listed.
+ *     op            arg                reads                                                        writes (column c)
+ *     WAVE_SHFL                        v = in[0], src = in[1] (any int)                             [0] wave_shfl(v, src)
+ *     LANE_BCAST                       v = in[0], src_c = in0[1 + c] in 0..63                       c < 63: lane_bcast(v, src_c)
+ *     HALF_BCAST                       v = in[0], src_c = in0[1 + c] in 0..31                       c < 63: half_bcast(v, src_c, lane / 32)
+ *     HALF_BCAST_C                     v = in[0]                                                    c < 32: half_bcast_c<c>(v, lane / 32)
+ *     SHFL_XOR_C                       v = in[0]                                                    c < 6: wave_shfl_xor_c<1 << c>(v)
+ *     LANE_SEL      mask chunk         a = in[0], b = in[1]                                         c < 64: lane_sel<mask(arg, c)>(a, b, lane, z)   (wp_mask of dm_wave_probe.h)
+ *     ROW_SEL_C                        old = in[0], new = in[1]                                     c < 64: row_sel_c<c>(old, new, lane, one)
+ *     HALF_SEL_C                       old = in[0], new = in[1]                                     c < 32: half_sel_c<c>(old, new, lane % 32, one)
+ *     CHAIN_KEEP                       v = in[0], lo = in[1], hi = in[2] (uint32 values)            c < 64: chain_keep<c>(v, lo, hi)
+ *     ROW_FILE      N: 32 40 48 56 64  x = in[0..N-1], s_k = in0[64 + k], g_k = in1[64 + k]         k < N, 0 <= g_k < N: entry g_k of the file after entry j := x[j] for all j,
+ *                                                                                                   then entry s_k := x[k] for k = 0..N-1 in turn where 0 <= s_k < N
+ *     BALLOT                           p = in[0] != 0                                               [0], [1] low, high word of wave_ballot(p)
+ *     WAVE_SUM, HALF_SUM               v = in[0]                                                    [0] the sum
+ *     RCP, RSQRT                       x_c = in[c]                                                  c < 64: dm_rcp(x_c) / dm_rsqrt(x_c)
+ *     MED3                             lo, x, hi = in[3c .. 3c + 2]                                 c < 32: dm_med3(lo, x, hi)
+ *     WG_UNIT                                                                                       [0] dm_wg_unit() (the grid is n_waves)
+ *     GRAM32        NP2: 17 20 32      y = in[0 .. 2 NP2 - 1]                                       c < 32: wave_gram32<NP2>
+ *     GRAM64        NP2: 17 32         y                                                            c < 64: wave_gram64_half<NP2, c / 32> entry c % 32
+ *     DUO_GRAM32    NP2: 17 20         y                                                            c < 32: duo_gram32<NP2>
+ *     XD_OPERANDS                      y (NP2 = 17)                                                 c < 34: y after xd_gram_operands<17>
+ *     XD_BLOCK      2 X + Y            y (NP2 = 17)                                                 c < 32: the f(c, value) of xd_gram_block<17, X, Y> after xd_gram_operands
+ *     XD_TR_STAGE   stage 0..3         w = in[0..16]                                                c < 17: w after xd_tr_stage<N, MASK, 17>, (N, MASK) = (17, 2) (9, 4) (5, 8) (3, 16)
+ * Needs no dm_ctx; asynchronous on hip_stream of device device_id.  Refused, nothing is launched: n_waves < 1 or > 65536, a NULL pointer, an op outside
+ * [0, DM_WOP_COUNT), an arg the op does not list, no HIP device or a device_id it does not have. */
+#define DM_WAVE_PROBE_IN 128
+#define DM_WAVE_PROBE_OUT 64
+#define DM_WAVE_PROBE_MASK_CHUNKS 9
+enum { DM_WOP_WAVE_SHFL = 0, DM_WOP_LANE_BCAST, DM_WOP_HALF_BCAST, DM_WOP_HALF_BCAST_C, DM_WOP_SHFL_XOR_C, DM_WOP_LANE_SEL, DM_WOP_ROW_SEL_C, DM_WOP_HALF_SEL_C,
+       DM_WOP_CHAIN_KEEP, DM_WOP_ROW_FILE, DM_WOP_BALLOT, DM_WOP_WAVE_SUM, DM_WOP_HALF_SUM, DM_WOP_RCP, DM_WOP_RSQRT, DM_WOP_MED3, DM_WOP_WG_UNIT, DM_WOP_GRAM32,
+       DM_WOP_GRAM64, DM_WOP_DUO_GRAM32, DM_WOP_XD_OPERANDS, DM_WOP_XD_BLOCK, DM_WOP_XD_TR_STAGE, DM_WOP_COUNT };
+int dm_wave_probe(int device_id, int op, int arg, int f64, int n_waves, const double* in_dev, double* out_dev, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

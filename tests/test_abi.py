@@ -96,6 +96,7 @@ def test_invalid_device_id_is_refused_by_name_gpu(hip_lib):
     import numpy as np
     import torch
     from deepmimic_amd import math_probe as mpr
+    from deepmimic_amd import wave_probe as wpr
     from deepmimic_amd import ppo_batch as pb
     from deepmimic_amd import returns as rt
     from deepmimic_amd.normalizer import DeviceNormalizer
@@ -114,6 +115,8 @@ def test_invalid_device_id_is_refused_by_name_gpu(hip_lib):
     weights = random_weights(2, 1, H1=64, H2=64)
     probe_in = torch.zeros((1, mpr.IN), dtype=torch.float64, device="cuda")
     probe_out = torch.full((1, mpr.OUT), -77.0, dtype=torch.float64, device="cuda")
+    wave_in = torch.zeros((wpr.WAVE, wpr.IN), dtype=torch.float64, device="cuda")
+    wave_out = torch.full((wpr.WAVE, wpr.OUT), -77.0, dtype=torch.float64, device="cuda")
     for dev in (-1, torch.cuda.device_count()):
         with pytest.raises(RuntimeError, match="dm_td_lambda_returns: invalid device_id"):
             rt.td_lambda_returns(1, 1, rewards.data_ptr(), values.data_ptr(), term_values.data_ptr(), terminate.data_ptr(), done.data_ptr(), 0, 0.95, 0.95, 0.0, 1.0,
@@ -129,5 +132,7 @@ def test_invalid_device_id_is_refused_by_name_gpu(hip_lib):
             Policy(weights, device_id=dev, lib_path=hip_lib)
         with pytest.raises(RuntimeError, match="dm_math_probe: invalid device_id"):
             mpr.math_probe("SINCOS", 0, 1, probe_in.data_ptr(), probe_out.data_ptr(), device_id=dev, lib_path=hip_lib)
-    for name, t in dict(returns=returns, mask=mask, adv=adv, targets=targets, valid_idx=valid_idx, exp_idx=exp_idx, counts=counts, stats=stats, work=work, dst=dst, probe_out=probe_out).items():
+        with pytest.raises(RuntimeError, match="dm_wave_probe: invalid device_id"):
+            wpr.wave_probe("WAVE_SUM", 0, 1, wave_in.data_ptr(), wave_out.data_ptr(), device_id=dev, lib_path=hip_lib)
+    for name, t in dict(returns=returns, mask=mask, adv=adv, targets=targets, valid_idx=valid_idx, exp_idx=exp_idx, counts=counts, stats=stats, work=work, dst=dst, probe_out=probe_out, wave_out=wave_out).items():
         assert (t == -77).all(), name

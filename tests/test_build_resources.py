@@ -112,6 +112,22 @@ def test_secondary_kernels_stay_inside_their_measured_spill_budget(family, what,
     assert r["spill"] <= spill_max, (what, r)
 
 
+@pytest.mark.parametrize("prec,real,scratch_max", [("f32", "f", 0), ("f64", "d", 272)])
+def test_wave_probe_kernel_keeps_its_operands_in_registers(prec, real, scratch_max):
+    """k_wave_probe (dm_wave_probe.h, in the object of the reset / query / probe family) measures the primitives as the step kernels use them only while its row files,
+    Gram operands and accumulators stay in VGPRs: no spill in either precision, no scratch in float.  In double the 272 bytes are the `out[i]` of the fp64 Gram bodies' own
+    `#pragma unroll 1` row loop (32 doubles and a pair), the primitive as it is written."""
+    path = os.path.join(BUILD, "k_%s_11.o.res" % prec)
+    if not os.path.exists(path):
+        pytest.skip("no resource remarks (libdm_hip.so not built here)")
+    blocks = re.split(r"remark: Function Name: ", open(path).read())
+    mine = [b for b in blocks if b.startswith("_ZN3dmw12k_wave_probeI%sEE" % real)]
+    assert len(mine) == 1, [b.split(" ")[0] for b in blocks[1:]]
+    get = lambda pat: int(re.search(pat, mine[0]).group(1))
+    assert get(r"VGPRs Spill: (\d+)") == 0 and get(r"SGPRs Spill: (\d+)") == 0
+    assert get(r"ScratchSize \[bytes/lane\]: (\d+)") <= scratch_max and get(r"LDS Size \[bytes/block\]: (\d+)") == 0
+
+
 def test_committed_counter_files_carry_the_kernel_source_stamp():
     """bench.py quotes HBM traffic and VALU figures from COMMITTED rocprofv3 counter files (PMC passes serialise the kernels, so they cannot be taken inside
     the timed run).  Each file carries the hash of the device sources it was taken on and the bench line says whether that is what it runs
