@@ -277,12 +277,9 @@ int dm_policy_forward_ex(dm_policy* p, const float* states_dev, const float* goa
 
 }  // extern "C"
 
-// What dm_policy_forward_ex and dm_policy_eval_scalar share: the activation buffers grown to io.M rows, the kernel choice (policy_path) and the launches.  `io` carries the
-// call's own members (inputs, outputs, noise or head); scalar: the HEAD = 1 instantiation of the kernel that holds layer 3, everything in front of it as for the actor.
-static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_stream) {
-    const int n = io.M;
-    DevGuard guard(p->device_id);
-    rt_stream stream = (rt_stream)hip_stream;
+// the activation buffers of a context grown to n rows (what policy_run and the training calls of dm_train.h share): n x (K1 + H1 + H2) bf16, with a gate its four fp32 scratch
+// arrays; a growth waits for `stream` first, so work queued on it has left the old buffers
+static int policy_grow(dm_policy* p, int n, rt_stream stream) {
     if (n > p->cap) {                       // hidden activations: n x (H1 + H2) bf16, grown on demand
         rt_sync(stream);
         if (p->h1) rt_free(p->h1); if (p->h2) rt_free(p->h2); if (p->s16) rt_free(p->s16); p->h1 = p->h2 = p->s16 = nullptr; p->cap = 0;
@@ -296,6 +293,16 @@ static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_st
         }
         p->h1 = (uint16_t*)a; p->h2 = (uint16_t*)b; p->s16 = (uint16_t*)c; p->cap = n;
     }
+    return 0;
+}
+
+// What dm_policy_forward_ex and dm_policy_eval_scalar share: the activation buffers grown to io.M rows, the kernel choice (policy_path) and the launches.  `io` carries the
+// call's own members (inputs, outputs, noise or head); scalar: the HEAD = 1 instantiation of the kernel that holds layer 3, everything in front of it as for the actor.
+static int policy_run(dm_policy* p, dmp::ScalarIO& io, bool scalar, void* hip_stream) {
+    const int n = io.M;
+    DevGuard guard(p->device_id);
+    rt_stream stream = (rt_stream)hip_stream;
+    if (policy_grow(p, n, stream)) return -1;
     io.s16 = p->s16; io.h1 = p->h1; io.h2 = p->h2;
     if (!scalar) if (const char* pr = getenv("DM_POLICY_PROBE")) io.probe = atoi(pr);
     io.gsig0 = p->gbuf[0]; io.gbeta0 = p->gbuf[1]; io.gsig1 = p->gbuf[2]; io.gbeta1 = p->gbuf[3]; io.gate = p->gd_dev;

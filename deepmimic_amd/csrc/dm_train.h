@@ -1,0 +1,508 @@
+// PPO actor and critic minibatch updates on the device (include/dm_hip.h dm_train_*, deepmimic_amd/train.py): what PPOAgent._update_actor / _update_critic and
+// MPISolver.update do (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples.
+// Included at the end of dm_host.cpp (shares its runtime shim, dm_policy's kernels and the workgroup tree of dm_ppo_batch.h); in no step-kernel translation unit.
+// Out of scope: the gated nets, the AMP discriminator update (its gradient penalty needs a second derivative), Adam, one fused training kernel, step-size schedules.
+//
+// One *_grad call is, in stream order:
+//     k_policy_prep, layers 1 and 2     the context's own per-layer kernels (forced: DM_POLICY_* is not read), leaving s16 / h1 / h2 in bf16 as the sampling net had them
+//     k_train_head                      one wavefront per 16 rows owns all N3 columns: layer 3 with the MFMA chain of k_policy_layer<2,1,2>, z3 (fp32) and dz3 (bf16, padded
+//                                       columns zero) into the workspace, per-row statistics folded over the workgroup's rows in row order into one fp64 partial block
+//     k_train_fold                      one workgroup: the partial blocks in a fixed order (contiguous runs per thread, then the tree of dm_ppo_batch.h) -> stats
+//     k_train_wgrad x 3, k_train_bgrad x 3, k_train_dgrad x 2        layer 3 first
+// Every matrix-core operand is bf16 (RNE), accumulation fp32, gradients fp32.  Nothing is split over the contraction, so there is no partial to fold and no atomic: the
+// k-steps of a tile are accumulated in ascending order by one wavefront, two calls on one input give the same bytes.
+//
+// k_train_wgrad   dW [K x N] = in^T dz: both operands are contracted over the ROW index of row-major arrays.  A wavefront owns a 32 x 32 tile of dW; per 32 batch rows it
+//                 stages the 32 x 32 blocks of `in` and `dz` in LDS with 16-byte row reads and takes its fragments back column-wise (8 two-byte LDS reads per fragment;
+//                 rows past M are staged as zeros).  The padding columns of s16 are computed and not stored.
+// k_train_bgrad   db = the column sums of the same bf16 dz in fp32: per column four contiguous row quarters, each ascending, added in order.
+// k_train_dgrad   dz_prev [M x H] = (dz W^T) . [h != 0]: A fragments are 16 bytes of a dz row, B fragments 8 consecutive floats of a master row converted on load (zeros
+//                 past the true width of w3), the ReLU mask and the bf16 store in the epilogue.  A wavefront owns 32 rows x 32 columns.
+// k_train_sgd     the momentum step, a grid-stride loop over P: the new momentum from exact fp64 products, rounded once; the master by one fmaf.
+// A non-finite input (observation past the normaliser's clip, action, advantage, old logp, target, master) reaches the gradients as a non-finite value: bf16_rne keeps a
+// NaN a NaN, nothing clamps.  (A NaN OBSERVATION is not one: k_policy_prep turns it into -s_clip, as for the sampling net.)
+#pragma once
+
+namespace dmt {
+
+using dmp::bf16x8; using dmp::f32x4; using dmp::mfma16;
+
+constexpr int kMaxA = 128;        // action bounds ride in the kernel arguments
+
+// round to nearest even; unlike dmp::f32_to_bf16 a NaN stays a NaN (quiet, sign kept)
+DMP_DEV uint16_t bf16_rne(float f) {
+    uint32_t u = __builtin_bit_cast(uint32_t, f);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)((u >> 16) | 0x40u);
+    u += 0x7fffu + ((u >> 16) & 1u);
+    return (uint16_t)(u >> 16);
+}
+
+DMP_DEV float bf16_f32(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
+
+// exp(x) with every rounding point written down (Cephes expf: k = rint(x log2 e), r = x - k ln 2 in two fmaf, a degree-5 polynomial in Horner form, ldexp), so that
+// device, emulator and the numpy mirror (deepmimic_amd/train.py reference_exp) agree bit for bit; within 2 ulp of exp.  NaN -> NaN, +inf -> +inf, -inf -> 0.
+DMP_DEV float exp_det(float x) {
+    if (!(x == x)) return x;
+    x = fminf(fmaxf(x, -104.0f), 89.0f);
+    const float kf = rintf(x * 1.44269504088896341f);
+    float r = fmaf(kf, -0.693359375f, x); r = fmaf(kf, 2.12194440e-4f, r);
+    float p = fmaf(r, 1.9875691500e-4f, 1.3981999507e-3f);
+    p = fmaf(p, r, 8.3334519073e-3f); p = fmaf(p, r, 4.1665795894e-2f); p = fmaf(p, r, 1.6666665459e-1f); p = fmaf(p, r, 5.0000001201e-1f);
+    const float z = r * r;
+    const float y = fmaf(p, z, r) + 1.0f;
+    return ldexpf(y, (int)kf);
+}
+
+enum { HEAD_ACTOR = 0, HEAD_CRITIC = 1 };
+enum { PART_WORDS = 8 };          // fp64 words per workgroup partial: actor {sum min(l0, l1), clipped rows, sum ratio, sum logp, sum violation^2}, critic {sum e^2, sum v}
+
+struct HeadArgs {
+    int M, kind, bounded;
+    const float *actions, *old_logp, *adv, *targets;
+    float clip_lo, clip_hi, eps, bwn, nf, c0;  // 1 - eps, 1 + eps, eps, bound_weight / n, n, (-0.5 A) ln 2 pi -- all float, formed on the host (no contraction)
+    float* z3; uint16_t* dz3; double* part; float* out;      // out: logp_out / values_out or null
+    float bmin[kMaxA], bmax[kMaxA];            // un-normalised action bounds (bounded != 0)
+};
+
+// what the actor head makes of one element: u = (x - mu) / sigma with x the normalised action
+struct HeadElem { float mu, sg, u; };
+DMP_DEV HeadElem head_elem(const dmp::PolicyDev& p, const HeadArgs& a, int row, int col, float mu) {
+    HeadElem e; e.mu = mu; e.sg = exp_det(p.logstd[col]);
+    const float x = (a.actions[(size_t)row * p.A + col] - p.a_mean[col]) / p.a_std[col];
+    e.u = (x - mu) / e.sg;
+    return e;
+}
+
+__global__ void __launch_bounds__(64) k_train_head(dmp::PolicyDev p, const uint16_t* h2, HeadArgs a) {
+    __shared__ double rowv[16][5];
+    __shared__ double lanev[64][4];
+    const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
+    const int row0 = (int)blockIdx.x * 16, KS = p.H2 / 32, NB = p.N3 / 32, N3 = p.N3;
+    const uint16_t* const ap = h2 + (size_t)(row0 + c < a.M ? row0 + c : 0) * p.H2 + 8 * g;
+    float q[4] = {0.0f, 0.0f, 0.0f, 0.0f}, sls = 0.0f;
+    // ---- layer 3 (the MFMA chain of k_policy_layer<2, 1, 2>: per 16-column tile the k-steps ascending from a zero accumulator), z3 = acc + b3 into the workspace
+    for (int cb = 0; cb < NB; ++cb) {
+        f32x4 acc[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[j][r] = 0.0f;
+        for (int ks = 0; ks < KS; ++ks) {
+            const bf16x8 af = *reinterpret_cast<const bf16x8*>(ap + (size_t)ks * 32);
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[j] = mfma16(af, *reinterpret_cast<const bf16x8*>(p.w3p + (((size_t)(2 * cb + j) * KS + ks) * 64 + l) * 8), acc[j]);
+        }
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = (2 * cb + j) * 16 + c;
+            const bool live = col < p.A;
+            const float b3 = live ? p.b3[col] : 0.0f;
+            if (live && a.kind == HEAD_ACTOR) sls += p.logstd[col];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + 4 * g + r;
+                if (row >= a.M) continue;
+                const float mu = live ? acc[j][r] + b3 : 0.0f;
+                a.z3[(size_t)row * N3 + col] = mu;
+                if (live && a.kind == HEAD_ACTOR) { const HeadElem e = head_elem(p, a, row, col, mu); q[r] = fmaf(e.u, e.u, q[r]); }
+            }
+        }
+    }
+    if (a.kind == HEAD_CRITIC) {
+        // 0.5 MSE: dz3 = (v - tar) / n in column 0, zeros in the padding columns
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int row = row0 + 4 * g + r;
+            if (row < a.M) {
+                for (int col = c; col < N3; col += 16) if (col != 0) a.dz3[(size_t)row * N3 + col] = 0;
+                if (c == 0) {
+                    const float v = a.z3[(size_t)row * N3], e = v - a.targets[row];
+                    a.dz3[(size_t)row * N3] = bf16_rne(e / a.nf);
+                    if (a.out) a.out[row] = v;
+                    rowv[4 * g + r][0] = (double)e * (double)e; rowv[4 * g + r][1] = (double)v;
+                }
+            } else if (c == 0) { rowv[4 * g + r][0] = 0.0; rowv[4 * g + r][1] = 0.0; }
+        }
+        __syncthreads();
+        if (l < 2) { double s = 0.0; for (int m = 0; m < 16; ++m) s += rowv[m][l]; a.part[(size_t)blockIdx.x * PART_WORDS + l] = s; }
+        return;
+    }
+    // ---- actor: logp is a row sum over the 16 lanes of a group (each lane: its columns ascending, then the xor tree), the constant once
+    sls += dmp::lane_xor_f(sls, 1); sls += dmp::lane_xor_f(sls, 2); sls += dmp::lane_xor_f(sls, 4); sls += dmp::lane_xor_f(sls, 8);
+    const float cst = a.c0 - sls;
+    float gi[4];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = row0 + 4 * g + r;
+        float s = q[r];
+        s += dmp::lane_xor_f(s, 1); s += dmp::lane_xor_f(s, 2); s += dmp::lane_xor_f(s, 4); s += dmp::lane_xor_f(s, 8);
+        gi[r] = 0.0f;
+        double st[4] = {0.0, 0.0, 0.0, 0.0};
+        if (row < a.M) {
+            const float lp = fmaf(-0.5f, s, cst), adv = a.adv[row];
+            const float ratio = exp_det(lp - a.old_logp[row]);
+            const float l0 = adv * ratio, l1 = adv * fminf(fmaxf(ratio, a.clip_lo), a.clip_hi);
+            const bool first = !(l0 > l1);                   // tf.minimum sends the gradient of a tie to its first argument; a NaN stays in the gradient
+            gi[r] = first ? -(l0 / a.nf) : 0.0f;
+            st[0] = (double)(first ? l0 : l1); st[1] = fabsf(ratio - 1.0f) > a.eps ? 1.0 : 0.0; st[2] = (double)ratio; st[3] = (double)lp;
+            if (c == 0 && a.out) a.out[row] = lp;
+        }
+        if (c == 0) for (int k = 0; k < 4; ++k) rowv[4 * g + r][k] = st[k];
+    }
+    // ---- dz3 = g (x - mu) / sigma^2 + (bound_weight / n) (min(mu - lo, 0) + max(mu - hi, 0)), lo / hi in normalised action space
+    double viol[4] = {0.0, 0.0, 0.0, 0.0};
+    for (int cb = 0; cb < NB; ++cb)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int col = (2 * cb + j) * 16 + c;
+            const bool live = col < p.A;
+            float lo = 0.0f, hi = 0.0f;
+            if (live && a.bounded) { lo = (a.bmin[col] - p.a_mean[col]) / p.a_std[col]; hi = (a.bmax[col] - p.a_mean[col]) / p.a_std[col]; }
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = row0 + 4 * g + r;
+                if (row >= a.M) continue;
+                float dz = 0.0f;
+                if (live) {
+                    const HeadElem e = head_elem(p, a, row, col, a.z3[(size_t)row * N3 + col]);
+                    dz = gi[r] * (e.u / e.sg);
+                    if (a.bounded) {
+                        const float vlo = fminf(e.mu - lo, 0.0f), vhi = fmaxf(e.mu - hi, 0.0f);
+                        dz = fmaf(a.bwn, vlo + vhi, dz);
+                        viol[r] += (double)vlo * (double)vlo; viol[r] += (double)vhi * (double)vhi;
+                    }
+                }
+                a.dz3[(size_t)row * N3 + col] = live ? bf16_rne(dz) : (uint16_t)0;
+            }
+        }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) lanev[l][r] = viol[r];
+    __syncthreads();
+    if (c == 0)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) { double s = 0.0; for (int k = 0; k < 16; ++k) s += lanev[16 * g + k][r]; rowv[4 * g + r][4] = s; }
+    __syncthreads();
+    if (l < 5) { double s = 0.0; for (int m = 0; m < 16; ++m) s += rowv[m][l]; a.part[(size_t)blockIdx.x * PART_WORDS + l] = s; }
+}
+
+// the partial blocks of k_train_head in a fixed order -> stats (actor: double[6], critic: double[2])
+__global__ void __launch_bounds__(256) k_train_fold(const double* part, int groups, int kind, int n, double* stats) {
+    __shared__ double red[dmb::kThreads];
+    const int t = (int)threadIdx.x, per = (groups + dmb::kThreads - 1) / dmb::kThreads, g0 = t * per, g1 = (g0 + per < groups) ? g0 + per : groups;
+    double tot[5];
+    for (int k = 0; k < 5; ++k) {
+        double s = 0.0;
+        for (int g = g0; g < g1; ++g) s += part[(size_t)g * PART_WORDS + k];
+        tot[k] = dmb::block_sum(s, red);
+        if (kind == HEAD_CRITIC && k == 1) break;
+    }
+    if (t != 0) return;
+    const double dn = (double)n;
+    if (kind == HEAD_CRITIC) { stats[0] = 0.5 * tot[0] / dn; stats[1] = tot[1] / dn; return; }
+    stats[0] = dn; stats[1] = -(tot[0] / dn); stats[2] = 0.5 * tot[4] / dn; stats[3] = tot[1] / dn; stats[4] = tot[2] / dn; stats[5] = tot[3] / dn;
+}
+
+struct WgradArgs { const uint16_t* in; int ldin, K; const uint16_t* dz; int lddz, N; int M; float* dW; };
+
+__global__ void __launch_bounds__(64) k_train_wgrad(WgradArgs a) {
+    constexpr int PITCH = 40;                    // halves per staged row: 80 bytes, so a 16-byte record stays aligned
+    __shared__ alignas(16) uint16_t sa[32 * PITCH];
+    __shared__ alignas(16) uint16_t sb[32 * PITCH];
+    const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
+    const int nbn = (a.N + 31) / 32, k0 = ((int)blockIdx.x / nbn) * 32, n0 = ((int)blockIdx.x % nbn) * 32;
+    const int mr = l >> 1, hf = l & 1;           // staging: this lane moves the 16 columns 16 hf .. of block row mr
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
+    bf16x8 zero;
+#pragma unroll
+    for (int e = 0; e < 8; ++e) dmp::set8(zero, e, 0);
+    for (int m0 = 0; m0 < a.M; m0 += 32) {
+        const int row = m0 + mr;
+#pragma unroll
+        for (int v = 0; v < 2; ++v) {
+            bf16x8 ra = zero, rb = zero;
+            if (row < a.M) {
+                ra = *reinterpret_cast<const bf16x8*>(a.in + (size_t)row * a.ldin + k0 + 16 * hf + 8 * v);
+                rb = *reinterpret_cast<const bf16x8*>(a.dz + (size_t)row * a.lddz + n0 + 16 * hf + 8 * v);
+            }
+            *reinterpret_cast<bf16x8*>(sa + mr * PITCH + 16 * hf + 8 * v) = ra;
+            *reinterpret_cast<bf16x8*>(sb + mr * PITCH + 16 * hf + 8 * v) = rb;
+        }
+        __syncthreads();
+        bf16x8 fa[2], fb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int e = 0; e < 8; ++e) { dmp::set8(fa[i], e, sa[(8 * g + e) * PITCH + 16 * i + c]); dmp::set8(fb[i], e, sb[(8 * g + e) * PITCH + 16 * i + c]); }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
+        __syncthreads();
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = k0 + 16 * i + 4 * g + r, col = n0 + 16 * j + c;
+                if (row < a.K && col < a.N) a.dW[(size_t)row * a.N + col] = acc[i][j][r];
+            }
+}
+
+// four wavefronts per 64 columns: wave s adds the s-th contiguous quarter of the rows, ascending (16 independent loads in flight, added in row order), then the quarters in order
+__global__ void __launch_bounds__(256) k_train_bgrad(const uint16_t* dz, int lddz, int N, int M, float* db) {
+    __shared__ float part[4][64];
+    const int t = (int)threadIdx.x, cl = t & 63, sl = t >> 6, col = (int)blockIdx.x * 64 + cl;
+    const int q = (M + 3) / 4, m0 = sl * q, m1 = (m0 + q < M) ? m0 + q : M;
+    float s = 0.0f;
+    if (col < N) {
+        int m = m0;
+        for (; m + 16 <= m1; m += 16) {
+            uint16_t v[16];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) v[u] = dz[(size_t)(m + u) * lddz + col];
+#pragma unroll
+            for (int u = 0; u < 16; ++u) s += bf16_f32(v[u]);
+        }
+        for (; m < m1; ++m) s += bf16_f32(dz[(size_t)m * lddz + col]);
+    }
+    part[sl][cl] = s;
+    __syncthreads();
+    if (sl == 0 && col < N) db[col] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+}
+
+struct DgradArgs { const uint16_t* dz; int lddz; const float* W; int ldw; const uint16_t* h; int H; int M; uint16_t* out; };
+
+__global__ void __launch_bounds__(64) k_train_dgrad(DgradArgs a) {
+    const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
+    const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, k0 = ((int)blockIdx.x / rbn) * 32;      // consecutive workgroups walk down the rows under one block of W
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
+    const uint16_t* arow[2]; const float* wrow[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = m0 + 16 * i + c;
+        arow[i] = a.dz + (size_t)(row < a.M ? row : 0) * a.lddz + 8 * g;
+        wrow[i] = a.W + (size_t)(k0 + 16 * i + c) * a.ldw + 8 * g;
+    }
+    for (int nk = 0; nk < a.lddz; nk += 32) {
+        bf16x8 fa[2], fb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            fa[i] = *reinterpret_cast<const bf16x8*>(arow[i] + nk);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dmp::set8(fb[i], e, nk + 8 * g + e < a.ldw ? bf16_rne(wrow[i][nk + e]) : (uint16_t)0);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m0 + 16 * i + 4 * g + r, col = k0 + 16 * j + c;
+                if (row < a.M) {
+                    const size_t at = (size_t)row * a.H + col;
+                    a.out[at] = (a.h[at] & 0x7fffu) ? bf16_rne(acc[i][j][r]) : (uint16_t)0;
+                }
+            }
+}
+
+struct SgdArgs { float* w; float* v; const float* g; long long P, mat[3][2]; float lr, mom, wd, gs; unsigned blocks; };
+
+__global__ void __launch_bounds__(256) k_train_sgd(SgdArgs a) {
+    for (long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x; i < a.P; i += (long long)a.blocks * 256) {
+        const float w = a.w[i];
+        // g is carried in fp64, where every product of two floats is exact (a contraction changes nothing), and v is rounded ONCE: under cancellation between
+        // momentum * v and g a chain of fp32 roundings would be off by many ulps of the small result
+        double gg = (double)a.gs * (double)a.g[i];
+        const bool matrix = (i >= a.mat[0][0] && i < a.mat[0][1]) || (i >= a.mat[1][0] && i < a.mat[1][1]) || (i >= a.mat[2][0] && i < a.mat[2][1]);
+        if (matrix) gg += (double)a.wd * (double)w;          // _weight_decay_loss skips the biases
+        const float vv = (float)((double)a.mom * (double)a.v[i] + gg);
+        a.v[i] = vv;
+        a.w[i] = fmaf(-a.lr, vv, w);
+    }
+}
+
+// offsets (in floats) of w1, b1, w2, b2, w3, b3 in a parameter block and its length
+struct Layout { long long o[6], P; };
+inline Layout layout_of(const dmp::PolicyDev& d) {
+    Layout L; const long long S = d.S, H1 = d.H1, H2 = d.H2, A = d.A;
+    L.o[0] = 0; L.o[1] = S * H1; L.o[2] = L.o[1] + H1; L.o[3] = L.o[2] + H1 * H2; L.o[4] = L.o[3] + H2; L.o[5] = L.o[4] + H2 * A; L.P = L.o[5] + A;
+    return L;
+}
+// the caller's workspace: [z3 fp32 n x N3][dz3 bf16 n x N3][dz2 bf16 n x H2][dz1 bf16 n x H1][ceil(n / 16) partial blocks of PART_WORDS doubles]; every piece starts on a multiple of 16 bytes
+struct Work { float* z3; uint16_t *dz3, *dz2, *dz1; double* part; size_t bytes; };
+inline Work carve(const dmp::PolicyDev& d, int n, void* ws) {
+    Work w; char* at = (char*)ws;
+    w.z3 = (float*)at; at += (size_t)n * d.N3 * 4;
+    w.dz3 = (uint16_t*)at; at += (size_t)n * d.N3 * 2;
+    w.dz2 = (uint16_t*)at; at += (size_t)n * d.H2 * 2;
+    w.dz1 = (uint16_t*)at; at += (size_t)n * d.H1 * 2;
+    w.part = (double*)at; at += (size_t)((n + 15) / 16) * PART_WORDS * sizeof(double);
+    w.bytes = (size_t)(at - (char*)ws);
+    return w;
+}
+
+}  // namespace dmt
+
+static int train_net_ok(const char* fn, const dm_policy* p) {
+    if (!p) return fail(std::string(fn) + ": null net");
+    if (p->gated) return fail(std::string(fn) + ": a gated context (dm_policy_create_gated) is not trained here: the plain three-layer nets only");
+    return 0;
+}
+
+// what the two *_grad calls share behind their own checks: the forward pass on the context's per-layer kernels, the head, the fold and the backward pass
+static int train_grad(dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, dmt::HeadArgs& ha, float* grads,
+                      double* stats, void* ws, int64_t ws_bytes, void* hip_stream) {
+    const dmp::PolicyDev& d = p->pd;
+    if (n < 1) return fail(std::string(fn) + ": n must be >= 1");
+    if (!params || !states || !grads || !stats || !ws) return fail(std::string(fn) + ": null argument");
+    if (check_goal(p, fn, "net", goals, goal_dim)) return -1;
+    if ((long long)n * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
+    const dmt::Work w = dmt::carve(d, n, ws);
+    if (ws_bytes < (int64_t)w.bytes) return fail(std::string(fn) + ": workspace too small (dm_train_workspace_bytes)");
+    if ((((uintptr_t)ws) & 15) != 0 || (((uintptr_t)stats) & 7) != 0) return fail(std::string(fn) + ": the workspace must be 16-byte and stats 8-byte aligned");
+    DevGuard guard(p->device_id);
+    rt_stream stream = (rt_stream)hip_stream;
+    if (policy_grow(p, n, stream)) return -1;
+    dmp::PolicyIO io; memset(&io, 0, sizeof(io));
+    io.states = states; io.M = n; io.goals = goal_dim ? goals : nullptr; io.G = goal_dim; io.exp_rate = 1.0f;
+    io.s16 = p->s16; io.h1 = p->h1; io.h2 = p->h2;
+    // the per-layer route as policy_path chooses it for the widths, whatever DM_POLICY_* says
+    const int path = DM_POLICY_PATH_LAYERED(d.H1 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE, d.H2 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE);
+    RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
+    launch_layers<false>(path, n, stream, d, io);
+    const int groups = (n + 15) / 16;
+    ha.M = n; ha.nf = (float)n; ha.z3 = w.z3; ha.dz3 = w.dz3; ha.part = w.part;
+    RT_LAUNCH(dmt::k_train_head, groups, stream, d, (const uint16_t*)p->h2, ha);
+    RT_LAUNCH4(dmt::k_train_fold, 1, stream, (const double*)w.part, groups, ha.kind, n, stats);
+    const dmt::Layout L = dmt::layout_of(d);
+    const uint16_t* in[3] = {p->s16, p->h1, p->h2}; const int ldin[3] = {d.K1, d.H1, d.H2}, K[3] = {d.S, d.H1, d.H2};
+    uint16_t* dz[3] = {w.dz1, w.dz2, w.dz3}; const int lddz[3] = {d.H1, d.H2, d.N3}, N[3] = {d.H1, d.H2, d.A};
+    for (int layer = 2; layer >= 0; --layer) {
+        dmt::WgradArgs wa; wa.in = in[layer]; wa.ldin = ldin[layer]; wa.K = K[layer]; wa.dz = dz[layer]; wa.lddz = lddz[layer]; wa.N = N[layer]; wa.M = n; wa.dW = grads + L.o[2 * layer];
+        RT_LAUNCH(dmt::k_train_wgrad, ((K[layer] + 31) / 32) * ((N[layer] + 31) / 32), stream, wa);
+        RT_LAUNCH4(dmt::k_train_bgrad, (N[layer] + 63) / 64, stream, (const uint16_t*)dz[layer], lddz[layer], N[layer], n, grads + L.o[2 * layer + 1]);
+        if (layer > 0) {
+            dmt::DgradArgs da; da.dz = dz[layer]; da.lddz = lddz[layer]; da.W = params + L.o[2 * layer]; da.ldw = N[layer]; da.h = in[layer]; da.H = K[layer]; da.M = n; da.out = dz[layer - 1];
+            RT_LAUNCH(dmt::k_train_dgrad, ((n + 31) / 32) * (K[layer] / 32), stream, da);
+        }
+    }
+    return launch_status(0);
+}
+
+extern "C" {
+
+int64_t dm_train_param_count(const dm_policy* net) {
+    if (train_net_ok("dm_train_param_count", net)) return -1;
+    return (int64_t)dmt::layout_of(net->pd).P;
+}
+
+int64_t dm_train_workspace_bytes(const dm_policy* net, int n) {
+    if (train_net_ok("dm_train_workspace_bytes", net)) return -1;
+    if (n < 1) { fail("dm_train_workspace_bytes: n must be >= 1"); return -1; }
+    return (int64_t)dmt::carve(net->pd, n, nullptr).bytes;
+}
+
+int dm_train_actor_grad(dm_policy* net, const float* params_dev, const float* states_dev, const float* goals_dev, int goal_dim, int n, const float* actions_dev,
+                        const float* old_logp_dev, const float* adv_dev, const dm_train_actor_cfg* cfg, float* grads_dev, double* stats_dev, float* logp_out,
+                        void* workspace, int64_t workspace_bytes, void* hip_stream) {
+    const char* fn = "dm_train_actor_grad";
+    if (train_net_ok(fn, net)) return -1;
+    if (!actions_dev || !old_logp_dev || !adv_dev || !cfg) return fail(std::string(fn) + ": null argument");
+    if (!(cfg->ratio_clip > 0.0)) return fail(std::string(fn) + ": ratio_clip must be > 0");
+    if (!(cfg->bound_weight >= 0.0)) return fail(std::string(fn) + ": bound_weight must be >= 0");
+    if ((cfg->a_bound_min == nullptr) != (cfg->a_bound_max == nullptr)) return fail(std::string(fn) + ": a_bound_min and a_bound_max come together (both NULL: no bound loss)");
+    const dmp::PolicyDev& d = net->pd;
+    if (!d.logstd || !d.a_mean || !d.a_std) return fail(std::string(fn) + ": the context holds no logstd / a_mean / a_std");
+    if (d.A > dmt::kMaxA) return fail(std::string(fn) + ": action_dim above 128 is not compiled (the action bounds ride in the kernel arguments)");
+    dmt::HeadArgs ha; memset(&ha, 0, sizeof(ha));
+    ha.kind = dmt::HEAD_ACTOR; ha.actions = actions_dev; ha.old_logp = old_logp_dev; ha.adv = adv_dev; ha.out = logp_out;
+    ha.eps = (float)cfg->ratio_clip; ha.clip_lo = 1.0f - ha.eps; ha.clip_hi = 1.0f + ha.eps;
+    ha.bounded = cfg->a_bound_min ? 1 : 0;
+    ha.c0 = (-0.5f * (float)d.A) * 1.8378770664093453f;
+    if (n >= 1) ha.bwn = (float)cfg->bound_weight / (float)n;
+    if (ha.bounded) for (int j = 0; j < d.A; ++j) { ha.bmin[j] = cfg->a_bound_min[j]; ha.bmax[j] = cfg->a_bound_max[j]; }
+    return train_grad(net, fn, params_dev, states_dev, goals_dev, goal_dim, n, ha, grads_dev, stats_dev, workspace, workspace_bytes, hip_stream);
+}
+
+int dm_train_value_grad(dm_policy* net, const float* params_dev, const float* states_dev, const float* goals_dev, int goal_dim, int n, const float* targets_dev,
+                        float* grads_dev, double* stats_dev, float* values_out, void* workspace, int64_t workspace_bytes, void* hip_stream) {
+    const char* fn = "dm_train_value_grad";
+    if (train_net_ok(fn, net)) return -1;
+    if (net->pd.A != 1) return fail(std::string(fn) + ": the context has action_dim " + std::to_string(net->pd.A) + ", the value head needs a net with one output");
+    if (!targets_dev) return fail(std::string(fn) + ": null argument");
+    dmt::HeadArgs ha; memset(&ha, 0, sizeof(ha));
+    ha.kind = dmt::HEAD_CRITIC; ha.targets = targets_dev; ha.out = values_out;
+    return train_grad(net, fn, params_dev, states_dev, goals_dev, goal_dim, n, ha, grads_dev, stats_dev, workspace, workspace_bytes, hip_stream);
+}
+
+int dm_train_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum, double weight_decay,
+                      double grad_scale, void* hip_stream) {
+    const char* fn = "dm_train_sgd_step";
+    if (net && train_net_ok(fn, net)) return -1;
+    if (!params_dev || !momentum_dev || !grads_dev) return fail(std::string(fn) + ": null argument");
+    if (P < 1) return fail(std::string(fn) + ": P must be >= 1");
+    if (!(stepsize >= 0.0 && std::isfinite(stepsize))) return fail(std::string(fn) + ": stepsize must be finite and >= 0");
+    if (!(momentum >= 0.0 && std::isfinite(momentum))) return fail(std::string(fn) + ": momentum must be finite and >= 0");
+    if (!(weight_decay >= 0.0 && std::isfinite(weight_decay))) return fail(std::string(fn) + ": weight_decay must be finite and >= 0");
+    if (!std::isfinite(grad_scale)) return fail(std::string(fn) + ": grad_scale must be finite");
+    dmt::SgdArgs a; memset(&a, 0, sizeof(a));
+    dmt::Layout L; memset(&L, 0, sizeof(L));
+    if (net) {
+        L = dmt::layout_of(net->pd);
+        if (P != L.P) return fail(std::string(fn) + ": P is " + std::to_string((long long)P) + ", the net has " + std::to_string(L.P) + " parameters (dm_train_param_count)");
+        for (int k = 0; k < 3; ++k) { a.mat[k][0] = L.o[2 * k]; a.mat[k][1] = L.o[2 * k + 1]; }
+    } else if (weight_decay != 0.0) return fail(std::string(fn) + ": weight_decay needs the net (which entries are matrices is its layout)");
+    a.w = params_dev; a.v = momentum_dev; a.g = grads_dev; a.P = P; a.lr = (float)stepsize; a.mom = (float)momentum; a.wd = (float)weight_decay; a.gs = (float)grad_scale;
+    a.blocks = (unsigned)std::min<int64_t>((P + 255) / 256, 4096);
+    rt_stream stream = (rt_stream)hip_stream;
+    if (!net) {                                   // no context: the step alone, on the calling thread's current device
+        RT_LAUNCH4(dmt::k_train_sgd, a.blocks, stream, a);
+        return launch_status(0);
+    }
+    DevGuard guard(net->device_id);
+    RT_LAUNCH4(dmt::k_train_sgd, a.blocks, stream, a);
+    if (launch_status(0)) return -1;
+    // the new masters into the context: dm_policy_set_weights with DM_DEVICE_PTRS on views of params_dev
+    const dmp::PolicyDev& d = net->pd;
+    dm_policy_params pp; memset(&pp, 0, sizeof(pp));
+    pp.state_dim = d.S; pp.hidden1 = d.H1; pp.hidden2 = d.H2; pp.action_dim = d.A;
+    pp.w1 = params_dev + L.o[0]; pp.b1 = params_dev + L.o[1]; pp.w2 = params_dev + L.o[2]; pp.b2 = params_dev + L.o[3]; pp.w3 = params_dev + L.o[4]; pp.b3 = params_dev + L.o[5];
+    return policy_pack(net, pp, nullptr, DM_DEVICE_PTRS, stream);
+}
+
+int dm_train_read_activations(dm_policy* net, int which, int n, void* host_out, size_t capacity) {
+    const char* fn = "dm_train_read_activations";
+    if (train_net_ok(fn, net)) return -1;
+    if (!host_out) return fail(std::string(fn) + ": null argument");
+    if (which < 0 || which > 2) return fail(std::string(fn) + ": which must be 0 (s16), 1 (h1) or 2 (h2)");
+    if (n < 1 || n > net->cap) return fail(std::string(fn) + ": n must be in [1, rows the context holds]");
+    const dmp::PolicyDev& d = net->pd;
+    const size_t bytes = (size_t)n * (which == 0 ? d.K1 : (which == 1 ? d.H1 : d.H2)) * 2;
+    if (capacity < bytes) return fail(std::string(fn) + ": the host buffer is smaller than the array (" + std::to_string(bytes) + " bytes)");
+    DevGuard guard(net->device_id);
+#ifndef DM_EMU
+    if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
+#endif
+    return rt_d2h(host_out, which == 0 ? net->s16 : (which == 1 ? net->h1 : net->h2), bytes, 0) == 0 ? 0 : fail("device to host copy failed");
+}
+
+}  // extern "C"

@@ -1,0 +1,408 @@
+"""PPO actor and critic minibatch updates on the device (libdm_hip.so `dm_train_*`, deepmimic_amd/csrc/dm_train.h, include/dm_hip.h): what the reference's
+PPOAgent._update_actor / _update_critic and MPISolver.update do (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain
+three-layer nets, on the `Policy` context that samples -- the forward pass runs on the context's own kernels, so the trained net IS the sampling net.
+
+    tr = ActorTrainer.from_policy(actor, weights, stepsize=..., momentum=0.9)       # owns the [3, P] tensor (params, momentum, grads) and the workspace
+    tr.grad(states, actions, old_logp, adv, goals=...)                               # gradients into tr.grads, statistics into tr.stats()
+    all_reduce_gradients(tr)                                                         # (deepmimic_amd/dist.py, several ranks)
+    tr.step(grad_scale=1.0 / world)                                                  # momentum SGD on the fp32 masters, then the refresh of the context
+
+A checkpoint is `torch.save(tr.buf)`.  Gated contexts, the AMP discriminator update, Adam, a fused training kernel and step-size schedules are out of scope.
+
+`reference_grad` / `reference_step` are the numpy statements of the arithmetic (the specification of include/dm_hip.h): the same rounding points -- bf16 operands, the head's
+fp32 operations one by one, the library's own exp -- with the contractions accumulated in float64."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Optional
+
+import numpy as np
+
+from .binding import check, stream_handle, tensor_arg, vp
+
+KEYS = ("w1", "b1", "w2", "b2", "w3", "b3")
+LN_2PI = np.float32(1.8378770664093453)
+
+
+class _ActorCfg(C.Structure):
+    _fields_ = [("ratio_clip", C.c_double), ("bound_weight", C.c_double), ("a_bound_min", C.POINTER(C.c_float)), ("a_bound_max", C.POINTER(C.c_float))]
+
+
+# ---- the parameter block and the workspace
+
+def layout(S: int, H1: int, H2: int, A: int) -> dict:
+    """{key: (offset in floats, shape)} of the parameter block, and "P" -> its length"""
+    shapes = dict(w1=(S, H1), b1=(H1,), w2=(H1, H2), b2=(H2,), w3=(H2, A), b3=(A,))
+    out, at = {}, 0
+    for k in KEYS:
+        out[k] = (at, shapes[k]); at += int(np.prod(shapes[k]))
+    out["P"] = at
+    return out
+
+
+def pack_params(weights: dict) -> np.ndarray:
+    """the float32 parameter block of a weights dict (w1 .. b3, tf.layers.dense layout)"""
+    return np.concatenate([np.ascontiguousarray(weights[k], dtype=np.float32).reshape(-1) for k in KEYS])
+
+
+def unpack_params(flat, S: int, H1: int, H2: int, A: int) -> dict:
+    """views of a parameter block under the keys w1 .. b3 (numpy array or torch tensor)"""
+    lay = layout(S, H1, H2, A)
+    return {k: flat[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))].reshape(lay[k][1]) for k in KEYS}
+
+
+def workspace_layout(H1: int, H2: int, A: int, n: int) -> dict:
+    """{name: (byte offset, dtype, shape)} of what a *_grad call leaves in its workspace (include/dm_hip.h); "bytes": the total"""
+    N3 = (A + 31) // 32 * 32
+    out, at = {}, 0
+    for name, dt, shape in (("z3", np.float32, (n, N3)), ("dz3", np.uint16, (n, N3)), ("dz2", np.uint16, (n, H2)), ("dz1", np.uint16, (n, H1)),
+                            ("part", np.float64, ((n + 15) // 16, 8))):
+        out[name] = (at, dt, shape); at += int(np.prod(shape)) * np.dtype(dt).itemsize
+    out["bytes"] = at
+    return out
+
+
+def param_count(policy) -> int:
+    n = policy.lib.dm_train_param_count(policy.h)
+    check(policy.lib, n < 0)
+    return int(n)
+
+
+def workspace_bytes(policy, n: int) -> int:
+    b = policy.lib.dm_train_workspace_bytes(policy.h, int(n))
+    check(policy.lib, b < 0)
+    return int(b)
+
+
+def _need(policy):
+    if not hasattr(policy.lib, "dm_train_actor_grad"):
+        raise RuntimeError("libdm_hip: this library has no dm_train_* entry points (rebuild it)")
+
+
+def actor_grad_device(policy, params_ptr: int, states_ptr: int, n: int, actions_ptr: int, old_logp_ptr: int, adv_ptr: int, grads_ptr: int, stats_ptr: int,
+                      workspace_ptr: int, workspace_nbytes: int, ratio_clip: float = 0.2, bound_weight: float = 10.0, a_bound_min=None, a_bound_max=None,
+                      goals_ptr: int = 0, goal_dim: int = 0, logp_ptr: int = 0, stream: int = 0):
+    """raw device pointers (ints); a_bound_min / a_bound_max: host arrays of A un-normalised entries or None; asynchronous on `stream`"""
+    _need(policy)
+    lo = None if a_bound_min is None else np.ascontiguousarray(a_bound_min, dtype=np.float32)
+    hi = None if a_bound_max is None else np.ascontiguousarray(a_bound_max, dtype=np.float32)
+    for b in (lo, hi):
+        if b is not None and b.shape != (policy.A,):
+            raise ValueError("action bounds must have %d entries" % policy.A)
+    fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
+    cfg = _ActorCfg(float(ratio_clip), float(bound_weight), fp(lo), fp(hi))
+    check(policy.lib, policy.lib.dm_train_actor_grad(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(actions_ptr), vp(old_logp_ptr),
+                                                     vp(adv_ptr), C.cast(C.pointer(cfg), C.c_void_p), vp(grads_ptr), vp(stats_ptr), vp(logp_ptr), vp(workspace_ptr),
+                                                     int(workspace_nbytes), vp(stream)))
+
+
+def value_grad_device(policy, params_ptr: int, states_ptr: int, n: int, targets_ptr: int, grads_ptr: int, stats_ptr: int, workspace_ptr: int, workspace_nbytes: int,
+                      goals_ptr: int = 0, goal_dim: int = 0, values_ptr: int = 0, stream: int = 0):
+    _need(policy)
+    check(policy.lib, policy.lib.dm_train_value_grad(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(targets_ptr), vp(grads_ptr),
+                                                     vp(stats_ptr), vp(values_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
+
+
+def sgd_step_device(policy, params_ptr: int, momentum_ptr: int, grads_ptr: int, P: int, stepsize: float, momentum: float, weight_decay: float = 0.0,
+                    grad_scale: float = 1.0, stream: int = 0, lib=None):
+    """policy None: the step alone (pass `lib`); with a policy its context is refreshed from the new masters"""
+    lib = policy.lib if policy is not None else lib
+    if not hasattr(lib, "dm_train_sgd_step"):
+        raise RuntimeError("libdm_hip: this library has no dm_train_* entry points (rebuild it)")
+    check(lib, lib.dm_train_sgd_step(policy.h if policy is not None else None, vp(params_ptr), vp(momentum_ptr), vp(grads_ptr), int(P), float(stepsize), float(momentum),
+                                     float(weight_decay), float(grad_scale), vp(stream)))
+
+
+def read_activations(policy, which: str, n: int) -> np.ndarray:
+    """test support: the first n rows of "s16" [n, K1], "h1" or "h2" as the last call left them, bf16 bits (uint16); synchronises"""
+    _need(policy)
+    width = dict(s16=policy.info()["K1"], h1=policy.H1, h2=policy.H2)[which]
+    out = np.zeros((int(n), width), np.uint16)
+    check(policy.lib, policy.lib.dm_train_read_activations(policy.h, ("s16", "h1", "h2").index(which), int(n), out.ctypes.data, out.nbytes))
+    return out
+
+
+# ---- the trainers
+
+class _Trainer:
+    """Owns buf [3, P] float32 = (params, momentum, grads) and the workspace, on `device` (the policy's GPU; "cpu" with the emulator build of the tests, where device
+    memory is host memory).  Every call runs on torch's current stream."""
+    N_STATS = 0
+
+    def __init__(self, policy, buf, stepsize: float, momentum: float, weight_decay: float):
+        import torch
+        _need(policy)
+        self.policy, self.buf = policy, buf
+        self.P = param_count(policy)
+        tensor_arg("buf", buf, buf.device, torch.float32, [(3, self.P)])
+        self.device = buf.device
+        self.params, self.momentum, self.grads = buf[0], buf[1], buf[2]
+        self.stepsize, self.mom, self.weight_decay = float(stepsize), float(momentum), float(weight_decay)
+        self._stats = torch.zeros(self.N_STATS, dtype=torch.float64, device=self.device)
+        self._work, self._work_bytes, self._work_rows = None, 0, 0
+
+    @classmethod
+    def from_policy(cls, policy, weights: dict, stepsize: float, momentum: float = 0.9, weight_decay: float = 0.0, device=None):
+        """masters from the weights dict the policy was built from (zero momentum), then `sync()`"""
+        import torch
+        dev = torch.device("cuda", policy.device_id) if device is None else torch.device(device)
+        flat = pack_params(weights)
+        buf = torch.zeros((3, flat.size), dtype=torch.float32, device=dev)
+        buf[0].copy_(torch.from_numpy(flat))
+        tr = cls(policy, buf, stepsize, momentum, weight_decay)
+        tr.sync()
+        return tr
+
+    def _stream(self):
+        return stream_handle(self.device) if self.device.type == "cuda" else 0
+
+    def views(self, which: str = "params") -> dict:
+        """w1 .. b3 as views of params / momentum / grads"""
+        p = self.policy
+        return unpack_params(getattr(self, which), p.S, p.H1, p.H2, p.A)
+
+    def sync(self):
+        """packs the masters into the context (the precondition of grad: its bf16 weights are the rounding of params)"""
+        self.policy.set_weights_device({k: v.data_ptr() for k, v in self.views().items()}, stream=self._stream())
+
+    def _workspace(self, n: int):
+        import torch
+        if n > self._work_rows:
+            self._work_bytes = workspace_bytes(self.policy, n)
+            self._work = torch.zeros((self._work_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
+            self._work_rows = n
+        return self._work.data_ptr(), self._work_bytes
+
+    def _rows(self, states, goals):
+        import torch
+        n = int(states.shape[0]) if states.dim() == 2 else -1
+        G = 0 if goals is None else (int(goals.shape[1]) if goals.dim() == 2 else -1)
+        tensor_arg("states", states, self.device, torch.float32, [(n, self.policy.S - max(G, 0))])
+        if goals is not None:
+            tensor_arg("goals", goals, self.device, torch.float32, [(n, G)])
+        return n, G
+
+    def step(self, grad_scale: float = 1.0):
+        sgd_step_device(self.policy, self.params.data_ptr(), self.momentum.data_ptr(), self.grads.data_ptr(), self.P, self.stepsize, self.mom, self.weight_decay,
+                        grad_scale, stream=self._stream())
+
+    def stats(self):
+        """the statistics of the last grad call, a float64 device tensor (no synchronisation here)"""
+        return self._stats
+
+
+class ActorTrainer(_Trainer):
+    """stats(): {n, -mean min(l0, l1), bound loss, clip_frac, mean ratio, mean logp_new}"""
+    N_STATS = 6
+
+    def grad(self, states, actions, old_logp, adv, goals=None, ratio_clip: float = 0.2, bound_weight: float = 10.0, a_bound_min=None, a_bound_max=None, logp_out=None):
+        import torch
+        n, G = self._rows(states, goals)
+        tensor_arg("actions", actions, self.device, torch.float32, [(n, self.policy.A)])
+        tensor_arg("old_logp", old_logp, self.device, torch.float32, [(n,)]); tensor_arg("adv", adv, self.device, torch.float32, [(n,)])
+        if logp_out is not None:
+            tensor_arg("logp_out", logp_out, self.device, torch.float32, [(n,)])
+        ws, nbytes = self._workspace(n)
+        actor_grad_device(self.policy, self.params.data_ptr(), states.data_ptr(), n, actions.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), self.grads.data_ptr(),
+                          self._stats.data_ptr(), ws, nbytes, ratio_clip, bound_weight, a_bound_min, a_bound_max, 0 if goals is None else goals.data_ptr(), G,
+                          0 if logp_out is None else logp_out.data_ptr(), self._stream())
+
+
+class CriticTrainer(_Trainer):
+    """stats(): {0.5 mean (tar - v)^2, mean v}"""
+    N_STATS = 2
+
+    def grad(self, states, targets, goals=None, values_out=None):
+        import torch
+        n, G = self._rows(states, goals)
+        tensor_arg("targets", targets, self.device, torch.float32, [(n,)])
+        if values_out is not None:
+            tensor_arg("values_out", values_out, self.device, torch.float32, [(n,)])
+        ws, nbytes = self._workspace(n)
+        value_grad_device(self.policy, self.params.data_ptr(), states.data_ptr(), n, targets.data_ptr(), self.grads.data_ptr(), self._stats.data_ptr(), ws, nbytes,
+                          0 if goals is None else goals.data_ptr(), G, 0 if values_out is None else values_out.data_ptr(), self._stream())
+
+
+# ---- numpy statements of the arithmetic (host; the tests hold the kernels to them)
+
+def bf16_bits(x) -> np.ndarray:
+    """round-to-nearest-even bf16 of float32 values, as uint16 bits; a NaN stays a quiet NaN"""
+    u = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
+    nan = (u & 0x7FFFFFFF) > 0x7F800000
+    r = ((u + 0x7FFF + ((u >> 16) & 1)) >> 16) & 0xFFFF
+    return np.where(nan, (u >> 16) | 0x40, r).astype(np.uint16)
+
+
+def bf16_value(bits) -> np.ndarray:
+    return (np.asarray(bits, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
+
+
+def bf16_round(x) -> np.ndarray:
+    return bf16_value(bf16_bits(x))
+
+
+def fma32(a, b, c) -> np.ndarray:
+    """fmaf on float32 arrays, one rounding: the product is exact in float64, the sum is rounded to odd there (Boldo-Melquiond), then to float32"""
+    a, b, c = (np.asarray(v, dtype=np.float32).astype(np.float64) for v in (a, b, c))
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p
+        err = (p - (s - bb)) + (c - bb)
+        fix = np.isfinite(s) & (err != 0) & ((s.view(np.int64) & 1) == 0)
+        s = np.where(fix, np.nextafter(s, np.where(err > 0, np.inf, -np.inf)), s)
+        return s.astype(np.float32)
+
+
+def reference_exp(x) -> np.ndarray:
+    """dm_train.h exp_det, operation by operation, in float32"""
+    f = np.float32
+    x = np.asarray(x, dtype=f)
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        xc = np.minimum(np.maximum(x, f(-104.0)), f(89.0))
+        xc = np.where(np.isnan(x), f(0), xc)
+        kf = np.rint(xc * f(1.44269504088896341))
+        r = fma32(kf, f(-0.693359375), xc); r = fma32(kf, f(2.12194440e-4), r)
+        p = fma32(r, f(1.9875691500e-4), f(1.3981999507e-3))
+        for coef in (8.3334519073e-3, 4.1665795894e-2, 1.6666665459e-1, 5.0000001201e-1):
+            p = fma32(p, r, f(coef))
+        y = fma32(p, r * r, r) + f(1.0)
+        out = np.ldexp(y, kf.astype(np.int32)).astype(f)
+        return np.where(np.isnan(x), x, out)
+
+
+def _tree16(v):
+    """the sum over the last axis (16 lanes) as the xor butterfly takes it: adjacent pairs, four times; float32"""
+    for _ in range(4):
+        v = v[..., 0::2] + v[..., 1::2]
+    return v[..., 0]
+
+
+def _lane_sum(terms, N3: int):
+    """sum over the N3 columns (zeros in the padding) as k_train_head takes it: lane c adds its columns c, 16 + c, .. ascending, then the tree over c; float32"""
+    t = terms.reshape(terms.shape[:-1] + (N3 // 16, 16))
+    s = np.zeros(t.shape[:-2] + (16,), np.float32)
+    for b in range(N3 // 16):
+        s = s + t[..., b, :]
+    return _tree16(s)
+
+
+def reference_actor_head(z3, actions, old_logp, adv, a_mean, a_std, logstd, ratio_clip=0.2, bound_weight=10.0, a_bound_min=None, a_bound_max=None):
+    """The actor head on given z3 [n, >= A] float32 (the padding columns are ignored), every operation in float32 as k_train_head orders it: dict(dz3 [n, N3] uint16 bf16 bits,
+    logp [n], g [n], ratio [n], stats float64[6]).  Exact: the kernel's bits on the same z3."""
+    f = np.float32
+    n, A = actions.shape
+    N3 = (A + 31) // 32 * 32
+    mu = np.zeros((n, N3), f); mu[:, :A] = np.asarray(z3, f)[:, :A]
+    a_mean, a_std, logstd = (np.asarray(v, f) for v in (a_mean, a_std, logstd))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        x = (np.asarray(actions, f) - a_mean) / a_std
+        sg = reference_exp(logstd)
+        u = np.zeros((n, N3), f); u[:, :A] = (x - mu[:, :A]) / sg
+        # q: per lane fmaf(u, u, q) over its columns ascending, then the tree
+        ub = u.reshape(n, N3 // 16, 16)
+        q = np.zeros((n, 16), f)
+        for b in range(N3 // 16):
+            live = (16 * b + np.arange(16)) < A
+            q = np.where(live, fma32(ub[:, b], ub[:, b], q), q)
+        q = _tree16(q)
+        ls = np.zeros(N3, f); ls[:A] = logstd
+        sls = _lane_sum(ls, N3)
+        cst = (f(-0.5) * f(A)) * LN_2PI - sls
+        logp = fma32(f(-0.5), q, cst)
+        ratio = reference_exp(logp - np.asarray(old_logp, f))
+        eps = f(ratio_clip); lo_c, hi_c = f(1.0) - eps, f(1.0) + eps
+        adv = np.asarray(adv, f); nf = f(n)
+        l0 = adv * ratio; l1 = adv * np.minimum(np.maximum(ratio, lo_c), hi_c)
+        first = ~(l0 > l1)
+        g = np.where(first, -(l0 / nf), f(0)).astype(f)
+        dz = (g[:, None] * (u[:, :A] / sg)).astype(f)
+        viol = np.zeros(n)
+        if a_bound_min is not None:
+            lo = (np.asarray(a_bound_min, f) - a_mean) / a_std; hi = (np.asarray(a_bound_max, f) - a_mean) / a_std
+            vlo = np.minimum(mu[:, :A] - lo, f(0)); vhi = np.maximum(mu[:, :A] - hi, f(0))
+            dz = fma32(f(bound_weight) / nf, vlo + vhi, dz)
+            viol = (vlo.astype(np.float64) ** 2 + vhi.astype(np.float64) ** 2).sum(axis=1)
+        bits = np.zeros((n, N3), np.uint16); bits[:, :A] = bf16_bits(dz)
+        dn = float(n)
+        stats = np.array([dn, -(np.where(first, l0, l1).astype(np.float64).sum() / dn), 0.5 * viol.sum() / dn,
+                          (np.abs(ratio - f(1.0)) > eps).sum() / dn, ratio.astype(np.float64).sum() / dn, logp.astype(np.float64).sum() / dn])
+    return dict(dz3=bits, logp=logp, g=g, ratio=ratio, stats=stats)
+
+
+def reference_value_head(z3, targets):
+    """the critic head on given z3 [n, >= 1]: dict(dz3 [n, 32] bf16 bits, values [n], stats float64[2])"""
+    f = np.float32
+    v = np.asarray(z3, f)[:, 0]; n = v.shape[0]
+    e = v - np.asarray(targets, f)
+    bits = np.zeros((n, 32), np.uint16); bits[:, 0] = bf16_bits(e / f(n))
+    return dict(dz3=bits, values=v, stats=np.array([0.5 * (e.astype(np.float64) ** 2).sum() / n, v.astype(np.float64).sum() / n]))
+
+
+def reference_forward_bf16(weights: dict, states, s_clip=np.inf):
+    """s16 [n, S], h1, h2 as bf16 VALUES (float32) and z3 [n, A] float32 of the plain actor: the rounding points of the device forward, float64 accumulation"""
+    f = np.float32
+    s = np.asarray(states, f)
+    sm, ss = weights.get("s_mean"), weights.get("s_std")
+    x = (s - (f(0) if sm is None else np.asarray(sm, f))) * (f(1) / (f(1) if ss is None else np.asarray(ss, f)))
+    s16 = bf16_round(np.clip(x, -s_clip, s_clip))
+    lin = lambda h, w, b: (h.astype(np.float64) @ bf16_round(weights[w]).astype(np.float64)).astype(f) + np.asarray(weights[b], f)
+    h1 = bf16_round(np.maximum(lin(s16, "w1", "b1"), f(0)))
+    h2 = bf16_round(np.maximum(lin(h1, "w2", "b2"), f(0)))
+    return s16, h1, h2, lin(h2, "w3", "b3")
+
+
+def reference_backward(weights: dict, s16, h1, h2, dz3_bits):
+    """the backward pass from bf16 dz3 [n, N3] (bits) and the saved bf16 activations (values): dict(grads float32 [P], dz2, dz1 bf16 bits); float64 accumulation"""
+    f = np.float32
+    A = np.asarray(weights["w3"]).shape[1]
+    dz3 = bf16_value(dz3_bits)[:, :A].astype(np.float64)
+    g = {}
+    g["w3"] = h2.astype(np.float64).T @ dz3; g["b3"] = dz3.sum(axis=0)
+    dz2_bits = bf16_bits(np.where(h2 != 0, (dz3 @ bf16_round(weights["w3"]).astype(np.float64).T).astype(f), f(0)))
+    dz2 = bf16_value(dz2_bits).astype(np.float64)
+    g["w2"] = h1.astype(np.float64).T @ dz2; g["b2"] = dz2.sum(axis=0)
+    dz1_bits = bf16_bits(np.where(h1 != 0, (dz2 @ bf16_round(weights["w2"]).astype(np.float64).T).astype(f), f(0)))
+    dz1 = bf16_value(dz1_bits).astype(np.float64)
+    g["w1"] = s16.astype(np.float64).T @ dz1; g["b1"] = dz1.sum(axis=0)
+    return dict(grads=np.concatenate([g[k].astype(f).reshape(-1) for k in KEYS]), dz2=dz2_bits, dz1=dz1_bits)
+
+
+def reference_grad(weights: dict, states, head: str, s_clip=np.inf, **kw):
+    """The whole *_grad call in numpy.  head "actor": kw = actions, old_logp, adv[, ratio_clip, bound_weight, a_bound_min, a_bound_max] (a_mean, a_std, logstd from the
+    weights); head "critic": kw = targets.  `states` holds the goal columns.  dict(grads, stats, dz3, dz2, dz1, z3, s16, h1, h2 and the head's own outputs)."""
+    s16, h1, h2, z3 = reference_forward_bf16(weights, states, s_clip)
+    if head == "actor":
+        A = z3.shape[1]
+        dflt = lambda k, v: np.full(A, v, np.float32) if weights.get(k) is None else weights[k]
+        hd = reference_actor_head(z3, a_mean=dflt("a_mean", 0), a_std=dflt("a_std", 1), logstd=dflt("logstd", 0), **kw)
+    else:
+        hd = reference_value_head(z3, **kw)
+    out = dict(hd); out.update(reference_backward(weights, s16, h1, h2, hd["dz3"]))
+    out.update(z3=z3, s16=s16, h1=h1, h2=h2)
+    return out
+
+
+def reference_step(params, momentum, grads, stepsize, mom, weight_decay=0.0, grad_scale=1.0, matrix_mask=None, exact=True):
+    """The momentum step per element: g = grad_scale grad (+ weight_decay w on the entries of matrix_mask, `matrix_mask_of`) and v = mom v + g in float64, where the
+    products of float32 values are exact, v rounded to float32 once; then the master from the stored v.  exact: w = fmaf(-stepsize, v, w), the kernel's bits; else
+    w - stepsize v in float64, rounded once.  Returns (params, momentum)."""
+    f = np.float32
+    w, v, g = (np.asarray(a, f) for a in (params, momentum, grads))
+    mask = np.zeros(w.shape, bool) if matrix_mask is None else np.asarray(matrix_mask, bool)
+    lr, mo, wd, gs = (float(f(x)) for x in (stepsize, mom, weight_decay, grad_scale))
+    w64 = w.astype(np.float64)
+    gg = gs * g.astype(np.float64)
+    gg = np.where(mask, gg + wd * w64, gg)
+    vv = (mo * v.astype(np.float64) + gg).astype(f)
+    if exact:
+        return fma32(f(-lr), vv, w), vv
+    return (w64 - lr * vv.astype(np.float64)).astype(f), vv
+
+
+def matrix_mask_of(S: int, H1: int, H2: int, A: int) -> np.ndarray:
+    lay = layout(S, H1, H2, A)
+    m = np.zeros(lay["P"], bool)
+    for k in ("w1", "w2", "w3"):
+        m[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))] = True
+    return m

@@ -716,6 +716,68 @@ int dm_time_warp_align(int device_id, int n_envs, int capacity, int dim, int f64
                        const int32_t* select_dev /* NULL: all */, double term_step_cost, float* reward_out_dev /* [N] */, double* cost_out_dev /* NULL or [N] */,
                        void* hip_stream);
 
+/* ---- PPO actor and critic minibatch updates on the device (deepmimic_amd/csrc/dm_train.h, deepmimic_amd/train.py): PPOAgent._update_actor / _update_critic and
+ * MPISolver.update (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples, so that
+ * exp(logp_new - logp_old) is 1 (to rounding) at the weights that sampled.  Stateless like dm_ppo_*, dm_replay_* and dm_episode_stats: the caller owns every byte, all
+ * pointers are DEVICE pointers, calls are asynchronous on hip_stream, nothing is read on the host or synchronised inside, a refused call launches nothing, writes nothing
+ * and names its reason through dm_last_error.  The one object is the dm_policy whose net is trained: its packed bf16 weights and its activation buffers s16 / h1 / h2 are
+ * read and written; the buffers grow to the largest n as in dm_policy_forward_ex (the one allocation).  ORDERING: like dm_policy_set_weights, a training call must not
+ * run while another stream runs a forward, a scalar evaluation, a refresh or another training call of the same context -- order them with events or use one stream.
+ * Out of scope: gated contexts, the AMP discriminator update (its gradient penalty needs a second derivative), Adam, one fused training kernel, step-size schedules
+ * (the step size is an argument).
+ *
+ * Parameter block: P = dm_train_param_count(net) floats in the order w1 [S x H1], b1, w2 [H1 x H2], b2, w3 [H2 x A], b3; matrices in tf.layers.dense layout (in x out,
+ * row-major), true widths, no padding.  The caller holds three such arrays: masters, momentum, gradients.
+ * PRECONDITION of the two *_grad calls: the net's packed weights are the round-to-nearest-even bf16 of params_dev (the backward pass multiplies by the bf16 of the
+ * masters, the forward pass by the packed arrays).  dm_train_sgd_step with the net keeps this true; dm_policy_set_weights from the block establishes it.
+ *
+ * Arithmetic (the specification; deepmimic_amd/train.py reference_grad / reference_step state it in numpy):
+ *   forward   k_policy_prep and layers 1 and 2 on the context's per-layer kernels as the widths choose them, whatever DM_POLICY_* says, with the bound observation
+ *             normaliser: s16, h1, h2 in bf16; z3 = h2 w3 + b3 with fp32 accumulation of bf16 products (the chain of the sampling net's layer 3).  logstd is not trained
+ *             (StdType.Default).
+ *   actor     per row i, all in fp32 with one rounding per written operation: x = (a - a_mean) / a_std, sigma = exp(logstd), mu = z3, u_j = (x_j - mu_j) / sigma_j,
+ *             logp = fmaf(-0.5, sum_j u_j^2, (-0.5 A) ln 2pi - sum_j logstd_j), ratio = exp(logp - old_logp), l0 = adv ratio, l1 = adv clip(ratio, 1 - eps, 1 + eps),
+ *             g_i = -(l0 / n) unless l0 > l1, else 0 (tf.minimum sends the gradient of a tie to its first argument),
+ *             dz3_ij = fmaf(bound_weight / n, min(mu_j - lo_j, 0) + max(mu_j - hi_j, 0), g_i (u_j / sigma_j)), lo / hi = (bound - a_mean) / a_std (learning/pg_agent.py:189-202,
+ *             tf_util.py:65-81).  exp is the library's own (dm_train.h exp_det: every rounding point written down, within 2 ulp), the row sums run over each lane's
+ *             columns c, 16 + c, .. ascending and then a pairwise tree over c.
+ *   critic    dz3_i = (v_i - tar_i) / n; no value clip, as in the reference's training graph.
+ *   stats     fp64 sums in a fixed order (per 16 rows in row order, the blocks by contiguous runs and a fixed tree), no atomics: two calls on one input are bit-identical.
+ *   backward  every matrix-core operand bf16 (RNE), accumulation fp32, gradients fp32: dW_l = in_l^T dz_l with in_l the saved bf16 activation (s16 without its padding
+ *             columns, h1, h2) and dz_l rounded to bf16; db_l = the column sums of the same bf16 dz_l in fp32 (four contiguous row quarters, each ascending, added in order); dz_(l-1) = (dz_l W_l^T) . [h_(l-1) != 0]
+ *             with W_l the RNE bf16 of the masters.  The contraction over the rows is not split: no partials, no floating-point atomics.
+ *   A non-finite action, advantage, old logp, target or master gives non-finite gradients; nothing clamps.  (Observations pass the normaliser's clip as for the
+ *   sampling net: a NaN observation becomes -s_clip there.)
+ *   step      (tf.train.MomentumOptimizer behind MPISolver) per element: g = grad_scale grad, on matrix entries g += weight_decay w (_weight_decay_loss skips
+ *             biases), v = momentum v + g -- these in fp64, where every product of two floats is exact, v rounded to fp32 ONCE (a chain of fp32 roundings is off by
+ *             many ulps of a v that momentum v and g nearly cancel to); then w = fmaf(-stepsize, v, w) with the stored v.  Device and emulator round alike.
+ *             With a net the new masters are then packed into it: dm_policy_set_weights with
+ *             DM_DEVICE_PTRS on views of params_dev, byte for byte what dm_policy_create makes of the same arrays.  Without one (NULL) only the step runs, on the
+ *             current device, and weight_decay must be 0 (which entries are matrices is the net's layout).
+ *
+ * Workspace (dm_train_workspace_bytes(net, n) bytes, 16-byte aligned), left behind by a *_grad call:
+ *   [z3 fp32 n x N3][dz3 bf16 n x N3][dz2 bf16 n x H2][dz1 bf16 n x H1][ceil(n / 16) blocks of 8 doubles], N3 = action_dim rounded up to 32, padded columns zero.
+ * dm_train_actor_grad: cfg->a_bound_min / a_bound_max are HOST arrays of action_dim un-normalised entries (+-inf allowed; both NULL: no bound loss), bound_weight is 10
+ *   in the reference.  grads_dev [P] is overwritten; stats_dev double[6] = {n, -mean min(l0, l1), bound loss 0.5 mean sum_j violation^2, clip_frac = mean[|ratio - 1| > eps],
+ *   mean ratio, mean logp_new}; logp_out [n] optional.
+ * dm_train_value_grad: stats_dev double[2] = {0.5 mean (tar - v)^2, mean v}; values_out [n] optional, the raw net output.
+ * Refused: a NULL net or required pointer; a gated context; n < 1; a workspace that is too small or not 16-byte aligned, stats not 8-byte aligned; a goal_dim
+ * dm_policy_forward_ex would refuse; ratio_clip <= 0; bound_weight < 0; one of the two bound arrays without the other; the actor call on a context without logstd /
+ * a_mean / a_std or with action_dim > 128; the value call on action_dim != 1; stepsize, momentum or weight_decay negative or non-finite, a non-finite grad_scale;
+ * P < 1 or, with a net, P != dm_train_param_count(net); weight_decay != 0 without a net.
+ * dm_train_read_activations: TEST SUPPORT, synchronous: the first n rows of s16 [n x K1] (which = 0), h1 (1) or h2 (2) as the last call left them, bf16, to the host. */
+typedef struct dm_train_actor_cfg { double ratio_clip, bound_weight; const float* a_bound_min; const float* a_bound_max; } dm_train_actor_cfg;
+int64_t dm_train_param_count(const dm_policy* net);                 /* < 0: refused (dm_last_error) */
+int64_t dm_train_workspace_bytes(const dm_policy* net, int n);      /* < 0: refused (dm_last_error) */
+int dm_train_actor_grad(dm_policy* net, const float* params_dev, const float* states_dev, const float* goals_dev, int goal_dim, int n, const float* actions_dev,
+                        const float* old_logp_dev, const float* adv_dev, const dm_train_actor_cfg* cfg, float* grads_dev, double* stats_dev, float* logp_out,
+                        void* workspace, int64_t workspace_bytes, void* hip_stream);
+int dm_train_value_grad(dm_policy* net, const float* params_dev, const float* states_dev, const float* goals_dev, int goal_dim, int n, const float* targets_dev,
+                        float* grads_dev, double* stats_dev, float* values_out, void* workspace, int64_t workspace_bytes, void* hip_stream);
+int dm_train_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum,
+                      double weight_decay, double grad_scale, void* hip_stream);
+int dm_train_read_activations(dm_policy* net, int which, int n, void* host_out, size_t capacity);
+
 /* ---- a probe for the device math helpers(deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
  * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
  * pointers.  The kernel narrows the inputs the op reads to float (f64 == 0) or keeps them double (f64 != 0), calls the helper in that type, and widens the result
