@@ -1,7 +1,7 @@
 // PPO actor and critic minibatch updates on the device (include/dm_hip.h dm_train_*, deepmimic_amd/train.py): what PPOAgent._update_actor / _update_critic and
 // MPISolver.update do (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples.
 // Included at the end of dm_host.cpp (shares its runtime shim, dm_policy's kernels and the workgroup tree of dm_ppo_batch.h); in no step-kernel translation unit.
-// Out of scope: the gated nets, the AMP discriminator update (its gradient penalty needs a second derivative), Adam, one fused training kernel, step-size schedules.
+// Out of scope: the gated nets, Adam, one fused training kernel, step-size schedules.  The AMP discriminator update (dm_train_disc_grad) is the second half of this file.
 //
 // One *_grad call is, in stream order:
 //     k_policy_prep, layers 1 and 2     the context's own per-layer kernels (forced: DM_POLICY_* is not read), leaving s16 / h1 / h2 in bf16 as the sampling net had them
@@ -204,6 +204,8 @@ __global__ void __launch_bounds__(256) k_train_fold(const double* part, int grou
 
 struct WgradArgs { const uint16_t* in; int ldin, K; const uint16_t* dz; int lddz, N; int M; float* dW; };
 
+// ACC: the tile is ADDED to what dW holds (one fp32 add per element by its one owner): the penalty's contribution on top of the least-squares gradient (dm_train_disc_grad)
+template <bool ACC>
 __global__ void __launch_bounds__(64) k_train_wgrad(WgradArgs a) {
     constexpr int PITCH = 40;                    // halves per staged row: 80 bytes, so a 16-byte record stays aligned
     __shared__ alignas(16) uint16_t sa[32 * PITCH];
@@ -252,12 +254,17 @@ __global__ void __launch_bounds__(64) k_train_wgrad(WgradArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const int row = k0 + 16 * i + 4 * g + r, col = n0 + 16 * j + c;
-                if (row < a.K && col < a.N) a.dW[(size_t)row * a.N + col] = acc[i][j][r];
+                if (row < a.K && col < a.N) {
+                    float* const at = a.dW + (size_t)row * a.N + col;
+                    if constexpr (ACC) *at = *at + acc[i][j][r]; else *at = acc[i][j][r];
+                }
             }
 }
 
 // four wavefronts per 64 columns: wave s adds the s-th contiguous quarter of the rows, ascending (16 independent loads in flight, added in row order), then the quarters in order
-__global__ void __launch_bounds__(256) k_train_bgrad(const uint16_t* dz, int lddz, int N, int M, float* db) {
+// ACC: db = (db + the column sums), then with w the regulariser db = fmaf(reg, w, db) -- dw3 of dm_train_disc_grad (M = 0: the regulariser alone)
+template <bool ACC>
+__global__ void __launch_bounds__(256) k_train_bgrad(const uint16_t* dz, int lddz, int N, int M, float* db, const float* w, float reg) {
     __shared__ float part[4][64];
     const int t = (int)threadIdx.x, cl = t & 63, sl = t >> 6, col = (int)blockIdx.x * 64 + cl;
     const int q = (M + 3) / 4, m0 = sl * q, m1 = (m0 + q < M) ? m0 + q : M;
@@ -275,12 +282,22 @@ __global__ void __launch_bounds__(256) k_train_bgrad(const uint16_t* dz, int ldd
     }
     part[sl][cl] = s;
     __syncthreads();
-    if (sl == 0 && col < N) db[col] = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+    if (sl == 0 && col < N) {
+        float v = ((part[0][cl] + part[1][cl]) + part[2][cl]) + part[3][cl];
+        if constexpr (ACC) { v = db[col] + v; if (w) v = fmaf(reg, w[col], v); }
+        db[col] = v;
+    }
 }
 
 struct DgradArgs { const uint16_t* dz; int lddz; const float* W; int ldw; const uint16_t* h; int H; int M; uint16_t* out; };
+// the layer-1 form (INPUT = true; dm_train_disc_grad): gx = g1 W1^T with W [S x ldw] the layer-1 master, rows S .. H - 1 (H = K1) read as zero; no mask; per row the fp32
+// sum of squares of the tile's 32 columns -> sq [M x H / 32]; out = bf16(gx scale), the padding columns zero
+struct DgradInArgs : DgradArgs { int S; float scale; float* sq; };
+template <bool INPUT> struct DgradSel { typedef DgradArgs type; };
+template <> struct DgradSel<true> { typedef DgradInArgs type; };
 
-__global__ void __launch_bounds__(64) k_train_dgrad(DgradArgs a) {
+template <bool INPUT>
+__global__ void __launch_bounds__(64) k_train_dgrad(typename DgradSel<INPUT>::type a) {
     const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
     const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, k0 = ((int)blockIdx.x / rbn) * 32;      // consecutive workgroups walk down the rows under one block of W
     f32x4 acc[2][2];
@@ -290,12 +307,13 @@ __global__ void __launch_bounds__(64) k_train_dgrad(DgradArgs a) {
         for (int j = 0; j < 2; ++j)
 #pragma unroll
             for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
-    const uint16_t* arow[2]; const float* wrow[2];
+    const uint16_t* arow[2]; const float* wrow[2]; bool wlive[2] = {true, true};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
         const int row = m0 + 16 * i + c;
         arow[i] = a.dz + (size_t)(row < a.M ? row : 0) * a.lddz + 8 * g;
-        wrow[i] = a.W + (size_t)(k0 + 16 * i + c) * a.ldw + 8 * g;
+        if constexpr (INPUT) { wlive[i] = k0 + 16 * i + c < a.S; wrow[i] = a.W + (size_t)(wlive[i] ? k0 + 16 * i + c : 0) * a.ldw + 8 * g; }
+        else wrow[i] = a.W + (size_t)(k0 + 16 * i + c) * a.ldw + 8 * g;
     }
     for (int nk = 0; nk < a.lddz; nk += 32) {
         bf16x8 fa[2], fb[2];
@@ -303,12 +321,33 @@ __global__ void __launch_bounds__(64) k_train_dgrad(DgradArgs a) {
         for (int i = 0; i < 2; ++i) {
             fa[i] = *reinterpret_cast<const bf16x8*>(arow[i] + nk);
 #pragma unroll
-            for (int e = 0; e < 8; ++e) dmp::set8(fb[i], e, nk + 8 * g + e < a.ldw ? bf16_rne(wrow[i][nk + e]) : (uint16_t)0);
+            for (int e = 0; e < 8; ++e) dmp::set8(fb[i], e, nk + 8 * g + e < a.ldw && (!INPUT || wlive[i]) ? bf16_rne(wrow[i][nk + e]) : (uint16_t)0);
         }
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
             for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
+    }
+    if constexpr (INPUT) {
+        // per row: the lane's two columns (v0 v0, then fmaf(v1, v1, .)), then the pairwise tree over the 16 lanes of the group
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m0 + 16 * i + 4 * g + r;
+                const float v0 = acc[i][0][r], v1 = acc[i][1][r];
+                float q = v0 * v0; q = fmaf(v1, v1, q);
+                q += dmp::lane_xor_f(q, 1); q += dmp::lane_xor_f(q, 2); q += dmp::lane_xor_f(q, 4); q += dmp::lane_xor_f(q, 8);
+                if (row < a.M) {
+                    if (c == 0) a.sq[(size_t)row * (a.H / 32) + k0 / 32] = q;
+#pragma unroll
+                    for (int j = 0; j < 2; ++j) {
+                        const int col = k0 + 16 * j + c;
+                        a.out[(size_t)row * a.H + col] = col < a.S ? bf16_rne(acc[i][j][r] * a.scale) : (uint16_t)0;
+                    }
+                }
+            }
+        return;
     }
 #pragma unroll
     for (int i = 0; i < 2; ++i)
@@ -360,6 +399,191 @@ inline Work carve(const dmp::PolicyDev& d, int n, void* ws) {
     return w;
 }
 
+// ---------------------------------------------------------------- the AMP discriminator update (dm_train_disc_grad): AMPAgent._step_disc, learning/amp_agent.py:134-207, 251-257
+// loss = 0.5 (mean_e 0.5 (y - 1)^2 + mean_a 0.5 (y + 1)^2) + c_gp 0.5 mean_e |dy/dx|^2 + c_lr 0.5 |w3|^2 on the plain ReLU net with one output; expert rows first.
+// relu'' = 0 almost everywhere, so the penalty's gradient is first-order algebra on the saved activations (m_k = [h_k != 0]):
+//     g2 = bf16(w3)^T . m2        g1 = (g2 W2^T) . m1        gx = g1 W1^T        a = gx (c_gp / n_e)
+//     dW1 += a^T g1       t1 = (a W1) . m1       dW2 += t1^T g2       dw3 += colsum((t1 W2) . m2)       dw3 = fmaf(c_lr, w3, dw3)
+// One call is, in stream order: k_policy_prep x 2 (expert rows, then agent rows behind them), layers 1 and 2, k_train_disc_head (which also writes g2), the least-squares
+// backward pass above over all rows, then on the expert rows k_train_dgrad<false> (g1), k_train_dgrad<true> (a, |gx|^2), k_train_fwdm x 2 (t1, t2),
+// k_train_wgrad<true> x 2, k_train_bgrad<true>, and k_train_disc_wnorm, k_train_disc_fold for the statistics.  Each gradient element has one owner: the least-squares
+// value is written first, the penalty's own contraction (from a zero accumulator, k-steps ascending) is added to it by one fp32 add, the regulariser last by one fmaf.
+//
+// k_train_fwdm    out [M x N] = (in W) . [h != 0], bf16: the contraction over the ROW index of W.  Its B operand is the context's PACKED bf16 weights (w1p / w2p) and not the
+//                 masters: the packed arrays ARE W in the B-fragment order of this contraction (16 bytes per lane per k-step, what the layer kernels read), by the
+//                 precondition of the *_grad calls they are the RNE bf16 of the masters, and a read of the masters would be eight floats from eight different rows per
+//                 fragment plus a conversion.  A wavefront owns 32 rows x 32 columns, k-steps ascending from a zero accumulator.
+enum { DISC_STATS = 8, DISC_WN_BLOCKS = 64 };
+
+struct DiscHeadArgs { int M, ne; float nef, naf; int penalty; const float* w3; float* z3; uint16_t* dz3; uint16_t* g2; double* part; float* out; };
+
+DMP_DEV uint16_t get8(const bf16x8& f, int i) {
+#ifdef DM_EMU
+    return f.v[i];
+#else
+    return (uint16_t)f[i];
+#endif
+}
+
+// one wavefront per 16 rows: layer 3 on column tile 0 (the chain of the scalar head k_policy_layer<2, 1, 1, false, 1>), y = acc + b3, t = +1 (expert) / -1 (agent),
+// dz3 = (0.5 (y - t)) / n_side in column 0; the partial block {sum_e e^2, sum_a e^2, #e[y > 0], #a[y < 0], sum_a sigmoid(y), sum_a |y|}; g2 of its expert rows
+__global__ void __launch_bounds__(64) k_train_disc_head(dmp::PolicyDev p, const uint16_t* h2, DiscHeadArgs a) {
+    __shared__ double rowv[16][6];
+    const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
+    const int row0 = (int)blockIdx.x * 16, KS = p.H2 / 32, N3 = p.N3;
+    const uint16_t* const ap = h2 + (size_t)(row0 + c < a.M ? row0 + c : 0) * p.H2 + 8 * g;
+    f32x4 acc;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[r] = 0.0f;
+    for (int ks = 0; ks < KS; ++ks)
+        acc = mfma16(*reinterpret_cast<const bf16x8*>(ap + (size_t)ks * 32), *reinterpret_cast<const bf16x8*>(p.w3p + ((size_t)ks * 64 + l) * 8), acc);
+    const float b3 = p.b3[0];
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = row0 + 4 * g + r;
+        double st[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+        if (row < a.M) {
+            for (int col = c; col < N3; col += 16) if (col != 0) { a.z3[(size_t)row * N3 + col] = 0.0f; a.dz3[(size_t)row * N3 + col] = 0; }
+            if (c == 0) {
+                const bool expert = row < a.ne;
+                const float y = acc[r] + b3, e = y - (expert ? 1.0f : -1.0f);
+                a.z3[(size_t)row * N3] = y;
+                a.dz3[(size_t)row * N3] = bf16_rne((0.5f * e) / (expert ? a.nef : a.naf));
+                if (a.out) a.out[row] = y;
+                st[expert ? 0 : 1] = (double)e * (double)e;
+                if (expert) st[2] = y > 0.0f ? 1.0 : 0.0;
+                else { st[3] = y < 0.0f ? 1.0 : 0.0; st[4] = (double)(1.0f / (1.0f + exp_det(-y))); st[5] = (double)fabsf(y); }
+            }
+        }
+        if (c == 0) for (int k = 0; k < 6; ++k) rowv[4 * g + r][k] = st[k];
+    }
+    __syncthreads();
+    if (l < 6) { double s = 0.0; for (int m = 0; m < 16; ++m) s += rowv[m][l]; a.part[(size_t)blockIdx.x * PART_WORDS + l] = s; }
+    if (!a.penalty) return;
+    for (int m = 0; m < 16; ++m) {
+        const int row = row0 + m;
+        if (row >= a.ne) break;
+        for (int k = 8 * l; k < p.H2; k += 512) {
+            const bf16x8 hv = *reinterpret_cast<const bf16x8*>(h2 + (size_t)row * p.H2 + k);
+            bf16x8 o;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) dmp::set8(o, e, (get8(hv, e) & 0x7fffu) ? bf16_rne(a.w3[k + e]) : (uint16_t)0);
+            *reinterpret_cast<bf16x8*>(a.g2 + (size_t)row * p.H2 + k) = o;
+        }
+    }
+}
+
+struct FwdmArgs { const uint16_t* in; const uint16_t* wp; int KS; const uint16_t* h; int N; int M; uint16_t* out; };      // in [M x 32 KS], wp: fragments of W [32 KS x N], h / out [M x N]
+
+__global__ void __launch_bounds__(64) k_train_fwdm(FwdmArgs a) {
+    const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
+    const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, n0 = ((int)blockIdx.x / rbn) * 32;      // consecutive workgroups walk down the rows under one block of W
+    f32x4 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
+    const uint16_t* arow[2]; const uint16_t* bcol[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = m0 + 16 * i + c;
+        arow[i] = a.in + (size_t)(row < a.M ? row : 0) * (32 * a.KS) + 8 * g;
+        bcol[i] = a.wp + ((size_t)(n0 / 16 + i) * a.KS * 64 + l) * 8;
+    }
+    for (int ks = 0; ks < a.KS; ++ks) {
+        bf16x8 fa[2], fb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            fa[i] = *reinterpret_cast<const bf16x8*>(arow[i] + (size_t)ks * 32);
+            fb[i] = *reinterpret_cast<const bf16x8*>(bcol[i] + (size_t)ks * 512);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m0 + 16 * i + 4 * g + r, col = n0 + 16 * j + c;
+                if (row < a.M) {
+                    const size_t at = (size_t)row * a.N + col;
+                    a.out[at] = (a.h[at] & 0x7fffu) ? bf16_rne(acc[i][j][r]) : (uint16_t)0;
+                }
+            }
+}
+
+// the sums of squares of the masters in fp64: workgroup b takes the b-th contiguous chunk of the parameter block, thread t its elements t, t + 256, .. ascending, then the
+// tree of dm_ppo_batch.h -> wn[2 b] (the three matrices), wn[2 b + 1] (w3 alone)
+__global__ void __launch_bounds__(256) k_train_disc_wnorm(const float* params, Layout L, int blocks, double* wn) {
+    __shared__ double red[dmb::kThreads];
+    const long long chunk = (L.P + blocks - 1) / blocks, lo = (long long)blockIdx.x * chunk, hi = lo + chunk < L.P ? lo + chunk : L.P;
+    double sm = 0.0, s3 = 0.0;
+    for (long long i = lo + (long long)threadIdx.x; i < hi; i += 256) {
+        const double x = (double)params[i], xx = x * x;
+        if ((i >= L.o[0] && i < L.o[1]) || (i >= L.o[2] && i < L.o[3]) || (i >= L.o[4] && i < L.o[5])) sm += xx;
+        if (i >= L.o[4] && i < L.o[5]) s3 += xx;
+    }
+    sm = dmb::block_sum(sm, red); s3 = dmb::block_sum(s3, red);
+    if (threadIdx.x == 0) { wn[2 * (size_t)blockIdx.x] = sm; wn[2 * (size_t)blockIdx.x + 1] = s3; }
+}
+
+struct DiscFoldArgs { const double* part; int groups; const float* sq; long long nsq; const double* wn; int wblocks; int ne, na; double* stats; };
+
+// one workgroup: every array by contiguous runs per thread, then the tree -> stats {least-squares loss, acc_expert, acc_agent, mean_a sigmoid(y), mean_a |y|,
+// gradient penalty 0.5 mean_e |gx|^2, 0.5 |w3|^2, 0.5 sum_k |W_k|^2}
+__global__ void __launch_bounds__(256) k_train_disc_fold(DiscFoldArgs a) {
+    __shared__ double red[dmb::kThreads];
+    const int t = (int)threadIdx.x;
+    double tot[9];
+    {
+        const int per = (a.groups + dmb::kThreads - 1) / dmb::kThreads, g0 = t * per, g1 = (g0 + per < a.groups) ? g0 + per : a.groups;
+        for (int k = 0; k < 6; ++k) {
+            double s = 0.0;
+            for (int g = g0; g < g1; ++g) s += a.part[(size_t)g * PART_WORDS + k];
+            tot[k] = dmb::block_sum(s, red);
+        }
+    }
+    {
+        const long long per = (a.nsq + dmb::kThreads - 1) / dmb::kThreads, i0 = t * per, i1 = (i0 + per < a.nsq) ? i0 + per : a.nsq;
+        double s = 0.0;
+        for (long long i = i0; i < i1; ++i) s += (double)a.sq[i];
+        tot[6] = dmb::block_sum(s, red);
+    }
+    for (int k = 0; k < 2; ++k) {
+        double s = 0.0;
+        if (t < a.wblocks) s = a.wn[2 * t + k];
+        tot[7 + k] = dmb::block_sum(s, red);
+    }
+    if (t != 0) return;
+    const double de = (double)a.ne, da = (double)a.na;
+    a.stats[0] = 0.5 * (0.5 * tot[0] / de + 0.5 * tot[1] / da);
+    a.stats[1] = tot[2] / de; a.stats[2] = tot[3] / da; a.stats[3] = tot[4] / da; a.stats[4] = tot[5] / da;
+    a.stats[5] = 0.5 * tot[6] / de; a.stats[6] = 0.5 * tot[8]; a.stats[7] = 0.5 * tot[7];
+}
+
+// the discriminator call's workspace: the pieces of `carve` for n = n_e + n_a rows, then [g2 bf16 n_e x H2][g1 bf16 n_e x H1][a bf16 n_e x K1][t1 bf16 n_e x H1]
+// [t2 bf16 n_e x H2][sq fp32 n_e x K1 / 32, padded to 16 bytes][wn 64 x 2 doubles]
+struct DiscWork { Work w; uint16_t *g2, *g1, *a, *t1, *t2; float* sq; double* wn; size_t bytes; };
+inline DiscWork carve_disc(const dmp::PolicyDev& d, int ne, int na, void* ws) {
+    DiscWork k; k.w = carve(d, ne + na, ws);
+    char* at = (char*)ws + k.w.bytes;
+    k.g2 = (uint16_t*)at; at += (size_t)ne * d.H2 * 2;
+    k.g1 = (uint16_t*)at; at += (size_t)ne * d.H1 * 2;
+    k.a = (uint16_t*)at; at += (size_t)ne * d.K1 * 2;
+    k.t1 = (uint16_t*)at; at += (size_t)ne * d.H1 * 2;
+    k.t2 = (uint16_t*)at; at += (size_t)ne * d.H2 * 2;
+    k.sq = (float*)at; at += ((size_t)ne * (d.K1 / 32) * 4 + 15) / 16 * 16;
+    k.wn = (double*)at; at += (size_t)DISC_WN_BLOCKS * 2 * sizeof(double);
+    k.bytes = (size_t)(at - (char*)ws);
+    return k;
+}
+
 }  // namespace dmt
 
 static int train_net_ok(const char* fn, const dm_policy* p) {
@@ -398,11 +622,11 @@ static int train_grad(dm_policy* p, const char* fn, const float* params, const f
     uint16_t* dz[3] = {w.dz1, w.dz2, w.dz3}; const int lddz[3] = {d.H1, d.H2, d.N3}, N[3] = {d.H1, d.H2, d.A};
     for (int layer = 2; layer >= 0; --layer) {
         dmt::WgradArgs wa; wa.in = in[layer]; wa.ldin = ldin[layer]; wa.K = K[layer]; wa.dz = dz[layer]; wa.lddz = lddz[layer]; wa.N = N[layer]; wa.M = n; wa.dW = grads + L.o[2 * layer];
-        RT_LAUNCH(dmt::k_train_wgrad, ((K[layer] + 31) / 32) * ((N[layer] + 31) / 32), stream, wa);
-        RT_LAUNCH4(dmt::k_train_bgrad, (N[layer] + 63) / 64, stream, (const uint16_t*)dz[layer], lddz[layer], N[layer], n, grads + L.o[2 * layer + 1]);
+        RT_LAUNCH(dmt::k_train_wgrad<false>, ((K[layer] + 31) / 32) * ((N[layer] + 31) / 32), stream, wa);
+        RT_LAUNCH4(dmt::k_train_bgrad<false>, (N[layer] + 63) / 64, stream, (const uint16_t*)dz[layer], lddz[layer], N[layer], n, grads + L.o[2 * layer + 1], (const float*)nullptr, 0.0f);
         if (layer > 0) {
             dmt::DgradArgs da; da.dz = dz[layer]; da.lddz = lddz[layer]; da.W = params + L.o[2 * layer]; da.ldw = N[layer]; da.h = in[layer]; da.H = K[layer]; da.M = n; da.out = dz[layer - 1];
-            RT_LAUNCH(dmt::k_train_dgrad, ((n + 31) / 32) * (K[layer] / 32), stream, da);
+            RT_LAUNCH(dmt::k_train_dgrad<false>, ((n + 31) / 32) * (K[layer] / 32), stream, da);
         }
     }
     return launch_status(0);
@@ -452,6 +676,95 @@ int dm_train_value_grad(dm_policy* net, const float* params_dev, const float* st
     dmt::HeadArgs ha; memset(&ha, 0, sizeof(ha));
     ha.kind = dmt::HEAD_CRITIC; ha.targets = targets_dev; ha.out = values_out;
     return train_grad(net, fn, params_dev, states_dev, goals_dev, goal_dim, n, ha, grads_dev, stats_dev, workspace, workspace_bytes, hip_stream);
+}
+
+// what the two discriminator entry points refuse alike
+static int train_disc_ok(const char* fn, const dm_policy* net, int n_expert, int n_agent) {
+    if (train_net_ok(fn, net)) return -1;
+    if (net->pd.A != 1) return fail(std::string(fn) + ": the context has action_dim " + std::to_string(net->pd.A) + ", the discriminator is a net with one output");
+    if (n_expert < 1 || n_agent < 1) return fail(std::string(fn) + ": n_expert and n_agent must be >= 1");
+    const dmp::PolicyDev& d = net->pd;
+    if (((long long)n_expert + (long long)n_agent) * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
+    return 0;
+}
+
+int64_t dm_train_disc_workspace_bytes(const dm_policy* net, int n_expert, int n_agent) {
+    if (train_disc_ok("dm_train_disc_workspace_bytes", net, n_expert, n_agent)) return -1;
+    return (int64_t)dmt::carve_disc(net->pd, n_expert, n_agent, nullptr).bytes;
+}
+
+int dm_train_disc_grad(dm_policy* net, const float* params_dev, const float* expert_obs_dev, int n_expert, const float* agent_obs_dev, int n_agent,
+                       const dm_train_disc_cfg* cfg, float* grads_dev, double* stats_dev, float* logits_out, void* workspace, int64_t workspace_bytes, void* hip_stream) {
+    const char* fn = "dm_train_disc_grad";
+    if (train_disc_ok(fn, net, n_expert, n_agent)) return -1;
+    if (!params_dev || !expert_obs_dev || !agent_obs_dev || !cfg || !grads_dev || !stats_dev || !workspace) return fail(std::string(fn) + ": null argument");
+    if (!(cfg->grad_penalty >= 0.0 && std::isfinite(cfg->grad_penalty))) return fail(std::string(fn) + ": grad_penalty must be finite and >= 0");
+    if (!(cfg->logit_reg >= 0.0 && std::isfinite(cfg->logit_reg))) return fail(std::string(fn) + ": logit_reg must be finite and >= 0");
+    dm_policy* p = net;
+    const dmp::PolicyDev& d = p->pd;
+    const int ne = n_expert, na = n_agent, n = ne + na;
+    const dmt::DiscWork k = dmt::carve_disc(d, ne, na, workspace);
+    if (workspace_bytes < (int64_t)k.bytes) return fail(std::string(fn) + ": workspace too small (dm_train_disc_workspace_bytes)");
+    if ((((uintptr_t)workspace) & 15) != 0 || (((uintptr_t)stats_dev) & 7) != 0) return fail(std::string(fn) + ": the workspace must be 16-byte and stats 8-byte aligned");
+    DevGuard guard(p->device_id);
+    rt_stream stream = (rt_stream)hip_stream;
+    if (policy_grow(p, n, stream)) return -1;
+    const bool penalty = cfg->grad_penalty > 0.0;
+    const float c_lr = (float)cfg->logit_reg;
+    // ---- forward: the two batches into one s16 (expert rows first), then the context's per-layer kernels as train_grad chooses them
+    dmp::PolicyIO io; memset(&io, 0, sizeof(io));
+    io.exp_rate = 1.0f; io.h1 = p->h1; io.h2 = p->h2;
+    io.states = expert_obs_dev; io.M = ne; io.s16 = p->s16;
+    RT_LAUNCH(dmp::k_policy_prep, ne, stream, d, io);
+    io.states = agent_obs_dev; io.M = na; io.s16 = p->s16 + (size_t)ne * d.K1;
+    RT_LAUNCH(dmp::k_policy_prep, na, stream, d, io);
+    io.states = nullptr; io.M = n; io.s16 = p->s16;
+    const int path = DM_POLICY_PATH_LAYERED(d.H1 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE, d.H2 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE);
+    launch_layers<false>(path, n, stream, d, io);
+    const dmt::Layout L = dmt::layout_of(d);
+    const int groups = (n + 15) / 16;
+    dmt::DiscHeadArgs ha; memset(&ha, 0, sizeof(ha));
+    ha.M = n; ha.ne = ne; ha.nef = (float)ne; ha.naf = (float)na; ha.penalty = penalty ? 1 : 0; ha.w3 = params_dev + L.o[4];
+    ha.z3 = k.w.z3; ha.dz3 = k.w.dz3; ha.g2 = k.g2; ha.part = k.w.part; ha.out = logits_out;
+    RT_LAUNCH(dmt::k_train_disc_head, groups, stream, d, (const uint16_t*)p->h2, ha);
+    // ---- the least-squares backward pass over all rows (train_grad's), layer 3 first
+    const uint16_t* in[3] = {p->s16, p->h1, p->h2}; const int ldin[3] = {d.K1, d.H1, d.H2}, K[3] = {d.S, d.H1, d.H2};
+    uint16_t* dz[3] = {k.w.dz1, k.w.dz2, k.w.dz3}; const int lddz[3] = {d.H1, d.H2, d.N3}, N[3] = {d.H1, d.H2, d.A};
+    for (int layer = 2; layer >= 0; --layer) {
+        dmt::WgradArgs wa; wa.in = in[layer]; wa.ldin = ldin[layer]; wa.K = K[layer]; wa.dz = dz[layer]; wa.lddz = lddz[layer]; wa.N = N[layer]; wa.M = n; wa.dW = grads_dev + L.o[2 * layer];
+        RT_LAUNCH(dmt::k_train_wgrad<false>, ((K[layer] + 31) / 32) * ((N[layer] + 31) / 32), stream, wa);
+        RT_LAUNCH4(dmt::k_train_bgrad<false>, (N[layer] + 63) / 64, stream, (const uint16_t*)dz[layer], lddz[layer], N[layer], n, grads_dev + L.o[2 * layer + 1], (const float*)nullptr, 0.0f);
+        if (layer > 0) {
+            dmt::DgradArgs da; da.dz = dz[layer]; da.lddz = lddz[layer]; da.W = params_dev + L.o[2 * layer]; da.ldw = N[layer]; da.h = in[layer]; da.H = K[layer]; da.M = n; da.out = dz[layer - 1];
+            RT_LAUNCH(dmt::k_train_dgrad<false>, ((n + 31) / 32) * (K[layer] / 32), stream, da);
+        }
+    }
+    // ---- the penalty, expert rows only
+    const int rb = (ne + 31) / 32;
+    if (penalty) {
+        dmt::DgradArgs d2; d2.dz = k.g2; d2.lddz = d.H2; d2.W = params_dev + L.o[2]; d2.ldw = d.H2; d2.h = p->h1; d2.H = d.H1; d2.M = ne; d2.out = k.g1;
+        RT_LAUNCH(dmt::k_train_dgrad<false>, rb * (d.H1 / 32), stream, d2);
+        dmt::DgradInArgs d1; d1.dz = k.g1; d1.lddz = d.H1; d1.W = params_dev + L.o[0]; d1.ldw = d.H1; d1.h = nullptr; d1.H = d.K1; d1.M = ne; d1.out = k.a;
+        d1.S = d.S; d1.scale = (float)cfg->grad_penalty / (float)ne; d1.sq = k.sq;
+        RT_LAUNCH(dmt::k_train_dgrad<true>, rb * (d.K1 / 32), stream, d1);
+        dmt::FwdmArgs f1; f1.in = k.a; f1.wp = d.w1p; f1.KS = d.K1 / 32; f1.h = p->h1; f1.N = d.H1; f1.M = ne; f1.out = k.t1;
+        RT_LAUNCH(dmt::k_train_fwdm, rb * (d.H1 / 32), stream, f1);
+        dmt::FwdmArgs f2; f2.in = k.t1; f2.wp = d.w2p; f2.KS = d.H1 / 32; f2.h = p->h2; f2.N = d.H2; f2.M = ne; f2.out = k.t2;
+        RT_LAUNCH(dmt::k_train_fwdm, rb * (d.H2 / 32), stream, f2);
+        dmt::WgradArgs w1; w1.in = k.a; w1.ldin = d.K1; w1.K = d.S; w1.dz = k.g1; w1.lddz = d.H1; w1.N = d.H1; w1.M = ne; w1.dW = grads_dev + L.o[0];
+        RT_LAUNCH(dmt::k_train_wgrad<true>, ((d.S + 31) / 32) * (d.H1 / 32), stream, w1);
+        dmt::WgradArgs w2; w2.in = k.t1; w2.ldin = d.H1; w2.K = d.H1; w2.dz = k.g2; w2.lddz = d.H2; w2.N = d.H2; w2.M = ne; w2.dW = grads_dev + L.o[2];
+        RT_LAUNCH(dmt::k_train_wgrad<true>, (d.H1 / 32) * (d.H2 / 32), stream, w2);
+    }
+    if (penalty || c_lr > 0.0f)
+        RT_LAUNCH4(dmt::k_train_bgrad<true>, (d.H2 + 63) / 64, stream, (const uint16_t*)k.t2, d.H2, d.H2, penalty ? ne : 0, grads_dev + L.o[4], c_lr > 0.0f ? params_dev + L.o[4] : (const float*)nullptr, c_lr);
+    // ---- the statistics
+    const int wblocks = (int)std::min<long long>((L.P + 16383) / 16384, dmt::DISC_WN_BLOCKS);
+    RT_LAUNCH4(dmt::k_train_disc_wnorm, wblocks, stream, params_dev, L, wblocks, k.wn);
+    dmt::DiscFoldArgs fa; fa.part = k.w.part; fa.groups = groups; fa.sq = k.sq; fa.nsq = penalty ? (long long)ne * (d.K1 / 32) : 0; fa.wn = k.wn; fa.wblocks = wblocks;
+    fa.ne = ne; fa.na = na; fa.stats = stats_dev;
+    RT_LAUNCH4(dmt::k_train_disc_fold, 1, stream, fa);
+    return launch_status(0);
 }
 
 int dm_train_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum, double weight_decay,

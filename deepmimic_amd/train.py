@@ -7,9 +7,16 @@ three-layer nets, on the `Policy` context that samples -- the forward pass runs 
     all_reduce_gradients(tr)                                                         # (deepmimic_amd/dist.py, several ranks)
     tr.step(grad_scale=1.0 / world)                                                  # momentum SGD on the fp32 masters, then the refresh of the context
 
-A checkpoint is `torch.save(tr.buf)`.  Gated contexts, the AMP discriminator update, Adam, a fused training kernel and step-size schedules are out of scope.
+A checkpoint is `torch.save(tr.buf)`.  Gated contexts, Adam, a fused training kernel and step-size schedules are out of scope.
 
-`reference_grad` / `reference_step` are the numpy statements of the arithmetic (the specification of include/dm_hip.h): the same rounding points -- bf16 operands, the head's
+The AMP discriminator update (AMPAgent._step_disc, learning/amp_agent.py:134-207, 251-257, 356-377; `dm_train_disc_grad`) is `DiscTrainer`, on the context inside a
+`heads.Discriminator`, so that the net that scores the style reward is the net that was trained:
+
+    dt = DiscTrainer.from_policy(disc.net, weights, stepsize=..., momentum=0.9, weight_decay=DiscWeightDecay)
+    dt.grad(expert_obs, agent_obs, grad_penalty=10.0, logit_reg=0.05)                # the two batches as dm_amp_expert_draw / dm_replay_sample fill them
+    all_reduce_gradients(dt); dt.step(grad_scale=1.0 / world)                        # disc.eval_* now scores with the new weights
+
+`reference_grad` / `reference_step` / `reference_disc_grad` are the numpy statements of the arithmetic (the specification of include/dm_hip.h): the same rounding points -- bf16 operands, the head's
 fp32 operations one by one, the library's own exp -- with the contractions accumulated in float64."""
 from __future__ import annotations
 
@@ -223,6 +230,94 @@ class CriticTrainer(_Trainer):
                           0 if goals is None else goals.data_ptr(), G, 0 if values_out is None else values_out.data_ptr(), self._stream())
 
 
+# ---- the AMP discriminator update
+
+class _DiscCfg(C.Structure):
+    _fields_ = [("grad_penalty", C.c_double), ("logit_reg", C.c_double)]
+
+
+DISC_STATS = ("loss_ls", "acc_expert", "acc_agent", "prob_agent", "abs_logit_agent", "grad_penalty", "logit_reg", "weight_decay")
+
+
+def disc_workspace_layout(S: int, H1: int, H2: int, n_expert: int, n_agent: int) -> dict:
+    """{name: (byte offset, dtype, shape)} of what dm_train_disc_grad leaves in its workspace (include/dm_hip.h): the pieces of `workspace_layout` for all rows, then the
+    penalty's stages on the expert rows; "bytes": the total"""
+    n, ne, K1 = n_expert + n_agent, n_expert, (S + 63) // 64 * 64
+    out = workspace_layout(H1, H2, 1, n)
+    at = out.pop("bytes")
+    for name, dt, shape in (("g2", np.uint16, (ne, H2)), ("g1", np.uint16, (ne, H1)), ("a", np.uint16, (ne, K1)), ("t1", np.uint16, (ne, H1)), ("t2", np.uint16, (ne, H2)),
+                            ("sq", np.float32, (ne, K1 // 32)), ("wn", np.float64, (64, 2))):
+        out[name] = (at, dt, shape); at += (int(np.prod(shape)) * np.dtype(dt).itemsize + 15) // 16 * 16
+    out["bytes"] = at
+    return out
+
+
+def disc_workspace_bytes(policy, n_expert: int, n_agent: int) -> int:
+    _need_disc(policy)
+    b = policy.lib.dm_train_disc_workspace_bytes(policy.h, int(n_expert), int(n_agent))
+    check(policy.lib, b < 0)
+    return int(b)
+
+
+def _need_disc(policy):
+    if not hasattr(policy.lib, "dm_train_disc_grad"):
+        raise RuntimeError("libdm_hip: this library has no dm_train_disc_grad (rebuild it)")
+
+
+def disc_grad_device(policy, params_ptr: int, expert_ptr: int, n_expert: int, agent_ptr: int, n_agent: int, grads_ptr: int, stats_ptr: int, workspace_ptr: int,
+                     workspace_nbytes: int, grad_penalty: float = 10.0, logit_reg: float = 0.05, logits_ptr: int = 0, stream: int = 0):
+    """raw device pointers (ints): the two observation batches [n_expert, S] and [n_agent, S], stats double[8] (DISC_STATS), logits [n_expert + n_agent] optional,
+    expert rows first; asynchronous on `stream`"""
+    _need_disc(policy)
+    cfg = _DiscCfg(float(grad_penalty), float(logit_reg))
+    check(policy.lib, policy.lib.dm_train_disc_grad(policy.h, vp(params_ptr), vp(expert_ptr), int(n_expert), vp(agent_ptr), int(n_agent), C.cast(C.pointer(cfg), C.c_void_p),
+                                                    vp(grads_ptr), vp(stats_ptr), vp(logits_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
+
+
+class DiscTrainer(_Trainer):
+    """The discriminator's update on the context of a `heads.Discriminator` (`from_policy(disc.net, weights, ...)`; weight_decay is DiscWeightDecay).
+    stats(): float64[8] in the order of DISC_STATS = STATS -- the least-squares loss, acc_expert, acc_agent, mean sigmoid(y) and mean |y| over the agent rows, the gradient
+    penalty 0.5 mean_e |dy/dx|^2, 0.5 |w3|^2, 0.5 sum_k |W_k|^2; `stat(name)` picks one, `loss()` is the reference's Disc_Loss."""
+    N_STATS = 8
+    STATS = DISC_STATS
+
+    def __init__(self, *a, **kw):
+        super().__init__(*a, **kw)
+        _need_disc(self.policy)
+        self._coef = (0.0, 0.0)
+        self._work_shape = (0, 0)
+
+    def _disc_workspace(self, ne: int, na: int):
+        import torch
+        if ne > self._work_shape[0] or na > self._work_shape[1]:
+            ne_c, na_c = max(ne, self._work_shape[0]), max(na, self._work_shape[1])
+            self._work_bytes = disc_workspace_bytes(self.policy, ne_c, na_c)
+            self._work = torch.zeros((self._work_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
+            self._work_shape = (ne_c, na_c)
+        return self._work.data_ptr(), self._work_bytes
+
+    def grad(self, expert_obs, agent_obs, grad_penalty: float = 10.0, logit_reg: float = 0.05, logits_out=None):
+        import torch
+        ne = int(expert_obs.shape[0]) if expert_obs.dim() == 2 else -1
+        na = int(agent_obs.shape[0]) if agent_obs.dim() == 2 else -1
+        tensor_arg("expert_obs", expert_obs, self.device, torch.float32, [(ne, self.policy.S)])
+        tensor_arg("agent_obs", agent_obs, self.device, torch.float32, [(na, self.policy.S)])
+        if logits_out is not None:
+            tensor_arg("logits_out", logits_out, self.device, torch.float32, [(ne + na,)])
+        ws, nbytes = self._disc_workspace(ne, na)
+        disc_grad_device(self.policy, self.params.data_ptr(), expert_obs.data_ptr(), ne, agent_obs.data_ptr(), na, self.grads.data_ptr(), self._stats.data_ptr(), ws, nbytes,
+                         grad_penalty, logit_reg, 0 if logits_out is None else logits_out.data_ptr(), self._stream())
+        self._coef = (float(grad_penalty), float(logit_reg))
+
+    def stat(self, name: str):
+        return self._stats[self.STATS.index(name)]
+
+    def loss(self):
+        """Disc_Loss of the last grad call (a 0-dim float64 device tensor): least squares + DiscWeightDecay 0.5 sum |W_k|^2 + logit_reg 0.5 |w3|^2 + grad_penalty penalty"""
+        s = self._stats
+        return s[0] + self.weight_decay * s[7] + self._coef[1] * s[6] + self._coef[0] * s[5]
+
+
 # ---- numpy statements of the arithmetic (host; the tests hold the kernels to them)
 
 def bf16_bits(x) -> np.ndarray:
@@ -406,3 +501,84 @@ def matrix_mask_of(S: int, H1: int, H2: int, A: int) -> np.ndarray:
     for k in ("w1", "w2", "w3"):
         m[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))] = True
     return m
+
+
+# ---- the discriminator update in numpy
+
+def reference_disc_head(z3, n_expert: int, n_agent: int):
+    """k_train_disc_head on given z3 [n, >= 1] (expert rows first), every operation in float32 as the kernel orders it: dict(dz3 [n, 32] bf16 bits, logits [n],
+    stats float64[5] = the first five of DISC_STATS).  Exact on the same z3 (the statistics up to the order of the float64 sums)."""
+    f = np.float32
+    y = np.asarray(z3, f)[:, 0]; n = y.shape[0]
+    assert n == n_expert + n_agent
+    expert = np.arange(n) < n_expert
+    with np.errstate(invalid="ignore", over="ignore"):
+        e = y - np.where(expert, f(1), f(-1))
+        bits = np.zeros((n, 32), np.uint16); bits[:, 0] = bf16_bits((f(0.5) * e) / np.where(expert, f(n_expert), f(n_agent)))
+        e2 = e.astype(np.float64) ** 2
+        ya = y[~expert]
+        sig = f(1) / (f(1) + reference_exp(-ya))
+        de, da = float(n_expert), float(n_agent)
+        stats = np.array([0.5 * (0.5 * e2[expert].sum() / de + 0.5 * e2[~expert].sum() / da), (y[expert] > 0).sum() / de, (ya < 0).sum() / da,
+                          sig.astype(np.float64).sum() / da, np.abs(ya).astype(np.float64).sum() / da])
+    return dict(dz3=bits, logits=y, stats=stats)
+
+
+def reference_row_squares(gx, K1: int):
+    """k_train_dgrad<true>'s |gx|^2 partials of fp32 gx [n, S]: per block of 32 columns (zeros behind S) lane c takes v0 v0 then fmaf(v1, v1, .) over its columns c, 16 + c,
+    then the tree over c; float32 [n, K1 / 32]"""
+    f = np.float32
+    n, S = gx.shape
+    v = np.zeros((n, K1), f); v[:, :S] = gx
+    v = v.reshape(n, K1 // 32, 2, 16)
+    with np.errstate(over="ignore", invalid="ignore"):
+        return _tree16(fma32(v[:, :, 1], v[:, :, 1], v[:, :, 0] * v[:, :, 0]))
+
+
+def reference_disc_penalty(weights: dict, h1, h2, grad_penalty: float):
+    """The penalty path on the saved bf16 activations of the EXPERT rows (values): dict(g2, g1, a [n_e, K1], t1, t2 as bf16 bits, gx float32 [n_e, S], sq float32
+    [n_e, K1 / 32], w1, w2, w3: the penalty's own gradient contributions in float32); the rounding points of include/dm_hip.h, contractions in float64"""
+    f, d = np.float32, np.float64
+    S = np.asarray(weights["w1"]).shape[0]; K1 = (S + 63) // 64 * 64
+    ne = h1.shape[0]
+    W1, W2 = bf16_round(weights["w1"]).astype(d), bf16_round(weights["w2"]).astype(d)
+    w3 = bf16_round(np.asarray(weights["w3"], f).reshape(-1))
+    with np.errstate(over="ignore", invalid="ignore"):
+        g2 = np.where(h2 != 0, w3[None, :], f(0)).astype(f)
+        g1 = bf16_round(np.where(h1 != 0, (g2.astype(d) @ W2.T).astype(f), f(0)))
+        gx = (g1.astype(d) @ W1.T).astype(f)
+        a = np.zeros((ne, K1), f); a[:, :S] = bf16_round(gx * (f(grad_penalty) / f(ne)))
+        t1 = bf16_round(np.where(h1 != 0, (a[:, :S].astype(d) @ W1).astype(f), f(0)))
+        t2 = bf16_round(np.where(h2 != 0, (t1.astype(d) @ W2).astype(f), f(0)))
+        out = dict(g2=bf16_bits(g2), g1=bf16_bits(g1), a=bf16_bits(a), t1=bf16_bits(t1), t2=bf16_bits(t2), gx=gx, sq=reference_row_squares(gx, K1),
+                   w1=(a[:, :S].astype(d).T @ g1.astype(d)).astype(f), w2=(t1.astype(d).T @ g2.astype(d)).astype(f), w3=t2.astype(d).sum(axis=0).astype(f))
+    return out
+
+
+def reference_disc_grad(weights: dict, expert_obs, agent_obs, grad_penalty: float = 10.0, logit_reg: float = 0.05, s_clip=np.inf):
+    """The whole dm_train_disc_grad call in numpy: dict(grads, stats float64[8], logits, z3, s16, h1, h2, dz3, dz2, dz1 and, with a penalty, g2, g1, gx, sq, a, t1, t2).
+    Rounding order of a gradient element: the least-squares value, + the penalty value (one float32 add), then on w3 fmaf(logit_reg, w3, .)."""
+    f, d = np.float32, np.float64
+    ne, na = np.asarray(expert_obs).shape[0], np.asarray(agent_obs).shape[0]
+    w = dict(weights); w["w3"] = np.asarray(w["w3"], f).reshape(-1, 1); w["b3"] = np.asarray(w["b3"], f).reshape(1)
+    s16, h1, h2, z3 = reference_forward_bf16(w, np.concatenate([np.asarray(expert_obs, f), np.asarray(agent_obs, f)]), s_clip)
+    hd = reference_disc_head(z3, ne, na)
+    out = dict(hd); out.update(reference_backward(w, s16, h1, h2, hd["dz3"]))
+    out.update(z3=z3, s16=s16, h1=h1, h2=h2)
+    S, H1 = w["w1"].shape; H2 = w["w2"].shape[1]
+    g = {k: v.copy() for k, v in unpack_params(out["grads"].copy(), S, H1, H2, 1).items()}
+    pen_stat = 0.0
+    with np.errstate(over="ignore", invalid="ignore"):
+        if grad_penalty > 0:
+            pen = reference_disc_penalty(w, h1[:ne], h2[:ne], grad_penalty)
+            out.update({k: pen[k] for k in ("g2", "g1", "gx", "sq", "a", "t1", "t2")})
+            g["w1"] = g["w1"] + pen["w1"]; g["w2"] = g["w2"] + pen["w2"]; g["w3"] = g["w3"] + pen["w3"].reshape(-1, 1)
+            pen_stat = 0.5 * pen["sq"].astype(d).sum() / float(ne)
+        elif logit_reg > 0:
+            g["w3"] = g["w3"] + f(0)
+        if logit_reg > 0:
+            g["w3"] = fma32(f(logit_reg), w["w3"], g["w3"])
+    out["grads"] = np.concatenate([g[k].astype(f).reshape(-1) for k in KEYS])
+    sqs = {k: (np.asarray(w[k], f).astype(d) ** 2).sum() for k in ("w1", "w2", "w3")}
+    out["stats"] = np.concatenate([hd["stats"], [pen_stat, 0.5 * sqs["w3"], 0.5 * (sqs["w1"] + sqs["w2"] + sqs["w3"])]])
+    return out

@@ -723,8 +723,7 @@ int dm_time_warp_align(int device_id, int n_envs, int capacity, int dim, int f64
  * and names its reason through dm_last_error.  The one object is the dm_policy whose net is trained: its packed bf16 weights and its activation buffers s16 / h1 / h2 are
  * read and written; the buffers grow to the largest n as in dm_policy_forward_ex (the one allocation).  ORDERING: like dm_policy_set_weights, a training call must not
  * run while another stream runs a forward, a scalar evaluation, a refresh or another training call of the same context -- order them with events or use one stream.
- * Out of scope: gated contexts, the AMP discriminator update (its gradient penalty needs a second derivative), Adam, one fused training kernel, step-size schedules
- * (the step size is an argument).
+ * Out of scope: gated contexts, Adam, one fused training kernel, step-size schedules (the step size is an argument).  The AMP discriminator update is dm_train_disc_grad below.
  *
  * Parameter block: P = dm_train_param_count(net) floats in the order w1 [S x H1], b1, w2 [H1 x H2], b2, w3 [H2 x A], b3; matrices in tf.layers.dense layout (in x out,
  * row-major), true widths, no padding.  The caller holds three such arrays: masters, momentum, gradients.
@@ -777,6 +776,41 @@ int dm_train_value_grad(dm_policy* net, const float* params_dev, const float* st
 int dm_train_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum,
                       double weight_decay, double grad_scale, void* hip_stream);
 int dm_train_read_activations(dm_policy* net, int which, int n, void* host_out, size_t capacity);
+
+/* ---- The AMP discriminator minibatch update, gradient penalty included (deepmimic_amd/csrc/dm_train.h, deepmimic_amd/train.py DiscTrainer): AMPAgent._step_disc
+ * (learning/amp_agent.py:134-207, 251-257, 356-377) on the context that scores the style reward (dm_policy_eval_scalar), under the rules of the section above: stateless,
+ * DEVICE pointers, asynchronous on hip_stream, a refused call launches and writes nothing, the PRECONDITION on the packed weights, the parameter block, dm_train_sgd_step
+ * (which carries DiscWeightDecay) and dm_train_read_activations unchanged.  The net is plain (not gated), action_dim = 1, no goal block.
+ *
+ * The two batches are separate arrays [n_expert x S] and [n_agent x S], what dm_amp_expert_draw / dm_replay_sample fill; in every per-row output (activations, workspace,
+ * logits_out) the expert rows come first.  x is the normalised, clipped bf16 observation, h1 / h2 the bf16 ReLU activations, m_k = [h_k != 0], y = h2 w3 + b3,
+ * c_gp = cfg->grad_penalty (DiscGradPenalty), c_lr = cfg->logit_reg (DiscLogitRegWeight):
+ *   loss = 0.5 (mean_e 0.5 (y - 1)^2 + mean_a 0.5 (y + 1)^2) + c_gp 0.5 mean_e |dy/dx|^2 + c_lr 0.5 |w3|^2       (the penalty on the normalised input, expert rows only)
+ * Arithmetic (deepmimic_amd/train.py reference_disc_head / reference_disc_grad state it in numpy):
+ *   forward   as in the section above; y is the chain of the scalar head (column tile 0, k-steps ascending from zero) plus b3: the bits dm_policy_eval_scalar's per-layer route gives.
+ *   head      fp32, one rounding per written operation: e = y - t with t = +1 (expert) / -1 (agent), dz3 = bf16((0.5 e) / n_side) with n_side = n_expert or n_agent as float.
+ *   least squares   the backward pass of the section above over all n_expert + n_agent rows from that dz3: every gradient element WRITTEN.
+ *   penalty   (c_gp > 0; expert rows) every operand bf16, accumulation fp32, k-steps ascending from a ZERO accumulator, results rounded to bf16 (RNE) where stored:
+ *             g2 = bf16(w3) . m2;  g1 = bf16((g2 W2^T) . m1);  gx = g1 W1^T in fp32, not stored;  per row and per block of 32 columns sq = the lane sums v0 v0 then
+ *             fmaf(v1, v1, .) over its columns c, 16 + c, then a pairwise tree over c (fp32);  a = bf16(gx (float(c_gp) / float(n_expert))), padding columns zero;
+ *             t1 = bf16((a W1) . m1);  t2 = bf16((t1 W2) . m2), both on the PACKED bf16 weights (= RNE bf16 of the masters by the precondition).
+ *   ROUNDING ORDER of a gradient element, by its one owner (no atomics, no split contraction): the least-squares value (its own contraction, rounded to fp32, stored);
+ *             then, c_gp > 0 only, the penalty value (its own contraction: dW1 a^T g1, dW2 t1^T g2, dw3 the column sums of t2 as dm_train's db) is ADDED by one fp32 add:
+ *             dW = fl(ls + pen); then, c_lr > 0 only, the regulariser by one fmaf on the fp32 master: dw3 = fmaf(float(c_lr), w3, dw3).  The biases get the
+ *             least-squares value alone.  c_gp = 0 skips the whole penalty path (its statistic is 0); c_gp = c_lr = 0 and n_expert = n_agent is, bit for bit,
+ *             dm_train_value_grad on the concatenated rows with targets +-1.
+ *   stats_dev double[8] = {least-squares loss, acc_expert = mean_e [y > 0], acc_agent = mean_a [y < 0], mean_a sigmoid(y) (fp32 1 / (1 + exp_det(-y))), mean_a |y|,
+ *             gradient penalty 0.5 mean_e sum sq, 0.5 |w3|^2, 0.5 sum_k |W_k|^2 over the three matrix masters}: fp64 sums in a fixed order (per 16 rows in row order, then
+ *             contiguous runs per thread and a fixed tree).  The reference's Disc_Loss is stats[0] + c_gp stats[5] + c_lr stats[6] + DiscWeightDecay stats[7].
+ * Workspace (dm_train_disc_workspace_bytes, 16-byte aligned), left behind: the five pieces of the section above for n = n_expert + n_agent rows, then
+ *   [g2 bf16 n_e x H2][g1 bf16 n_e x H1][a bf16 n_e x K1][t1 bf16 n_e x H1][t2 bf16 n_e x H2][sq fp32 n_e x K1 / 32, padded to 16 bytes][128 doubles: weight-norm partials].
+ *   With c_gp = 0 the pieces from g2 to sq are not written.
+ * Refused: a NULL net or required pointer (logits_out [n_expert + n_agent] is optional); a gated context; action_dim != 1; n_expert < 1 or n_agent < 1; grad_penalty or
+ * logit_reg negative or non-finite; a workspace that is too small or not 16-byte aligned, stats not 8-byte aligned; (n_expert + n_agent) max(K1, H1, H2) >= 2^31. */
+typedef struct dm_train_disc_cfg { double grad_penalty, logit_reg; } dm_train_disc_cfg;
+int64_t dm_train_disc_workspace_bytes(const dm_policy* net, int n_expert, int n_agent);      /* < 0: refused (dm_last_error) */
+int dm_train_disc_grad(dm_policy* net, const float* params_dev, const float* expert_obs_dev, int n_expert, const float* agent_obs_dev, int n_agent,
+                       const dm_train_disc_cfg* cfg, float* grads_dev, double* stats_dev, float* logits_out, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* ---- a probe for the device math helpers(deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
  * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
