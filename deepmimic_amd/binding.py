@@ -51,6 +51,12 @@ SIGNATURES = {
     "dm_train_read_activations": ([_p, _i, _i, _p, _sz], None),
     "dm_train_disc_workspace_bytes": ([_p, _i, _i], _i64),
     "dm_train_disc_grad": ([_p] * 3 + [_i, _p, _i] + [_p] * 5 + [_i64, _p], None),
+    "dm_train_gated_param_count": ([_p], _i64),
+    "dm_train_gated_workspace_bytes": ([_p, _i], _i64),
+    "dm_train_gated_actor_grad": ([_p] * 4 + [_i] * 2 + [_p] * 8 + [_i64, _p], None),
+    "dm_train_gated_value_grad": ([_p] * 4 + [_i] * 2 + [_p] * 5 + [_i64, _p], None),
+    "dm_train_gated_sgd_step": ([_p] * 4 + [_i64] + [_d] * 4 + [_p], None),
+    "dm_train_gated_read": ([_p, _i, _i, _p, _sz], None),
     "dm_math_probe": ([_i, _i, _i, _i, _p, _p, _p], None),
     "dm_wave_probe": ([_i, _i, _i, _i, _i, _p, _p, _p], None),
 }

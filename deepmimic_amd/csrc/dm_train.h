@@ -1,7 +1,8 @@
 // PPO actor and critic minibatch updates on the device (include/dm_hip.h dm_train_*, deepmimic_amd/train.py): what PPOAgent._update_actor / _update_critic and
 // MPISolver.update do (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples.
 // Included at the end of dm_host.cpp (shares its runtime shim, dm_policy's kernels and the workgroup tree of dm_ppo_batch.h); in no step-kernel translation unit.
-// Out of scope: the gated nets, Adam, one fused training kernel, step-size schedules.  The AMP discriminator update (dm_train_disc_grad) is the second half of this file.
+// Out of scope: Adam, one fused training kernel, step-size schedules.  The AMP discriminator update (dm_train_disc_grad) is the second half of this file; the gated nets
+// of the AMP task agents are trained by dm_train_gated.h (dm_train_gated_*), which is included behind this file and launches its kernels.
 //
 // One *_grad call is, in stream order:
 //     k_policy_prep, layers 1 and 2     the context's own per-layer kernels (forced: DM_POLICY_* is not read), leaving s16 / h1 / h2 in bf16 as the sampling net had them
@@ -588,7 +589,21 @@ inline DiscWork carve_disc(const dmp::PolicyDev& d, int ne, int na, void* ws) {
 
 static int train_net_ok(const char* fn, const dm_policy* p) {
     if (!p) return fail(std::string(fn) + ": null net");
-    if (p->gated) return fail(std::string(fn) + ": a gated context (dm_policy_create_gated) is not trained here: the plain three-layer nets only");
+    if (p->gated) return fail(std::string(fn) + ": a gated context (dm_policy_create_gated) is not trained here: the plain three-layer nets only (a gated net: dm_train_gated_*)");
+    return 0;
+}
+
+// what every *_grad call (plain and gated) refuses alike in its common arguments; need(n): the bytes of the call's workspace, `sizer` the entry point that states them
+template <typename Need>
+static int train_args_ok(const dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, const float* grads,
+                         const double* stats, const void* ws, int64_t ws_bytes, Need need, const char* sizer) {
+    const dmp::PolicyDev& d = p->pd;
+    if (n < 1) return fail(std::string(fn) + ": n must be >= 1");
+    if (!params || !states || !grads || !stats || !ws) return fail(std::string(fn) + ": null argument");
+    if (check_goal(p, fn, "net", goals, goal_dim)) return -1;
+    if ((long long)n * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
+    if (ws_bytes < (int64_t)need(n)) return fail(std::string(fn) + ": workspace too small (" + sizer + ")");
+    if ((((uintptr_t)ws) & 15) != 0 || (((uintptr_t)stats) & 7) != 0) return fail(std::string(fn) + ": the workspace must be 16-byte and stats 8-byte aligned");
     return 0;
 }
 
@@ -596,13 +611,8 @@ static int train_net_ok(const char* fn, const dm_policy* p) {
 static int train_grad(dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, dmt::HeadArgs& ha, float* grads,
                       double* stats, void* ws, int64_t ws_bytes, void* hip_stream) {
     const dmp::PolicyDev& d = p->pd;
-    if (n < 1) return fail(std::string(fn) + ": n must be >= 1");
-    if (!params || !states || !grads || !stats || !ws) return fail(std::string(fn) + ": null argument");
-    if (check_goal(p, fn, "net", goals, goal_dim)) return -1;
-    if ((long long)n * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
+    if (train_args_ok(p, fn, params, states, goals, goal_dim, n, grads, stats, ws, ws_bytes, [&](int rows) { return dmt::carve(d, rows, nullptr).bytes; }, "dm_train_workspace_bytes")) return -1;
     const dmt::Work w = dmt::carve(d, n, ws);
-    if (ws_bytes < (int64_t)w.bytes) return fail(std::string(fn) + ": workspace too small (dm_train_workspace_bytes)");
-    if ((((uintptr_t)ws) & 15) != 0 || (((uintptr_t)stats) & 7) != 0) return fail(std::string(fn) + ": the workspace must be 16-byte and stats 8-byte aligned");
     DevGuard guard(p->device_id);
     rt_stream stream = (rt_stream)hip_stream;
     if (policy_grow(p, n, stream)) return -1;
@@ -632,6 +642,46 @@ static int train_grad(dm_policy* p, const char* fn, const float* params, const f
     return launch_status(0);
 }
 
+// the head's own checks and its kernel arguments, for the plain and the gated call alike (the caller has checked the net)
+static int train_actor_head(const char* fn, const dm_policy* net, int n, const float* actions_dev, const float* old_logp_dev, const float* adv_dev, const dm_train_actor_cfg* cfg,
+                            float* logp_out, dmt::HeadArgs& ha) {
+    if (!actions_dev || !old_logp_dev || !adv_dev || !cfg) return fail(std::string(fn) + ": null argument");
+    if (!(cfg->ratio_clip > 0.0)) return fail(std::string(fn) + ": ratio_clip must be > 0");
+    if (!(cfg->bound_weight >= 0.0)) return fail(std::string(fn) + ": bound_weight must be >= 0");
+    if ((cfg->a_bound_min == nullptr) != (cfg->a_bound_max == nullptr)) return fail(std::string(fn) + ": a_bound_min and a_bound_max come together (both NULL: no bound loss)");
+    const dmp::PolicyDev& d = net->pd;
+    if (!d.logstd || !d.a_mean || !d.a_std) return fail(std::string(fn) + ": the context holds no logstd / a_mean / a_std");
+    if (d.A > dmt::kMaxA) return fail(std::string(fn) + ": action_dim above 128 is not compiled (the action bounds ride in the kernel arguments)");
+    memset(&ha, 0, sizeof(ha));
+    ha.kind = dmt::HEAD_ACTOR; ha.actions = actions_dev; ha.old_logp = old_logp_dev; ha.adv = adv_dev; ha.out = logp_out;
+    ha.eps = (float)cfg->ratio_clip; ha.clip_lo = 1.0f - ha.eps; ha.clip_hi = 1.0f + ha.eps;
+    ha.bounded = cfg->a_bound_min ? 1 : 0;
+    ha.c0 = (-0.5f * (float)d.A) * 1.8378770664093453f;
+    if (n >= 1) ha.bwn = (float)cfg->bound_weight / (float)n;
+    if (ha.bounded) for (int j = 0; j < d.A; ++j) { ha.bmin[j] = cfg->a_bound_min[j]; ha.bmax[j] = cfg->a_bound_max[j]; }
+    return 0;
+}
+
+static int train_value_head(const char* fn, const dm_policy* net, const float* targets_dev, float* values_out, dmt::HeadArgs& ha) {
+    if (net->pd.A != 1) return fail(std::string(fn) + ": the context has action_dim " + std::to_string(net->pd.A) + ", the value head needs a net with one output");
+    if (!targets_dev) return fail(std::string(fn) + ": null argument");
+    memset(&ha, 0, sizeof(ha));
+    ha.kind = dmt::HEAD_CRITIC; ha.targets = targets_dev; ha.out = values_out;
+    return 0;
+}
+
+// what the plain and the gated step refuse alike in their arrays and scalars
+static int train_step_ok(const char* fn, const float* params_dev, const float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum,
+                         double weight_decay, double grad_scale) {
+    if (!params_dev || !momentum_dev || !grads_dev) return fail(std::string(fn) + ": null argument");
+    if (P < 1) return fail(std::string(fn) + ": P must be >= 1");
+    if (!(stepsize >= 0.0 && std::isfinite(stepsize))) return fail(std::string(fn) + ": stepsize must be finite and >= 0");
+    if (!(momentum >= 0.0 && std::isfinite(momentum))) return fail(std::string(fn) + ": momentum must be finite and >= 0");
+    if (!(weight_decay >= 0.0 && std::isfinite(weight_decay))) return fail(std::string(fn) + ": weight_decay must be finite and >= 0");
+    if (!std::isfinite(grad_scale)) return fail(std::string(fn) + ": grad_scale must be finite");
+    return 0;
+}
+
 extern "C" {
 
 int64_t dm_train_param_count(const dm_policy* net) {
@@ -650,20 +700,8 @@ int dm_train_actor_grad(dm_policy* net, const float* params_dev, const float* st
                         void* workspace, int64_t workspace_bytes, void* hip_stream) {
     const char* fn = "dm_train_actor_grad";
     if (train_net_ok(fn, net)) return -1;
-    if (!actions_dev || !old_logp_dev || !adv_dev || !cfg) return fail(std::string(fn) + ": null argument");
-    if (!(cfg->ratio_clip > 0.0)) return fail(std::string(fn) + ": ratio_clip must be > 0");
-    if (!(cfg->bound_weight >= 0.0)) return fail(std::string(fn) + ": bound_weight must be >= 0");
-    if ((cfg->a_bound_min == nullptr) != (cfg->a_bound_max == nullptr)) return fail(std::string(fn) + ": a_bound_min and a_bound_max come together (both NULL: no bound loss)");
-    const dmp::PolicyDev& d = net->pd;
-    if (!d.logstd || !d.a_mean || !d.a_std) return fail(std::string(fn) + ": the context holds no logstd / a_mean / a_std");
-    if (d.A > dmt::kMaxA) return fail(std::string(fn) + ": action_dim above 128 is not compiled (the action bounds ride in the kernel arguments)");
-    dmt::HeadArgs ha; memset(&ha, 0, sizeof(ha));
-    ha.kind = dmt::HEAD_ACTOR; ha.actions = actions_dev; ha.old_logp = old_logp_dev; ha.adv = adv_dev; ha.out = logp_out;
-    ha.eps = (float)cfg->ratio_clip; ha.clip_lo = 1.0f - ha.eps; ha.clip_hi = 1.0f + ha.eps;
-    ha.bounded = cfg->a_bound_min ? 1 : 0;
-    ha.c0 = (-0.5f * (float)d.A) * 1.8378770664093453f;
-    if (n >= 1) ha.bwn = (float)cfg->bound_weight / (float)n;
-    if (ha.bounded) for (int j = 0; j < d.A; ++j) { ha.bmin[j] = cfg->a_bound_min[j]; ha.bmax[j] = cfg->a_bound_max[j]; }
+    dmt::HeadArgs ha;
+    if (train_actor_head(fn, net, n, actions_dev, old_logp_dev, adv_dev, cfg, logp_out, ha)) return -1;
     return train_grad(net, fn, params_dev, states_dev, goals_dev, goal_dim, n, ha, grads_dev, stats_dev, workspace, workspace_bytes, hip_stream);
 }
 
@@ -671,10 +709,8 @@ int dm_train_value_grad(dm_policy* net, const float* params_dev, const float* st
                         float* grads_dev, double* stats_dev, float* values_out, void* workspace, int64_t workspace_bytes, void* hip_stream) {
     const char* fn = "dm_train_value_grad";
     if (train_net_ok(fn, net)) return -1;
-    if (net->pd.A != 1) return fail(std::string(fn) + ": the context has action_dim " + std::to_string(net->pd.A) + ", the value head needs a net with one output");
-    if (!targets_dev) return fail(std::string(fn) + ": null argument");
-    dmt::HeadArgs ha; memset(&ha, 0, sizeof(ha));
-    ha.kind = dmt::HEAD_CRITIC; ha.targets = targets_dev; ha.out = values_out;
+    dmt::HeadArgs ha;
+    if (train_value_head(fn, net, targets_dev, values_out, ha)) return -1;
     return train_grad(net, fn, params_dev, states_dev, goals_dev, goal_dim, n, ha, grads_dev, stats_dev, workspace, workspace_bytes, hip_stream);
 }
 
@@ -771,12 +807,7 @@ int dm_train_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, co
                       double grad_scale, void* hip_stream) {
     const char* fn = "dm_train_sgd_step";
     if (net && train_net_ok(fn, net)) return -1;
-    if (!params_dev || !momentum_dev || !grads_dev) return fail(std::string(fn) + ": null argument");
-    if (P < 1) return fail(std::string(fn) + ": P must be >= 1");
-    if (!(stepsize >= 0.0 && std::isfinite(stepsize))) return fail(std::string(fn) + ": stepsize must be finite and >= 0");
-    if (!(momentum >= 0.0 && std::isfinite(momentum))) return fail(std::string(fn) + ": momentum must be finite and >= 0");
-    if (!(weight_decay >= 0.0 && std::isfinite(weight_decay))) return fail(std::string(fn) + ": weight_decay must be finite and >= 0");
-    if (!std::isfinite(grad_scale)) return fail(std::string(fn) + ": grad_scale must be finite");
+    if (train_step_ok(fn, params_dev, momentum_dev, grads_dev, P, stepsize, momentum, weight_decay, grad_scale)) return -1;
     dmt::SgdArgs a; memset(&a, 0, sizeof(a));
     dmt::Layout L; memset(&L, 0, sizeof(L));
     if (net) {

@@ -214,7 +214,7 @@ def all_reduce_normalizer(norm, device="cpu", group=None):
 
 
 def all_reduce_gradients(trainer, group=None):
-    """`MPISolver.update_flatgrad` of learning/solvers/mpi_solver.py:47-54 for an `ActorTrainer` / `CriticTrainer` / `DiscTrainer` (deepmimic_amd/train.py): the `grads` view of every
+    """`MPISolver.update_flatgrad` of learning/solvers/mpi_solver.py:47-54 for an `ActorTrainer` / `CriticTrainer` / `DiscTrainer` or a `GatedActorTrainer` / `GatedCriticTrainer` (deepmimic_amd/train.py; a gated trainer's `grads` holds its twenty arrays): the `grads` view of every
     rank is summed IN PLACE (RCCL on a GPU, gloo on the CPU test harness); follow it with `trainer.step(grad_scale=1.0 / world)`, which every rank then takes on the
     same sum, so the ranks' masters stay identical.  Ordered on torch's current stream, like the trainer's own calls."""
     import torch.distributed as dist

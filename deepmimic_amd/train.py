@@ -7,7 +7,12 @@ three-layer nets, on the `Policy` context that samples -- the forward pass runs 
     all_reduce_gradients(tr)                                                         # (deepmimic_amd/dist.py, several ranks)
     tr.step(grad_scale=1.0 / world)                                                  # momentum SGD on the fp32 masters, then the refresh of the context
 
-A checkpoint is `torch.save(tr.buf)`.  Gated contexts, Adam, a fused training kernel and step-size schedules are out of scope.
+A checkpoint is `torch.save(tr.buf)`.  Adam, a fused training kernel and step-size schedules are out of scope.
+
+The gated nets of the AMP task agents (fc_2layers_gated_1024units as ActorNet and CriticNet; `dm_train_gated_*`, deepmimic_amd/csrc/dm_train_gated.h) have trainers of
+their own with the same surface, `GatedActorTrainer` / `GatedCriticTrainer`, on a gated `Policy` or on the context inside a gated `heads.Critic`
+(`GatedCriticTrainer.from_policy(critic.net, weights, ...)`): the parameter block carries the gate's fourteen arrays behind the six plain ones (`gated_layout`), the
+backward pass runs through sigma, beta and the gate's hidden layers, and the step refreshes the gate in the context too.  The plain trainers refuse a gated context.
 
 The AMP discriminator update (AMPAgent._step_disc, learning/amp_agent.py:134-207, 251-257, 356-377; `dm_train_disc_grad`) is `DiscTrainer`, on the context inside a
 `heads.Discriminator`, so that the net that scores the style reward is the net that was trained:
@@ -16,8 +21,8 @@ The AMP discriminator update (AMPAgent._step_disc, learning/amp_agent.py:134-207
     dt.grad(expert_obs, agent_obs, grad_penalty=10.0, logit_reg=0.05)                # the two batches as dm_amp_expert_draw / dm_replay_sample fill them
     all_reduce_gradients(dt); dt.step(grad_scale=1.0 / world)                        # disc.eval_* now scores with the new weights
 
-`reference_grad` / `reference_step` / `reference_disc_grad` are the numpy statements of the arithmetic (the specification of include/dm_hip.h): the same rounding points -- bf16 operands, the head's
-fp32 operations one by one, the library's own exp -- with the contractions accumulated in float64."""
+`reference_grad` / `reference_step` / `reference_disc_grad` / `reference_gated_grad` are the numpy statements of the arithmetic (the specification of include/dm_hip.h): the same
+rounding points -- bf16 operands, the head's fp32 operations one by one, the library's own exp -- with the contractions accumulated in float64."""
 from __future__ import annotations
 
 import ctypes as C
@@ -26,8 +31,10 @@ from typing import Optional
 import numpy as np
 
 from .binding import check, stream_handle, tensor_arg, vp
+from .policy import GATE_KEYS
 
 KEYS = ("w1", "b1", "w2", "b2", "w3", "b3")
+GATED_KEYS = KEYS + GATE_KEYS           # the gated parameter block: matrices and their bias vectors alternate
 LN_2PI = np.float32(1.8378770664093453)
 
 
@@ -81,16 +88,17 @@ def workspace_bytes(policy, n: int) -> int:
     return int(b)
 
 
-def _need(policy):
-    if not hasattr(policy.lib, "dm_train_actor_grad"):
-        raise RuntimeError("libdm_hip: this library has no dm_train_* entry points (rebuild it)")
+def _need(policy, gated: bool = False):
+    if not hasattr(policy.lib, "dm_train_gated_actor_grad" if gated else "dm_train_actor_grad"):
+        raise RuntimeError("libdm_hip: this library has no dm_train_%s* entry points (rebuild it)" % ("gated_" if gated else ""))
 
 
 def actor_grad_device(policy, params_ptr: int, states_ptr: int, n: int, actions_ptr: int, old_logp_ptr: int, adv_ptr: int, grads_ptr: int, stats_ptr: int,
                       workspace_ptr: int, workspace_nbytes: int, ratio_clip: float = 0.2, bound_weight: float = 10.0, a_bound_min=None, a_bound_max=None,
-                      goals_ptr: int = 0, goal_dim: int = 0, logp_ptr: int = 0, stream: int = 0):
-    """raw device pointers (ints); a_bound_min / a_bound_max: host arrays of A un-normalised entries or None; asynchronous on `stream`"""
-    _need(policy)
+                      goals_ptr: int = 0, goal_dim: int = 0, logp_ptr: int = 0, stream: int = 0, gated: bool = False):
+    """raw device pointers (ints); a_bound_min / a_bound_max: host arrays of A un-normalised entries or None; asynchronous on `stream`.  gated: dm_train_gated_actor_grad,
+    the same parameter list on a gated context and its block and workspace"""
+    _need(policy, gated)
     lo = None if a_bound_min is None else np.ascontiguousarray(a_bound_min, dtype=np.float32)
     hi = None if a_bound_max is None else np.ascontiguousarray(a_bound_max, dtype=np.float32)
     for b in (lo, hi):
@@ -98,16 +106,17 @@ def actor_grad_device(policy, params_ptr: int, states_ptr: int, n: int, actions_
             raise ValueError("action bounds must have %d entries" % policy.A)
     fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
     cfg = _ActorCfg(float(ratio_clip), float(bound_weight), fp(lo), fp(hi))
-    check(policy.lib, policy.lib.dm_train_actor_grad(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(actions_ptr), vp(old_logp_ptr),
-                                                     vp(adv_ptr), C.cast(C.pointer(cfg), C.c_void_p), vp(grads_ptr), vp(stats_ptr), vp(logp_ptr), vp(workspace_ptr),
-                                                     int(workspace_nbytes), vp(stream)))
+    call = policy.lib.dm_train_gated_actor_grad if gated else policy.lib.dm_train_actor_grad
+    check(policy.lib, call(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(actions_ptr), vp(old_logp_ptr), vp(adv_ptr),
+                           C.cast(C.pointer(cfg), C.c_void_p), vp(grads_ptr), vp(stats_ptr), vp(logp_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
 
 
 def value_grad_device(policy, params_ptr: int, states_ptr: int, n: int, targets_ptr: int, grads_ptr: int, stats_ptr: int, workspace_ptr: int, workspace_nbytes: int,
-                      goals_ptr: int = 0, goal_dim: int = 0, values_ptr: int = 0, stream: int = 0):
-    _need(policy)
-    check(policy.lib, policy.lib.dm_train_value_grad(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(targets_ptr), vp(grads_ptr),
-                                                     vp(stats_ptr), vp(values_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
+                      goals_ptr: int = 0, goal_dim: int = 0, values_ptr: int = 0, stream: int = 0, gated: bool = False):
+    _need(policy, gated)
+    call = policy.lib.dm_train_gated_value_grad if gated else policy.lib.dm_train_value_grad
+    check(policy.lib, call(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(targets_ptr), vp(grads_ptr), vp(stats_ptr), vp(values_ptr),
+                           vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
 
 
 def sgd_step_device(policy, params_ptr: int, momentum_ptr: int, grads_ptr: int, P: int, stepsize: float, momentum: float, weight_decay: float = 0.0,
@@ -135,12 +144,19 @@ class _Trainer:
     """Owns buf [3, P] float32 = (params, momentum, grads) and the workspace, on `device` (the policy's GPU; "cpu" with the emulator build of the tests, where device
     memory is host memory).  Every call runs on torch's current stream."""
     N_STATS = 0
+    GATED = False
+    # what a trainer of another kind of net replaces: the block's length, packing and views, the workspace's size and the step
+    _param_count = staticmethod(param_count)
+    _pack = staticmethod(pack_params)
+    _unpack = staticmethod(lambda flat, p: unpack_params(flat, p.S, p.H1, p.H2, p.A))
+    _workspace_bytes = staticmethod(workspace_bytes)
+    _step = staticmethod(sgd_step_device)
 
     def __init__(self, policy, buf, stepsize: float, momentum: float, weight_decay: float):
         import torch
-        _need(policy)
+        _need(policy, self.GATED)
         self.policy, self.buf = policy, buf
-        self.P = param_count(policy)
+        self.P = self._param_count(policy)
         tensor_arg("buf", buf, buf.device, torch.float32, [(3, self.P)])
         self.device = buf.device
         self.params, self.momentum, self.grads = buf[0], buf[1], buf[2]
@@ -153,7 +169,7 @@ class _Trainer:
         """masters from the weights dict the policy was built from (zero momentum), then `sync()`"""
         import torch
         dev = torch.device("cuda", policy.device_id) if device is None else torch.device(device)
-        flat = pack_params(weights)
+        flat = cls._pack(weights)
         buf = torch.zeros((3, flat.size), dtype=torch.float32, device=dev)
         buf[0].copy_(torch.from_numpy(flat))
         tr = cls(policy, buf, stepsize, momentum, weight_decay)
@@ -164,9 +180,8 @@ class _Trainer:
         return stream_handle(self.device) if self.device.type == "cuda" else 0
 
     def views(self, which: str = "params") -> dict:
-        """w1 .. b3 as views of params / momentum / grads"""
-        p = self.policy
-        return unpack_params(getattr(self, which), p.S, p.H1, p.H2, p.A)
+        """w1 .. b3 (a gated trainer: and the gate's arrays) as views of params / momentum / grads"""
+        return self._unpack(getattr(self, which), self.policy)
 
     def sync(self):
         """packs the masters into the context (the precondition of grad: its bf16 weights are the rounding of params)"""
@@ -175,7 +190,7 @@ class _Trainer:
     def _workspace(self, n: int):
         import torch
         if n > self._work_rows:
-            self._work_bytes = workspace_bytes(self.policy, n)
+            self._work_bytes = self._workspace_bytes(self.policy, n)
             self._work = torch.zeros((self._work_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
             self._work_rows = n
         return self._work.data_ptr(), self._work_bytes
@@ -190,8 +205,8 @@ class _Trainer:
         return n, G
 
     def step(self, grad_scale: float = 1.0):
-        sgd_step_device(self.policy, self.params.data_ptr(), self.momentum.data_ptr(), self.grads.data_ptr(), self.P, self.stepsize, self.mom, self.weight_decay,
-                        grad_scale, stream=self._stream())
+        self._step(self.policy, self.params.data_ptr(), self.momentum.data_ptr(), self.grads.data_ptr(), self.P, self.stepsize, self.mom, self.weight_decay,
+                   grad_scale, stream=self._stream())
 
     def stats(self):
         """the statistics of the last grad call, a float64 device tensor (no synchronisation here)"""
@@ -212,7 +227,7 @@ class ActorTrainer(_Trainer):
         ws, nbytes = self._workspace(n)
         actor_grad_device(self.policy, self.params.data_ptr(), states.data_ptr(), n, actions.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), self.grads.data_ptr(),
                           self._stats.data_ptr(), ws, nbytes, ratio_clip, bound_weight, a_bound_min, a_bound_max, 0 if goals is None else goals.data_ptr(), G,
-                          0 if logp_out is None else logp_out.data_ptr(), self._stream())
+                          0 if logp_out is None else logp_out.data_ptr(), self._stream(), self.GATED)
 
 
 class CriticTrainer(_Trainer):
@@ -227,7 +242,104 @@ class CriticTrainer(_Trainer):
             tensor_arg("values_out", values_out, self.device, torch.float32, [(n,)])
         ws, nbytes = self._workspace(n)
         value_grad_device(self.policy, self.params.data_ptr(), states.data_ptr(), n, targets.data_ptr(), self.grads.data_ptr(), self._stats.data_ptr(), ws, nbytes,
-                          0 if goals is None else goals.data_ptr(), G, 0 if values_out is None else values_out.data_ptr(), self._stream())
+                          0 if goals is None else goals.data_ptr(), G, 0 if values_out is None else values_out.data_ptr(), self._stream(), self.GATED)
+
+
+# ---- the gated nets (dm_train_gated_*)
+
+def gated_layout(S: int, H1: int, H2: int, A: int, G: int, GC: int, GH: int) -> dict:
+    """{key: (offset in floats, shape)} of the gated parameter block -- the six plain arrays, then the gate's in the order of dm_policy_gate_params -- and "P" -> its length"""
+    shapes = dict(w1=(S, H1), b1=(H1,), w2=(H1, H2), b2=(H2,), w3=(H2, A), b3=(A,), gc_w=(G, GC), gc_b=(GC,))
+    for i, H in ((0, H1), (1, H2)):
+        shapes.update({"g%d_w" % i: (GC, GH), "g%d_b" % i: (GH,), "g%d_bias_w" % i: (GH, H), "g%d_bias_b" % i: (H,), "g%d_scale_w" % i: (GH, H), "g%d_scale_b" % i: (H,)})
+    out, at = {}, 0
+    for k in GATED_KEYS:
+        out[k] = (at, shapes[k]); at += int(np.prod(shapes[k]))
+    out["P"] = at
+    return out
+
+
+def gated_dims(weights: dict) -> tuple:
+    """(S, H1, H2, A, G, GC, GH) of a gated weights dict"""
+    S, H1 = np.shape(weights["w1"]); H2, A = np.shape(weights["w3"])
+    return S, H1, H2, A, int(weights["goal_dim"]), np.shape(weights["gc_w"])[1], np.shape(weights["g0_w"])[1]
+
+
+def pack_gated_params(weights: dict) -> np.ndarray:
+    """the float32 parameter block of a gated weights dict (GATED_KEYS, tf.layers.dense layout)"""
+    return np.concatenate([np.ascontiguousarray(weights[k], dtype=np.float32).reshape(-1) for k in GATED_KEYS])
+
+
+def unpack_gated_params(flat, S: int, H1: int, H2: int, A: int, G: int, GC: int, GH: int) -> dict:
+    """views of a gated parameter block under GATED_KEYS (numpy array or torch tensor)"""
+    lay = gated_layout(S, H1, H2, A, G, GC, GH)
+    return {k: flat[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))].reshape(lay[k][1]) for k in GATED_KEYS}
+
+
+def gated_workspace_layout(H1: int, H2: int, A: int, G: int, GC: int, GH: int, n: int) -> dict:
+    """{name: (byte offset, dtype, shape)} of what a gated *_grad call leaves in its workspace: the pieces of `workspace_layout` (dz2 / dz1 hold dp_1 / dp_0), then the
+    gate split, the gate's activations and their gradients, bf16; "bytes": the total"""
+    KG = (G + 31) // 32 * 32
+    out = workspace_layout(H1, H2, A, n)
+    at = out.pop("bytes")
+    for name, width in (("du1", H2), ("du0", H1), ("da1", H2), ("da0", H1), ("xg", KG), ("c", GC), ("e0", GH), ("e1", GH), ("dze0", GH), ("dze1", GH), ("dzc", GC)):
+        out[name] = (at, np.uint16, (n, width)); at += (n * width * 2 + 15) // 16 * 16
+    out["bytes"] = at
+    return out
+
+
+def gated_param_count(policy) -> int:
+    _need(policy, True)
+    n = policy.lib.dm_train_gated_param_count(policy.h)
+    check(policy.lib, n < 0)
+    return int(n)
+
+
+def gated_workspace_bytes(policy, n: int) -> int:
+    _need(policy, True)
+    b = policy.lib.dm_train_gated_workspace_bytes(policy.h, int(n))
+    check(policy.lib, b < 0)
+    return int(b)
+
+
+def gated_sgd_step_device(policy, params_ptr: int, momentum_ptr: int, grads_ptr: int, P: int, stepsize: float, momentum: float, weight_decay: float = 0.0,
+                          grad_scale: float = 1.0, stream: int = 0):
+    """the momentum step on a gated block (weight decay on its ten matrices), then the refresh of the context, gate included; the net is required"""
+    _need(policy, True)
+    check(policy.lib, policy.lib.dm_train_gated_sgd_step(policy.h, vp(params_ptr), vp(momentum_ptr), vp(grads_ptr), int(P), float(stepsize), float(momentum),
+                                                         float(weight_decay), float(grad_scale), vp(stream)))
+
+
+GATED_READ = ("s16", "h1", "h2", "sigma0", "beta0", "sigma1", "beta1")
+
+
+def read_gated(policy, which: str, n: int) -> np.ndarray:
+    """test support: the first n rows of "s16" [n, K1], "h1", "h2" (bf16 bits, uint16) or "sigma0", "beta0" [n, H1], "sigma1", "beta1" [n, H2] (float32) as the last call
+    left them; synchronises"""
+    _need(policy, True)
+    i = GATED_READ.index(which)
+    width = (policy.info()["K1"], policy.H1, policy.H2, policy.H1, policy.H1, policy.H2, policy.H2)[i]
+    out = np.zeros((int(n), width), np.uint16 if i < 3 else np.float32)
+    check(policy.lib, policy.lib.dm_train_gated_read(policy.h, i, int(n), out.ctypes.data, out.nbytes))
+    return out
+
+
+class _GatedHooks:
+    """what turns a trainer into the one of a gated context: the gated block, workspace and step"""
+    GATED = True
+    _param_count = staticmethod(gated_param_count)
+    _pack = staticmethod(pack_gated_params)
+    _unpack = staticmethod(lambda flat, p: unpack_gated_params(flat, p.S, p.H1, p.H2, p.A, *p.gate_dims))
+    _workspace_bytes = staticmethod(gated_workspace_bytes)
+    _step = staticmethod(gated_sgd_step_device)
+
+
+class GatedActorTrainer(_GatedHooks, ActorTrainer):
+    """ActorTrainer on a gated `Policy`: views() has the twenty arrays of GATED_KEYS, sync() and step() refresh the gate as well"""
+
+
+class GatedCriticTrainer(_GatedHooks, CriticTrainer):
+    """CriticTrainer on a gated context with one output, e.g. `from_policy(critic.net, weights, ...)` of a gated `heads.Critic`"""
 
 
 # ---- the AMP discriminator update
@@ -582,3 +694,131 @@ def reference_disc_grad(weights: dict, expert_obs, agent_obs, grad_penalty: floa
     sqs = {k: (np.asarray(w[k], f).astype(d) ** 2).sum() for k in ("w1", "w2", "w3")}
     out["stats"] = np.concatenate([hd["stats"], [pen_stat, 0.5 * sqs["w3"], 0.5 * (sqs["w1"] + sqs["w2"] + sqs["w3"])]])
     return out
+
+
+# ---- the gated update in numpy
+
+def reference_gated_forward_bf16(weights: dict, states, s_clip=np.inf, rounded=True):
+    """The forward pass of the gated net at the rounding points of dm_policy.h GateDev, contractions in float64: dict(s16 [n, S], xg [n, G], c, e0, e1, h1, h2 -- bf16 VALUES
+    --, sigma0, beta0, u0, sigma1, beta1, u1 (u_i = W_i h + b_i as the gate split recomputes it) and z3 [n, A], float32).  sigma uses numpy's exp: the platform's, like the
+    device's own expf, so it is the device's bits only where sigma is exactly 0, 1 or 2.  rounded=False: nothing is rounded, every array float64."""
+    d = np.float64
+    f = np.float32 if rounded else d
+    R = bf16_round if rounded else (lambda x: np.asarray(x, d))
+    F = lambda x: np.asarray(x).astype(f)
+    S, G = np.shape(weights["w1"])[0], int(weights["goal_dim"])
+    sm, ss = weights.get("s_mean"), weights.get("s_std")
+    inv_std = np.float32(1) / (np.float32(1) if ss is None else np.asarray(ss, np.float32))        # the context holds 1 / s_std as a float32 array: a parameter, not a rounding point
+    x = (F(states) - (f(0) if sm is None else F(sm))) * F(inv_std)
+    out = dict(s16=R(np.clip(x, -s_clip, s_clip)))
+    out["xg"] = out["s16"][:, S - G:]
+    # one dense layer: the float64 contraction of (bf16) operands rounded to float32, then the bias by one float32 add
+    dense = lambda h, wk, bk: F(np.asarray(h, d) @ np.asarray(R(weights[wk]), d)) + F(weights[bk])
+    gate = lambda h, k: dense(h, k + "_w", k + "_b")
+    out["c"] = R(np.maximum(gate(out["xg"], "gc"), f(0)))
+    h = out["s16"]
+    for i in (0, 1):
+        e = R(np.maximum(gate(out["c"], "g%d" % i), f(0)))
+        beta = gate(e, "g%d_bias" % i)
+        with np.errstate(over="ignore"):
+            sigma = F(f(2) / (f(1) + np.exp(-gate(e, "g%d_scale" % i))))
+        u = dense(h, "w%d" % (i + 1), "b%d" % (i + 1))
+        p = fma32(sigma, u, beta) if rounded else sigma * u + beta
+        h = R(np.maximum(p, f(0)))
+        out.update({"e%d" % i: e, "beta%d" % i: beta, "sigma%d" % i: sigma, "u%d" % i: u, "h%d" % (i + 1): h})
+    out["z3"] = dense(h, "w3", "b3")
+    return out
+
+
+def reference_gate_split(dp, u, sigma, rounded=True):
+    """k_train_gate_split per element: (du, da) = (bf16(dp sigma), bf16((dp u) ds)) with ds = sigma fmaf(-0.5, sigma, 1), every operation in float32, as bf16 VALUES;
+    rounded=False: the same algebra in float64"""
+    if not rounded:
+        dp, u, sigma = (np.asarray(v, np.float64) for v in (dp, u, sigma))
+        return dp * sigma, dp * u * (sigma * (1.0 - 0.5 * sigma))
+    f = np.float32
+    dp, u, sigma = (np.asarray(v, f) for v in (dp, u, sigma))
+    with np.errstate(invalid="ignore", over="ignore"):
+        ds = sigma * fma32(f(-0.5), sigma, f(1.0))
+        return bf16_round(dp * sigma), bf16_round((dp * u) * ds)
+
+
+def reference_gated_backward(weights: dict, fwd: dict, dz3, rounded=True):
+    """The backward pass from dz3 [n, A] (values) and the arrays of reference_gated_forward_bf16: dict(grads {key: array} over GATED_KEYS, and the stages dp1, dp0, du1, du0,
+    da1, da0, dze0, dze1, dzc as values); contractions in float64, results float32 and the stages bf16 where the device stores them (rounded=False: float64 throughout)"""
+    d = np.float64
+    f = np.float32 if rounded else d
+    R = bf16_round if rounded else (lambda x: np.asarray(x, d))
+    W = lambda k: np.asarray(R(weights[k]), d)
+    mm = lambda a, b: np.asarray(a, d) @ np.asarray(b, d)
+    # bf16((sum of dz W^T over the pairs) . [h != 0]): one float64 contraction, rounded to float32, masked, rounded to bf16
+    back = lambda h, *pairs: R(np.where(h != 0, sum(mm(dz, W(k).T) for dz, k in pairs).astype(f), f(0)))
+    g, st = {}, {}
+    def wb(wk, bk, a, dz):
+        g[wk] = mm(np.asarray(a).T, dz).astype(f); g[bk] = np.asarray(dz, d).sum(axis=0).astype(f)
+    dz3 = np.asarray(dz3, d)
+    wb("w3", "b3", fwd["h2"], dz3)
+    st["dp1"] = back(fwd["h2"], (dz3, "w3"))
+    st["du1"], st["da1"] = reference_gate_split(st["dp1"], fwd["u1"], fwd["sigma1"], rounded)
+    wb("w2", "b2", fwd["h1"], st["du1"])
+    st["dp0"] = back(fwd["h1"], (st["du1"], "w2"))
+    st["du0"], st["da0"] = reference_gate_split(st["dp0"], fwd["u0"], fwd["sigma0"], rounded)
+    wb("w1", "b1", fwd["s16"], st["du0"])
+    for i in (0, 1):
+        e, dp, da = fwd["e%d" % i], st["dp%d" % i], st["da%d" % i]
+        wb("g%d_bias_w" % i, "g%d_bias_b" % i, e, dp)
+        wb("g%d_scale_w" % i, "g%d_scale_b" % i, e, da)
+        st["dze%d" % i] = back(e, (dp, "g%d_bias_w" % i), (da, "g%d_scale_w" % i))
+        wb("g%d_w" % i, "g%d_b" % i, fwd["c"], st["dze%d" % i])
+    st["dzc"] = back(fwd["c"], (st["dze0"], "g0_w"), (st["dze1"], "g1_w"))
+    wb("gc_w", "gc_b", fwd["xg"], st["dzc"])
+    return dict(st, grads=g)
+
+
+def _head64(z3, head: str, weights: dict, kw: dict):
+    """the heads in float64, nothing rounded: dz3 [n, A] of the PPO surrogate + bound loss (actor) or of 0.5 MSE (critic)"""
+    d = np.float64
+    z3 = np.asarray(z3, d); n, A = z3.shape
+    if head != "actor":
+        return (z3 - np.asarray(kw["targets"], d)[:, None]) / n
+    dflt = lambda k, v: np.full(A, v, d) if weights.get(k) is None else np.asarray(weights[k], d)
+    mean, std, sg = dflt("a_mean", 0), dflt("a_std", 1), np.exp(dflt("logstd", 0))
+    u = ((np.asarray(kw["actions"], d) - mean) / std - z3) / sg
+    logp = -0.5 * (u ** 2).sum(axis=1) - 0.5 * A * np.log(2 * np.pi) - np.log(sg).sum()
+    ratio, adv, eps = np.exp(logp - np.asarray(kw["old_logp"], d)), np.asarray(kw["adv"], d), kw.get("ratio_clip", 0.2)
+    l0, l1 = adv * ratio, adv * np.clip(ratio, 1 - eps, 1 + eps)
+    dz = np.where(~(l0 > l1), -(l0 / n), 0.0)[:, None] * (u / sg)
+    if kw.get("a_bound_min") is not None:
+        lo, hi = (np.asarray(kw["a_bound_min"], d) - mean) / std, (np.asarray(kw["a_bound_max"], d) - mean) / std
+        dz = dz + kw.get("bound_weight", 10.0) / n * (np.minimum(z3 - lo, 0) + np.maximum(z3 - hi, 0))
+    return dz
+
+
+def reference_gated_grad(weights: dict, states, head: str, s_clip=np.inf, rounded=True, **kw):
+    """The whole dm_train_gated_*_grad call in numpy (kw as reference_grad; `states` holds the goal columns): the arrays of reference_gated_forward_bf16 and
+    reference_gated_backward, `grads` also flat as "flat" [P], and with rounded=True the head's own outputs (dz3 bits, logp / values, stats).  rounded=False drops every
+    bf16 and float32 rounding -- the algebra alone, for a check against autograd."""
+    out = reference_gated_forward_bf16(weights, states, s_clip, rounded)
+    if not rounded:
+        dz3 = _head64(out["z3"], head, weights, kw)
+    else:
+        A = out["z3"].shape[1]
+        if head == "actor":
+            dflt = lambda k, v: np.full(A, v, np.float32) if weights.get(k) is None else weights[k]
+            hd = reference_actor_head(out["z3"], a_mean=dflt("a_mean", 0), a_std=dflt("a_std", 1), logstd=dflt("logstd", 0), **kw)
+        else:
+            hd = reference_value_head(out["z3"], **kw)
+        out.update(hd)
+        dz3 = bf16_value(hd["dz3"])[:, :A]
+    out.update(reference_gated_backward(weights, out, dz3, rounded))
+    out["flat"] = np.concatenate([np.asarray(out["grads"][k]).reshape(-1) for k in GATED_KEYS])
+    return out
+
+
+def gated_matrix_mask_of(S: int, H1: int, H2: int, A: int, G: int, GC: int, GH: int) -> np.ndarray:
+    """the entries of a gated block under the weight decay: its ten matrices"""
+    lay = gated_layout(S, H1, H2, A, G, GC, GH)
+    m = np.zeros(lay["P"], bool)
+    for k in GATED_KEYS[0::2]:
+        m[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))] = True
+    return m

@@ -723,7 +723,8 @@ int dm_time_warp_align(int device_id, int n_envs, int capacity, int dim, int f64
  * and names its reason through dm_last_error.  The one object is the dm_policy whose net is trained: its packed bf16 weights and its activation buffers s16 / h1 / h2 are
  * read and written; the buffers grow to the largest n as in dm_policy_forward_ex (the one allocation).  ORDERING: like dm_policy_set_weights, a training call must not
  * run while another stream runs a forward, a scalar evaluation, a refresh or another training call of the same context -- order them with events or use one stream.
- * Out of scope: gated contexts, Adam, one fused training kernel, step-size schedules (the step size is an argument).  The AMP discriminator update is dm_train_disc_grad below.
+ * Out of scope: Adam, one fused training kernel, step-size schedules (the step size is an argument).  The AMP discriminator update is dm_train_disc_grad below; gated
+ * contexts have entry points of their own, dm_train_gated_* further below, and these calls refuse them.
  *
  * Parameter block: P = dm_train_param_count(net) floats in the order w1 [S x H1], b1, w2 [H1 x H2], b2, w3 [H2 x A], b3; matrices in tf.layers.dense layout (in x out,
  * row-major), true widths, no padding.  The caller holds three such arrays: masters, momentum, gradients.
@@ -811,6 +812,54 @@ typedef struct dm_train_disc_cfg { double grad_penalty, logit_reg; } dm_train_di
 int64_t dm_train_disc_workspace_bytes(const dm_policy* net, int n_expert, int n_agent);      /* < 0: refused (dm_last_error) */
 int dm_train_disc_grad(dm_policy* net, const float* params_dev, const float* expert_obs_dev, int n_expert, const float* agent_obs_dev, int n_agent,
                        const dm_train_disc_cfg* cfg, float* grads_dev, double* stats_dev, float* logits_out, void* workspace, int64_t workspace_bytes, void* hip_stream);
+
+/* ---- The PPO actor and critic minibatch updates for GATED contexts (deepmimic_amd/csrc/dm_train_gated.h, deepmimic_amd/train.py GatedActorTrainer / GatedCriticTrainer):
+ * the nets of the AMP task agents (ct_agent_humanoid_amp_tasks*.txt: "ActorNet" and "CriticNet" fc_2layers_gated_1024units), trained on the context that samples
+ * (dm_policy_create_gated).  New entry points beside the dm_train_* of the plain nets, which keep refusing a gated context; the rules of that section hold: stateless, DEVICE
+ * pointers, asynchronous on hip_stream, nothing allocated beyond the context's activation buffers, a refused call launches and writes nothing and names its reason, the
+ * ORDERING rule, the PRECONDITION (the packed weights of all twenty arrays are the RNE bf16 of params_dev; dm_train_gated_sgd_step keeps it true, dm_policy_set_weights with
+ * the gate struct from the block establishes it), the actor and critic heads, the statistics and dm_train_actor_cfg unchanged.
+ *
+ * Notation (dm_policy_gate_params; i = 0: layer 1, width H1; i = 1: layer 2, width H2; GC = gate_common, GH = gate_hidden, G = goal_dim, KG = G rounded up to 32):
+ *   xg = the bf16 goal block of s16;  c = relu(Wc xg + bc);  e_i = relu(We_i c + be_i);  beta_i = Wb_i e_i + bb_i;  sigma_i = 2 sigmoid(Ws_i e_i + bs_i);
+ *   u_i = W_i h_(i-1) + b_i;  p_i = fmaf(sigma_i, u_i, beta_i);  h_i = bf16(relu(p_i)).
+ * Arithmetic (the specification; deepmimic_amd/train.py reference_gated_grad states it in numpy):
+ *   forward   the context's per-layer gated route, forced: k_policy_prep, k_policy_gate, the GATED layer kernels as the widths choose them: s16, h1, h2 in bf16 and
+ *             sigma_i, beta_i in fp32 with the rounding points of dm_policy.h GateDev.  xg [n x KG] (padding columns zero), c [n x GC], e_0, e_1 [n x GH] are formed once
+ *             more by the function the forward uses (dmp::gate_hidden: the same bits) and written to the workspace as row-major bf16.
+ *   head, statistics, layer 3   as in the plain section: dW3 = h2^T dz3, db3, dp_1 = bf16((dz3 W3^T) . [h2 != 0]).
+ *   gate split   once per hidden layer, i = 1 then 0.  acc is recomputed by the forward's chain (packed bf16 fragments, k-steps ascending from a zero accumulator), u = acc + b.
+ *             Per element in fp32, one rounding per written operation, dp the bf16 value: du = bf16(dp sigma);  t = fmaf(-0.5, sigma, 1), ds = sigma t (dsigma/dz of
+ *             sigma = 2 sigmoid(z));  da = bf16((dp u) ds).  The ReLU mask [h != 0] is already inside dp.  sigma = 0 and sigma = 2 give ds = 0; a NaN propagates.
+ *   main layers  as in the plain section from du_i in dz_i's place: dW_i = in^T du_i, db_i = the column sums of du_i, dp_0 = bf16((du_1 W2^T) . [h1 != 0]).
+ *   gate projections   dWb_i = e_i^T dp_i, dbb_i = the column sums of dp_i;  dWs_i = e_i^T da_i, dbs_i = the column sums of da_i.
+ *   gate hidden layers   dze_i = bf16((dp_i Wb_i^T + da_i Ws_i^T) . [e_i != 0]): ONE accumulator started at zero, the k-steps of the beta pair ascending, then those of the
+ *             sigma pair; B operands the RNE bf16 of the masters.  dWe_i = c^T dze_i, dbe_i its column sums.  dzc = bf16((dze_0 We_0^T + dze_1 We_1^T) . [c != 0]) the same
+ *             way, pair 0 first.  dWc = xg^T dzc over the true G rows, dbc its column sums.  Nothing flows into the observations.
+ *   Every gradient element is written by its one owner from one contraction: no split contraction, no atomic, no partial; two calls on one input give the same bytes, in
+ *   the workspace as well.
+ *   step      k_train_sgd's arithmetic per element; the weight decay falls on all TEN matrices and on none of the ten vectors (_weight_decay_loss drops only variables
+ *             whose name contains "bias"; gate{i}/dense/kernel, the beta projection, is not one).  Then the context is refreshed from the new masters, gate included
+ *             (dm_policy_set_weights with both structs and DM_DEVICE_PTRS on views of params_dev).
+ * Parameter block: P = dm_train_gated_param_count(net) floats: the six arrays of the plain block, then the gate's in the order of dm_policy_gate_params -- gc_w [G x GC],
+ *   gc_b, g0_w [GC x GH], g0_b, g0_bias_w [GH x H1], g0_bias_b, g0_scale_w, g0_scale_b, then g1_* with H2 -- tf.layers.dense layout, true widths, no padding.
+ * Workspace (dm_train_gated_workspace_bytes(net, n), 16-byte aligned), left behind: the five pieces of the plain section, its dz2 / dz1 slots holding dp_1 / dp_0, then, all
+ *   bf16 and each piece starting on a multiple of 16 bytes,
+ *   [du_1 n x H2][du_0 n x H1][da_1 n x H2][da_0 n x H1][xg n x KG][c n x GC][e_0 n x GH][e_1 n x GH][dze_0 n x GH][dze_1 n x GH][dzc n x GC].
+ * Refused: a NULL net; a PLAIN context (dm_policy_create: "a plain context"); everything the plain calls refuse in the same words; a goal_dim other than 0 or the gate's;
+ * in the step P != dm_train_gated_param_count(net).  dm_train_gated_sgd_step needs its net.
+ * dm_train_gated_read: TEST SUPPORT, synchronous: the first n rows of s16 (which = 0), h1 (1), h2 (2) in bf16 or of sigma_0 (3), beta_0 (4) [n x H1], sigma_1 (5),
+ * beta_1 (6) [n x H2] in fp32, as the last call left them, to the host. */
+int64_t dm_train_gated_param_count(const dm_policy* net);                 /* < 0: refused (dm_last_error) */
+int64_t dm_train_gated_workspace_bytes(const dm_policy* net, int n);      /* < 0: refused (dm_last_error) */
+int dm_train_gated_actor_grad(dm_policy* net, const float* params_dev, const float* states_dev, const float* goals_dev, int goal_dim, int n, const float* actions_dev,
+                              const float* old_logp_dev, const float* adv_dev, const dm_train_actor_cfg* cfg, float* grads_dev, double* stats_dev, float* logp_out,
+                              void* workspace, int64_t workspace_bytes, void* hip_stream);
+int dm_train_gated_value_grad(dm_policy* net, const float* params_dev, const float* states_dev, const float* goals_dev, int goal_dim, int n, const float* targets_dev,
+                              float* grads_dev, double* stats_dev, float* values_out, void* workspace, int64_t workspace_bytes, void* hip_stream);
+int dm_train_gated_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum,
+                            double weight_decay, double grad_scale, void* hip_stream);
+int dm_train_gated_read(dm_policy* net, int which, int n, void* host_out, size_t capacity);
 
 /* ---- a probe for the device math helpers(deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
  * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
