@@ -47,6 +47,13 @@ static void launch_layers(int path, int n, rt_stream stream, const dmp::PolicyDe
     }
 }
 
+// The per-layer route for the widths: the LDS-tiled four-wave GEMM of height `tile` when the width allows it (a multiple of 128) and `tiled`, the one-wave kernel otherwise.
+// With its defaults it is the route the trainers force (dm_train.h train_forward), whatever DM_POLICY_* says.
+static int policy_path_layered(const dmp::PolicyDev& d, bool tiled = true, int tile = DM_POLICY_LAYER_TILE64) {
+    const int l1 = (tiled && d.H1 % 128 == 0) ? tile : DM_POLICY_LAYER_ONE_WAVE, l2 = (tiled && d.H2 % 128 == 0) ? tile : DM_POLICY_LAYER_ONE_WAVE;
+    return DM_POLICY_PATH_LAYERED(l1, l2);
+}
+
 // The ONE place that decides which kernels a forward call runs (ids: include/dm_hip.h dm_policy_path): dm_policy_forward_ex launches from the id
 // this returns and dm_policy_info reports it, so the report cannot drift from the launch.
 // One launch for the whole actor (k_policy_fused) where it is compiled for the widths; DM_POLICY_LAYERED=1 keeps the per-layer kernels (A/B, tests).
@@ -61,8 +68,7 @@ static int policy_path(const dmp::PolicyDev& d) {
     const bool tiled = (getenv("DM_POLICY_ONE_WAVE") == nullptr);
     int tile = DM_POLICY_LAYER_TILE64;
     if (const char* tl = getenv("DM_POLICY_TILE")) if (atoi(tl) == 128) tile = DM_POLICY_LAYER_TILE128;
-    const int l1 = (tiled && d.H1 % 128 == 0) ? tile : DM_POLICY_LAYER_ONE_WAVE, l2 = (tiled && d.H2 % 128 == 0) ? tile : DM_POLICY_LAYER_ONE_WAVE;
-    return DM_POLICY_PATH_LAYERED(l1, l2);
+    return policy_path_layered(d, tiled, tile);
 }
 
 extern "C" {

@@ -19,7 +19,10 @@
 // k_train_bgrad   db = the column sums of the same bf16 dz in fp32: per column four contiguous row quarters, each ascending, added in order.
 // k_train_dgrad   dz_prev [M x H] = (dz W^T) . [h != 0]: A fragments are 16 bytes of a dz row, B fragments 8 consecutive floats of a master row converted on load (zeros
 //                 past the true width of w3), the ReLU mask and the bf16 store in the epilogue.  A wavefront owns 32 rows x 32 columns.
-// k_train_sgd     the momentum step, a grid-stride loop over P: the new momentum from exact fp64 products, rounded once; the master by one fmaf.
+// k_train_sgd<NMAT>   the momentum step, a grid-stride loop over P: the new momentum from exact fp64 products, rounded once; the master by one fmaf.  NMAT: the matrix
+//                 ranges under the weight decay, 3 (a plain block) or GATED_MATRICES (a gated one, dm_train_gated.h).
+// The 32 x 32 tiles share a toolkit of inline functions (tile_zero, tile_chain_packed, tile_store_masked); the host side has one forward (train_forward), one backward
+// launcher (TrainBackward), one step (train_sgd) and one read (train_read), which dm_train_gated.h calls too.
 // A non-finite input (observation past the normaliser's clip, action, advantage, old logp, target, master) reaches the gradients as a non-finite value: bf16_rne keeps a
 // NaN a NaN, nothing clamps.  (A NaN OBSERVATION is not one: k_policy_prep turns it into -s_clip, as for the sampling net.)
 #pragma once
@@ -39,6 +42,60 @@ DMP_DEV uint16_t bf16_rne(float f) {
 }
 
 DMP_DEV float bf16_f32(uint16_t h) { return __builtin_bit_cast(float, (uint32_t)h << 16); }
+
+// ---- the tile toolkit.  A wavefront's 32 x 32 tile is f32x4 acc[2][2]: acc[i][j][r] is row 16 i + 4 g + r, column 16 j + c of the tile (c = lane & 15, g = lane >> 4).
+template <int N>
+DMP_DEV void tile_zero(f32x4 (&acc)[N]) {
+#pragma unroll
+    for (int j = 0; j < N; ++j)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[j][r] = 0.0f;
+}
+template <int N, int M>
+DMP_DEV void tile_zero(f32x4 (&acc)[N][M]) {
+#pragma unroll
+    for (int i = 0; i < N; ++i) tile_zero(acc[i]);
+}
+
+// acc += in[m0 .., :] W[:, n0 ..] with W's PACKED bf16 fragments as the B operand (16 bytes per lane per k-step, what the layer kernels read): in [M x 32 KS] (a row past
+// M reads row 0), wp the fragments of W [32 KS x N]; k-steps ascending
+DMP_DEV void tile_chain_packed(f32x4 (&acc)[2][2], const uint16_t* in, const uint16_t* wp, int KS, int M, int m0, int n0, int l, int c, int g) {
+    const uint16_t* arow[2]; const uint16_t* bcol[2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+        const int row = m0 + 16 * i + c;
+        arow[i] = in + (size_t)(row < M ? row : 0) * (32 * KS) + 8 * g;
+        bcol[i] = wp + ((size_t)(n0 / 16 + i) * KS * 64 + l) * 8;
+    }
+    for (int ks = 0; ks < KS; ++ks) {
+        bf16x8 fa[2], fb[2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            fa[i] = *reinterpret_cast<const bf16x8*>(arow[i] + (size_t)ks * 32);
+            fb[i] = *reinterpret_cast<const bf16x8*>(bcol[i] + (size_t)ks * 512);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
+    }
+}
+
+// out = bf16(acc) . [h != 0] on the tile's rows below M: the ReLU mask from the saved activation h, h / out [M x ld]
+DMP_DEV void tile_store_masked(const f32x4 (&acc)[2][2], const uint16_t* h, uint16_t* out, int ld, int M, int m0, int n0, int c, int g) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int row = m0 + 16 * i + 4 * g + r, col = n0 + 16 * j + c;
+                if (row < M) {
+                    const size_t at = (size_t)row * ld + col;
+                    out[at] = (h[at] & 0x7fffu) ? bf16_rne(acc[i][j][r]) : (uint16_t)0;
+                }
+            }
+}
 
 // exp(x) with every rounding point written down (Cephes expf: k = rint(x log2 e), r = x - k ln 2 in two fmaf, a degree-5 polynomial in Horner form, ldexp), so that
 // device, emulator and the numpy mirror (deepmimic_amd/train.py reference_exp) agree bit for bit; within 2 ulp of exp.  NaN -> NaN, +inf -> +inf, -inf -> 0.
@@ -84,10 +141,7 @@ __global__ void __launch_bounds__(64) k_train_head(dmp::PolicyDev p, const uint1
     // ---- layer 3 (the MFMA chain of k_policy_layer<2, 1, 2>: per 16-column tile the k-steps ascending from a zero accumulator), z3 = acc + b3 into the workspace
     for (int cb = 0; cb < NB; ++cb) {
         f32x4 acc[2];
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[j][r] = 0.0f;
+        tile_zero(acc);
         for (int ks = 0; ks < KS; ++ks) {
             const bf16x8 af = *reinterpret_cast<const bf16x8*>(ap + (size_t)ks * 32);
 #pragma unroll
@@ -215,12 +269,7 @@ __global__ void __launch_bounds__(64) k_train_wgrad(WgradArgs a) {
     const int nbn = (a.N + 31) / 32, k0 = ((int)blockIdx.x / nbn) * 32, n0 = ((int)blockIdx.x % nbn) * 32;
     const int mr = l >> 1, hf = l & 1;           // staging: this lane moves the 16 columns 16 hf .. of block row mr
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
+    tile_zero(acc);
     bf16x8 zero;
 #pragma unroll
     for (int e = 0; e < 8; ++e) dmp::set8(zero, e, 0);
@@ -302,12 +351,7 @@ __global__ void __launch_bounds__(64) k_train_dgrad(typename DgradSel<INPUT>::ty
     const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
     const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, k0 = ((int)blockIdx.x / rbn) * 32;      // consecutive workgroups walk down the rows under one block of W
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
+    tile_zero(acc);
     const uint16_t* arow[2]; const float* wrow[2]; bool wlive[2] = {true, true};
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -350,29 +394,25 @@ __global__ void __launch_bounds__(64) k_train_dgrad(typename DgradSel<INPUT>::ty
             }
         return;
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + 16 * i + 4 * g + r, col = k0 + 16 * j + c;
-                if (row < a.M) {
-                    const size_t at = (size_t)row * a.H + col;
-                    a.out[at] = (a.h[at] & 0x7fffu) ? bf16_rne(acc[i][j][r]) : (uint16_t)0;
-                }
-            }
+    tile_store_masked(acc, a.h, a.out, a.H, a.M, m0, k0, c, g);
 }
 
-struct SgdArgs { float* w; float* v; const float* g; long long P, mat[3][2]; float lr, mom, wd, gs; unsigned blocks; };
+// NMAT: the matrix ranges [mat[k][0], mat[k][1]) of the block, the entries under the weight decay -- 3 for a plain net, GATED_MATRICES for a gated one, where
+// _weight_decay_loss (learning/tf_agent.py) drops only the variables whose name contains "bias", and actor/gate{i}/dense/kernel -- the beta projection -- is not one
+enum { GATED_ARRAYS = 20, GATED_MATRICES = 10 };
+template <int NMAT> struct SgdArgs { float* w; float* v; const float* g; long long P, mat[NMAT][2]; float lr, mom, wd, gs; unsigned blocks; };
 
-__global__ void __launch_bounds__(256) k_train_sgd(SgdArgs a) {
+template <int NMAT>
+__global__ void __launch_bounds__(256) k_train_sgd(SgdArgs<NMAT> a) {
     for (long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x; i < a.P; i += (long long)a.blocks * 256) {
         const float w = a.w[i];
         // g is carried in fp64, where every product of two floats is exact (a contraction changes nothing), and v is rounded ONCE: under cancellation between
         // momentum * v and g a chain of fp32 roundings would be off by many ulps of the small result
         double gg = (double)a.gs * (double)a.g[i];
-        const bool matrix = (i >= a.mat[0][0] && i < a.mat[0][1]) || (i >= a.mat[1][0] && i < a.mat[1][1]) || (i >= a.mat[2][0] && i < a.mat[2][1]);
+        // (The three ranges of a plain block are one spelled-out chain: written as the loop, the same test costs the plain kernel two SGPRs and a VGPR.)
+        bool matrix = false;
+        if constexpr (NMAT == 3) matrix = (i >= a.mat[0][0] && i < a.mat[0][1]) || (i >= a.mat[1][0] && i < a.mat[1][1]) || (i >= a.mat[2][0] && i < a.mat[2][1]);
+        else for (int k = 0; k < NMAT; ++k) matrix = matrix || (i >= a.mat[k][0] && i < a.mat[k][1]);
         if (matrix) gg += (double)a.wd * (double)w;          // _weight_decay_loss skips the biases
         const float vv = (float)((double)a.mom * (double)a.v[i] + gg);
         a.v[i] = vv;
@@ -480,43 +520,9 @@ __global__ void __launch_bounds__(64) k_train_fwdm(FwdmArgs a) {
     const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
     const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, n0 = ((int)blockIdx.x / rbn) * 32;      // consecutive workgroups walk down the rows under one block of W
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
-    const uint16_t* arow[2]; const uint16_t* bcol[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = m0 + 16 * i + c;
-        arow[i] = a.in + (size_t)(row < a.M ? row : 0) * (32 * a.KS) + 8 * g;
-        bcol[i] = a.wp + ((size_t)(n0 / 16 + i) * a.KS * 64 + l) * 8;
-    }
-    for (int ks = 0; ks < a.KS; ++ks) {
-        bf16x8 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            fa[i] = *reinterpret_cast<const bf16x8*>(arow[i] + (size_t)ks * 32);
-            fb[i] = *reinterpret_cast<const bf16x8*>(bcol[i] + (size_t)ks * 512);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
-    }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + 16 * i + 4 * g + r, col = n0 + 16 * j + c;
-                if (row < a.M) {
-                    const size_t at = (size_t)row * a.N + col;
-                    a.out[at] = (a.h[at] & 0x7fffu) ? bf16_rne(acc[i][j][r]) : (uint16_t)0;
-                }
-            }
+    tile_zero(acc);
+    tile_chain_packed(acc, a.in, a.wp, a.KS, a.M, m0, n0, l, c, g);
+    tile_store_masked(acc, a.h, a.out, a.N, a.M, m0, n0, c, g);
 }
 
 // the sums of squares of the masters in fp64: workgroup b takes the b-th contiguous chunk of the parameter block, thread t its elements t, t + 256, .. ascending, then the
@@ -593,52 +599,87 @@ static int train_net_ok(const char* fn, const dm_policy* p) {
     return 0;
 }
 
-// what every *_grad call (plain and gated) refuses alike in its common arguments; need(n): the bytes of the call's workspace, `sizer` the entry point that states them
-template <typename Need>
-static int train_args_ok(const dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, const float* grads,
-                         const double* stats, const void* ws, int64_t ws_bytes, Need need, const char* sizer) {
-    const dmp::PolicyDev& d = p->pd;
-    if (n < 1) return fail(std::string(fn) + ": n must be >= 1");
-    if (!params || !states || !grads || !stats || !ws) return fail(std::string(fn) + ": null argument");
-    if (check_goal(p, fn, "net", goals, goal_dim)) return -1;
-    if ((long long)n * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
-    if (ws_bytes < (int64_t)need(n)) return fail(std::string(fn) + ": workspace too small (" + sizer + ")");
+// the refusals every *_grad call takes from here, the discriminator's included.  train_rows_ok: the row count the kernels' int indices hold; train_ws_ok: the workspace
+// against `need`, the bytes of the call's carve, which `sizer` states, and the alignment of the workspace and the statistics
+static int train_rows_ok(const char* fn, const dmp::PolicyDev& d, long long n) {
+    if (n * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
+    return 0;
+}
+static int train_ws_ok(const char* fn, const double* stats, const void* ws, int64_t ws_bytes, size_t need, const char* sizer) {
+    if (ws_bytes < (int64_t)need) return fail(std::string(fn) + ": workspace too small (" + sizer + ")");
     if ((((uintptr_t)ws) & 15) != 0 || (((uintptr_t)stats) & 7) != 0) return fail(std::string(fn) + ": the workspace must be 16-byte and stats 8-byte aligned");
     return 0;
 }
 
-// what the two *_grad calls share behind their own checks: the forward pass on the context's per-layer kernels, the head, the fold and the backward pass
-static int train_grad(dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, dmt::HeadArgs& ha, float* grads,
-                      double* stats, void* ws, int64_t ws_bytes, void* hip_stream) {
+// what the actor and critic *_grad calls (plain and gated) refuse alike in their common arguments
+static int train_args_ok(const dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, const float* grads,
+                         const double* stats, const void* ws, int64_t ws_bytes, size_t need, const char* sizer) {
+    if (n < 1) return fail(std::string(fn) + ": n must be >= 1");
+    if (!params || !states || !grads || !stats || !ws) return fail(std::string(fn) + ": null argument");
+    if (check_goal(p, fn, "net", goals, goal_dim)) return -1;
+    return train_rows_ok(fn, p->pd, n) || train_ws_ok(fn, stats, ws, ws_bytes, need, sizer) ? -1 : 0;
+}
+
+// The forward pass of every *_grad call: k_policy_prep on n rows of `states` (null: the caller has filled s16 -- dm_train_disc_grad's two batches), a gated context's
+// k_policy_gate, then layers 1 and 2 on the context's own per-layer kernels -- the forced route, DM_POLICY_* is not read -- leaving s16 / h1 / h2 in bf16 as the sampling
+// net had them and, gated, sigma_i / beta_i in fp32 (gbuf)
+static void train_forward(dm_policy* p, const float* states, const float* goals, int goal_dim, int n, rt_stream stream) {
     const dmp::PolicyDev& d = p->pd;
-    if (train_args_ok(p, fn, params, states, goals, goal_dim, n, grads, stats, ws, ws_bytes, [&](int rows) { return dmt::carve(d, rows, nullptr).bytes; }, "dm_train_workspace_bytes")) return -1;
-    const dmt::Work w = dmt::carve(d, n, ws);
-    DevGuard guard(p->device_id);
-    rt_stream stream = (rt_stream)hip_stream;
-    if (policy_grow(p, n, stream)) return -1;
     dmp::PolicyIO io; memset(&io, 0, sizeof(io));
     io.states = states; io.M = n; io.goals = goal_dim ? goals : nullptr; io.G = goal_dim; io.exp_rate = 1.0f;
     io.s16 = p->s16; io.h1 = p->h1; io.h2 = p->h2;
-    // the per-layer route as policy_path chooses it for the widths, whatever DM_POLICY_* says
-    const int path = DM_POLICY_PATH_LAYERED(d.H1 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE, d.H2 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE);
-    RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
-    launch_layers<false>(path, n, stream, d, io);
+    if (p->gated) { io.gsig0 = p->gbuf[0]; io.gbeta0 = p->gbuf[1]; io.gsig1 = p->gbuf[2]; io.gbeta1 = p->gbuf[3]; io.gate = p->gd_dev; }
+    if (states) RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
+    if (!p->gated) return launch_layers<false>(policy_path_layered(d), n, stream, d, io);
+    RT_LAUNCH4(dmp::k_policy_gate, (n + 31) / 32, stream, d, io, p->gd);
+    launch_layers<true>(policy_path_layered(d), n, stream, d, io);
+}
+
+// k_train_head and k_train_fold of an actor or critic call, on the h2 the forward left
+static void train_head(const dm_policy* p, int n, dmt::HeadArgs& ha, const dmt::Work& w, double* stats, rt_stream stream) {
     const int groups = (n + 15) / 16;
     ha.M = n; ha.nf = (float)n; ha.z3 = w.z3; ha.dz3 = w.dz3; ha.part = w.part;
-    RT_LAUNCH(dmt::k_train_head, groups, stream, d, (const uint16_t*)p->h2, ha);
+    RT_LAUNCH(dmt::k_train_head, groups, stream, p->pd, (const uint16_t*)p->h2, ha);
     RT_LAUNCH4(dmt::k_train_fold, 1, stream, (const double*)w.part, groups, ha.kind, n, stats);
-    const dmt::Layout L = dmt::layout_of(d);
-    const uint16_t* in[3] = {p->s16, p->h1, p->h2}; const int ldin[3] = {d.K1, d.H1, d.H2}, K[3] = {d.S, d.H1, d.H2};
-    uint16_t* dz[3] = {w.dz1, w.dz2, w.dz3}; const int lddz[3] = {d.H1, d.H2, d.N3}, N[3] = {d.H1, d.H2, d.A};
-    for (int layer = 2; layer >= 0; --layer) {
-        dmt::WgradArgs wa; wa.in = in[layer]; wa.ldin = ldin[layer]; wa.K = K[layer]; wa.dz = dz[layer]; wa.lddz = lddz[layer]; wa.N = N[layer]; wa.M = n; wa.dW = grads + L.o[2 * layer];
-        RT_LAUNCH(dmt::k_train_wgrad<false>, ((K[layer] + 31) / 32) * ((N[layer] + 31) / 32), stream, wa);
-        RT_LAUNCH4(dmt::k_train_bgrad<false>, (N[layer] + 63) / 64, stream, (const uint16_t*)dz[layer], lddz[layer], N[layer], n, grads + L.o[2 * layer + 1], (const float*)nullptr, 0.0f);
-        if (layer > 0) {
-            dmt::DgradArgs da; da.dz = dz[layer]; da.lddz = lddz[layer]; da.W = params + L.o[2 * layer]; da.ldw = N[layer]; da.h = in[layer]; da.H = K[layer]; da.M = n; da.out = dz[layer - 1];
-            RT_LAUNCH(dmt::k_train_dgrad<false>, ((n + 31) / 32) * (K[layer] / 32), stream, da);
+}
+
+// The backward launches of a *_grad call over n rows: masters read from `params` and gradients written into `grads` at offsets (in floats) of the call's layout
+struct TrainBackward {
+    rt_stream stream; int n; const float* params; float* grads;
+    // dW [K x N] = in^T dz at offset ow, and db = the column sums of dz at offset ob
+    void wgrad_bgrad(const uint16_t* in, int ldin, int K, const uint16_t* dz, int lddz, int N, long long ow, long long ob) const {
+        dmt::WgradArgs wa; wa.in = in; wa.ldin = ldin; wa.K = K; wa.dz = dz; wa.lddz = lddz; wa.N = N; wa.M = n; wa.dW = grads + ow;
+        RT_LAUNCH(dmt::k_train_wgrad<false>, ((K + 31) / 32) * ((N + 31) / 32), stream, wa);
+        RT_LAUNCH4(dmt::k_train_bgrad<false>, (N + 63) / 64, stream, dz, lddz, N, n, grads + ob, (const float*)nullptr, 0.0f);
+    }
+    // out [n x H] = bf16((dz W^T) . [h != 0]) with W [H x ldw] the master at offset ow
+    void dgrad(const uint16_t* dz, int lddz, long long ow, int ldw, const uint16_t* h, int H, uint16_t* out) const {
+        dmt::DgradArgs da; da.dz = dz; da.lddz = lddz; da.W = params + ow; da.ldw = ldw; da.h = h; da.H = H; da.M = n; da.out = out;
+        RT_LAUNCH(dmt::k_train_dgrad<false>, ((n + 31) / 32) * (H / 32), stream, da);
+    }
+    // the plain three-layer net from the dz3 in the workspace, layer 3 first
+    void plain_backward(const dm_policy* p, const dmt::Work& w, const dmt::Layout& L) const {
+        const dmp::PolicyDev& d = p->pd;
+        const uint16_t* in[3] = {p->s16, p->h1, p->h2}; const int ldin[3] = {d.K1, d.H1, d.H2}, K[3] = {d.S, d.H1, d.H2};
+        uint16_t* dz[3] = {w.dz1, w.dz2, w.dz3}; const int lddz[3] = {d.H1, d.H2, d.N3}, N[3] = {d.H1, d.H2, d.A};
+        for (int layer = 2; layer >= 0; --layer) {
+            wgrad_bgrad(in[layer], ldin[layer], K[layer], dz[layer], lddz[layer], N[layer], L.o[2 * layer], L.o[2 * layer + 1]);
+            if (layer > 0) dgrad(dz[layer], lddz[layer], L.o[2 * layer], N[layer], in[layer], K[layer], dz[layer - 1]);
         }
     }
+};
+
+// what the two *_grad calls share behind their own checks: the forward pass, the head, the fold and the backward pass
+static int train_grad(dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, dmt::HeadArgs& ha, float* grads,
+                      double* stats, void* ws, int64_t ws_bytes, void* hip_stream) {
+    const dmt::Work w = dmt::carve(p->pd, n, ws);
+    if (train_args_ok(p, fn, params, states, goals, goal_dim, n, grads, stats, ws, ws_bytes, w.bytes, "dm_train_workspace_bytes")) return -1;
+    DevGuard guard(p->device_id);
+    rt_stream stream = (rt_stream)hip_stream;
+    if (policy_grow(p, n, stream)) return -1;
+    train_forward(p, states, goals, goal_dim, n, stream);
+    train_head(p, n, ha, w, stats, stream);
+    TrainBackward{stream, n, params, grads}.plain_backward(p, w, dmt::layout_of(p->pd));
     return launch_status(0);
 }
 
@@ -682,6 +723,50 @@ static int train_step_ok(const char* fn, const float* params_dev, const float* m
     return 0;
 }
 
+// What the plain and the gated step share behind their checks.  o: the offsets of the block's 2 NMAT arrays (a layout's o: array 2 k a matrix, under the weight decay,
+// 2 k + 1 its bias vector); null with no context: no matrix, the step alone.  k_train_sgd<NMAT>, then the new masters into the context -- dm_policy_set_weights with
+// DM_DEVICE_PTRS on views of params, the gate's arrays included: "packed weights = RNE bf16 of the masters" stays true for every array
+template <int NMAT>
+static int train_sgd(dm_policy* net, const long long* o, float* params, float* momentum_dev, const float* grads, int64_t P, double stepsize, double momentum,
+                     double weight_decay, double grad_scale, void* hip_stream) {
+    dmt::SgdArgs<NMAT> a; memset(&a, 0, sizeof(a));
+    if (o) for (int k = 0; k < NMAT; ++k) { a.mat[k][0] = o[2 * k]; a.mat[k][1] = o[2 * k + 1]; }
+    a.w = params; a.v = momentum_dev; a.g = grads; a.P = P; a.lr = (float)stepsize; a.mom = (float)momentum; a.wd = (float)weight_decay; a.gs = (float)grad_scale;
+    a.blocks = (unsigned)std::min<int64_t>((P + 255) / 256, 4096);
+    rt_stream stream = (rt_stream)hip_stream;
+    if (!net) {                                   // no context: on the calling thread's current device
+        RT_LAUNCH4(dmt::k_train_sgd<NMAT>, a.blocks, stream, a);
+        return launch_status(0);
+    }
+    DevGuard guard(net->device_id);
+    RT_LAUNCH4(dmt::k_train_sgd<NMAT>, a.blocks, stream, a);
+    if (launch_status(0)) return -1;
+    const dmp::PolicyDev& d = net->pd;
+    dm_policy_params pp; memset(&pp, 0, sizeof(pp));
+    pp.state_dim = d.S; pp.hidden1 = d.H1; pp.hidden2 = d.H2; pp.action_dim = d.A;
+    dm_policy_gate_params gp; memset(&gp, 0, sizeof(gp));
+    if (net->gated) { gp.goal_dim = net->gd.G; gp.gate_common = net->gd.GC; gp.gate_hidden = net->gd.GH; }
+    const float** const arr[dmt::GATED_ARRAYS] = {&pp.w1, &pp.b1, &pp.w2, &pp.b2, &pp.w3, &pp.b3, &gp.gc_w, &gp.gc_b, &gp.g0_w, &gp.g0_b, &gp.g0_bias_w, &gp.g0_bias_b, &gp.g0_scale_w, &gp.g0_scale_b,
+                                                  &gp.g1_w, &gp.g1_b, &gp.g1_bias_w, &gp.g1_bias_b, &gp.g1_scale_w, &gp.g1_scale_b};
+    for (int k = 0; k < 2 * NMAT; ++k) *arr[k] = params + o[k];
+    return policy_pack(net, pp, net->gated ? &gp : nullptr, DM_DEVICE_PTRS, stream);
+}
+
+// what dm_train_read_activations and dm_train_gated_read share behind the check of the net: array `which` of `count` = {source, bytes per row}; `names`: what `which` may be
+struct TrainReadRow { const void* src; size_t row_bytes; };
+static int train_read(const char* fn, dm_policy* net, const TrainReadRow* table, int count, const char* names, int which, int n, void* host_out, size_t capacity) {
+    if (!host_out) return fail(std::string(fn) + ": null argument");
+    if (which < 0 || which >= count) return fail(std::string(fn) + ": which must be " + names);
+    if (n < 1 || n > net->cap) return fail(std::string(fn) + ": n must be in [1, rows the context holds]");
+    const size_t bytes = (size_t)n * table[which].row_bytes;
+    if (capacity < bytes) return fail(std::string(fn) + ": the host buffer is smaller than the array (" + std::to_string(bytes) + " bytes)");
+    DevGuard guard(net->device_id);
+#ifndef DM_EMU
+    if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
+#endif
+    return rt_d2h(host_out, table[which].src, bytes, 0) == 0 ? 0 : fail("device to host copy failed");
+}
+
 extern "C" {
 
 int64_t dm_train_param_count(const dm_policy* net) {
@@ -719,9 +804,7 @@ static int train_disc_ok(const char* fn, const dm_policy* net, int n_expert, int
     if (train_net_ok(fn, net)) return -1;
     if (net->pd.A != 1) return fail(std::string(fn) + ": the context has action_dim " + std::to_string(net->pd.A) + ", the discriminator is a net with one output");
     if (n_expert < 1 || n_agent < 1) return fail(std::string(fn) + ": n_expert and n_agent must be >= 1");
-    const dmp::PolicyDev& d = net->pd;
-    if (((long long)n_expert + (long long)n_agent) * std::max(std::max(d.K1, d.H1), d.H2) > 0x7fffffffLL) return fail(std::string(fn) + ": too many rows for one call");
-    return 0;
+    return train_rows_ok(fn, net->pd, (long long)n_expert + (long long)n_agent);
 }
 
 int64_t dm_train_disc_workspace_bytes(const dm_policy* net, int n_expert, int n_agent) {
@@ -740,46 +823,32 @@ int dm_train_disc_grad(dm_policy* net, const float* params_dev, const float* exp
     const dmp::PolicyDev& d = p->pd;
     const int ne = n_expert, na = n_agent, n = ne + na;
     const dmt::DiscWork k = dmt::carve_disc(d, ne, na, workspace);
-    if (workspace_bytes < (int64_t)k.bytes) return fail(std::string(fn) + ": workspace too small (dm_train_disc_workspace_bytes)");
-    if ((((uintptr_t)workspace) & 15) != 0 || (((uintptr_t)stats_dev) & 7) != 0) return fail(std::string(fn) + ": the workspace must be 16-byte and stats 8-byte aligned");
+    if (train_ws_ok(fn, stats_dev, workspace, workspace_bytes, k.bytes, "dm_train_disc_workspace_bytes")) return -1;
     DevGuard guard(p->device_id);
     rt_stream stream = (rt_stream)hip_stream;
     if (policy_grow(p, n, stream)) return -1;
     const bool penalty = cfg->grad_penalty > 0.0;
     const float c_lr = (float)cfg->logit_reg;
-    // ---- forward: the two batches into one s16 (expert rows first), then the context's per-layer kernels as train_grad chooses them
+    // ---- forward: the two batches into one s16 (expert rows first), then the layers over all rows
     dmp::PolicyIO io; memset(&io, 0, sizeof(io));
     io.exp_rate = 1.0f; io.h1 = p->h1; io.h2 = p->h2;
     io.states = expert_obs_dev; io.M = ne; io.s16 = p->s16;
     RT_LAUNCH(dmp::k_policy_prep, ne, stream, d, io);
     io.states = agent_obs_dev; io.M = na; io.s16 = p->s16 + (size_t)ne * d.K1;
     RT_LAUNCH(dmp::k_policy_prep, na, stream, d, io);
-    io.states = nullptr; io.M = n; io.s16 = p->s16;
-    const int path = DM_POLICY_PATH_LAYERED(d.H1 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE, d.H2 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE);
-    launch_layers<false>(path, n, stream, d, io);
+    train_forward(p, nullptr, nullptr, 0, n, stream);
     const dmt::Layout L = dmt::layout_of(d);
     const int groups = (n + 15) / 16;
     dmt::DiscHeadArgs ha; memset(&ha, 0, sizeof(ha));
     ha.M = n; ha.ne = ne; ha.nef = (float)ne; ha.naf = (float)na; ha.penalty = penalty ? 1 : 0; ha.w3 = params_dev + L.o[4];
     ha.z3 = k.w.z3; ha.dz3 = k.w.dz3; ha.g2 = k.g2; ha.part = k.w.part; ha.out = logits_out;
     RT_LAUNCH(dmt::k_train_disc_head, groups, stream, d, (const uint16_t*)p->h2, ha);
-    // ---- the least-squares backward pass over all rows (train_grad's), layer 3 first
-    const uint16_t* in[3] = {p->s16, p->h1, p->h2}; const int ldin[3] = {d.K1, d.H1, d.H2}, K[3] = {d.S, d.H1, d.H2};
-    uint16_t* dz[3] = {k.w.dz1, k.w.dz2, k.w.dz3}; const int lddz[3] = {d.H1, d.H2, d.N3}, N[3] = {d.H1, d.H2, d.A};
-    for (int layer = 2; layer >= 0; --layer) {
-        dmt::WgradArgs wa; wa.in = in[layer]; wa.ldin = ldin[layer]; wa.K = K[layer]; wa.dz = dz[layer]; wa.lddz = lddz[layer]; wa.N = N[layer]; wa.M = n; wa.dW = grads_dev + L.o[2 * layer];
-        RT_LAUNCH(dmt::k_train_wgrad<false>, ((K[layer] + 31) / 32) * ((N[layer] + 31) / 32), stream, wa);
-        RT_LAUNCH4(dmt::k_train_bgrad<false>, (N[layer] + 63) / 64, stream, (const uint16_t*)dz[layer], lddz[layer], N[layer], n, grads_dev + L.o[2 * layer + 1], (const float*)nullptr, 0.0f);
-        if (layer > 0) {
-            dmt::DgradArgs da; da.dz = dz[layer]; da.lddz = lddz[layer]; da.W = params_dev + L.o[2 * layer]; da.ldw = N[layer]; da.h = in[layer]; da.H = K[layer]; da.M = n; da.out = dz[layer - 1];
-            RT_LAUNCH(dmt::k_train_dgrad<false>, ((n + 31) / 32) * (K[layer] / 32), stream, da);
-        }
-    }
+    // ---- the least-squares backward pass over all rows
+    TrainBackward{stream, n, params_dev, grads_dev}.plain_backward(p, k.w, L);
     // ---- the penalty, expert rows only
     const int rb = (ne + 31) / 32;
     if (penalty) {
-        dmt::DgradArgs d2; d2.dz = k.g2; d2.lddz = d.H2; d2.W = params_dev + L.o[2]; d2.ldw = d.H2; d2.h = p->h1; d2.H = d.H1; d2.M = ne; d2.out = k.g1;
-        RT_LAUNCH(dmt::k_train_dgrad<false>, rb * (d.H1 / 32), stream, d2);
+        TrainBackward{stream, ne, params_dev, grads_dev}.dgrad(k.g2, d.H2, L.o[2], d.H2, p->h1, d.H1, k.g1);
         dmt::DgradInArgs d1; d1.dz = k.g1; d1.lddz = d.H1; d1.W = params_dev + L.o[0]; d1.ldw = d.H1; d1.h = nullptr; d1.H = d.K1; d1.M = ne; d1.out = k.a;
         d1.S = d.S; d1.scale = (float)cfg->grad_penalty / (float)ne; d1.sq = k.sq;
         RT_LAUNCH(dmt::k_train_dgrad<true>, rb * (d.K1 / 32), stream, d1);
@@ -808,45 +877,20 @@ int dm_train_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, co
     const char* fn = "dm_train_sgd_step";
     if (net && train_net_ok(fn, net)) return -1;
     if (train_step_ok(fn, params_dev, momentum_dev, grads_dev, P, stepsize, momentum, weight_decay, grad_scale)) return -1;
-    dmt::SgdArgs a; memset(&a, 0, sizeof(a));
     dmt::Layout L; memset(&L, 0, sizeof(L));
     if (net) {
         L = dmt::layout_of(net->pd);
         if (P != L.P) return fail(std::string(fn) + ": P is " + std::to_string((long long)P) + ", the net has " + std::to_string(L.P) + " parameters (dm_train_param_count)");
-        for (int k = 0; k < 3; ++k) { a.mat[k][0] = L.o[2 * k]; a.mat[k][1] = L.o[2 * k + 1]; }
     } else if (weight_decay != 0.0) return fail(std::string(fn) + ": weight_decay needs the net (which entries are matrices is its layout)");
-    a.w = params_dev; a.v = momentum_dev; a.g = grads_dev; a.P = P; a.lr = (float)stepsize; a.mom = (float)momentum; a.wd = (float)weight_decay; a.gs = (float)grad_scale;
-    a.blocks = (unsigned)std::min<int64_t>((P + 255) / 256, 4096);
-    rt_stream stream = (rt_stream)hip_stream;
-    if (!net) {                                   // no context: the step alone, on the calling thread's current device
-        RT_LAUNCH4(dmt::k_train_sgd, a.blocks, stream, a);
-        return launch_status(0);
-    }
-    DevGuard guard(net->device_id);
-    RT_LAUNCH4(dmt::k_train_sgd, a.blocks, stream, a);
-    if (launch_status(0)) return -1;
-    // the new masters into the context: dm_policy_set_weights with DM_DEVICE_PTRS on views of params_dev
-    const dmp::PolicyDev& d = net->pd;
-    dm_policy_params pp; memset(&pp, 0, sizeof(pp));
-    pp.state_dim = d.S; pp.hidden1 = d.H1; pp.hidden2 = d.H2; pp.action_dim = d.A;
-    pp.w1 = params_dev + L.o[0]; pp.b1 = params_dev + L.o[1]; pp.w2 = params_dev + L.o[2]; pp.b2 = params_dev + L.o[3]; pp.w3 = params_dev + L.o[4]; pp.b3 = params_dev + L.o[5];
-    return policy_pack(net, pp, nullptr, DM_DEVICE_PTRS, stream);
+    return train_sgd<3>(net, net ? L.o : nullptr, params_dev, momentum_dev, grads_dev, P, stepsize, momentum, weight_decay, grad_scale, hip_stream);
 }
 
 int dm_train_read_activations(dm_policy* net, int which, int n, void* host_out, size_t capacity) {
     const char* fn = "dm_train_read_activations";
     if (train_net_ok(fn, net)) return -1;
-    if (!host_out) return fail(std::string(fn) + ": null argument");
-    if (which < 0 || which > 2) return fail(std::string(fn) + ": which must be 0 (s16), 1 (h1) or 2 (h2)");
-    if (n < 1 || n > net->cap) return fail(std::string(fn) + ": n must be in [1, rows the context holds]");
     const dmp::PolicyDev& d = net->pd;
-    const size_t bytes = (size_t)n * (which == 0 ? d.K1 : (which == 1 ? d.H1 : d.H2)) * 2;
-    if (capacity < bytes) return fail(std::string(fn) + ": the host buffer is smaller than the array (" + std::to_string(bytes) + " bytes)");
-    DevGuard guard(net->device_id);
-#ifndef DM_EMU
-    if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
-#endif
-    return rt_d2h(host_out, which == 0 ? net->s16 : (which == 1 ? net->h1 : net->h2), bytes, 0) == 0 ? 0 : fail("device to host copy failed");
+    const TrainReadRow table[3] = {{net->s16, (size_t)d.K1 * 2}, {net->h1, (size_t)d.H1 * 2}, {net->h2, (size_t)d.H2 * 2}};
+    return train_read(fn, net, table, 3, "0 (s16), 1 (h1) or 2 (h2)", which, n, host_out, capacity);
 }
 
 }  // extern "C"

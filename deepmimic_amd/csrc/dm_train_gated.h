@@ -1,6 +1,7 @@
 // The PPO actor and critic minibatch updates for the GATED nets of the AMP task agents (include/dm_hip.h dm_train_gated_*, deepmimic_amd/train.py GatedActorTrainer /
 // GatedCriticTrainer): fc_2layers_gated_1024units as "ActorNet" and "CriticNet" of ct_agent_humanoid_amp_tasks*.txt, trained on the context that samples.  Included at the
-// end of dm_host.cpp behind dm_train.h, whose head, fold, wgrad / bgrad / dgrad kernels and checks it uses unchanged; in no step-kernel translation unit.
+// end of dm_host.cpp behind dm_train.h, whose head, fold, wgrad / bgrad / dgrad and step kernels, tile toolkit, checks, forward (train_forward), backward launcher
+// (TrainBackward), step (train_sgd<GATED_MATRICES>) and read (train_read) it uses unchanged; in no step-kernel translation unit.
 //
 // Notation (dm_policy.h GateDev; i = 0: layer 1, width H1, i = 1: layer 2, width H2): c = relu(Wc xg + bc), e_i = relu(We_i c + be_i), beta_i = Wb_i e_i + bb_i,
 // sigma_i = 2 sigmoid(Ws_i e_i + bs_i), u_i = W_i h_(i-1) + b_i, p_i = fmaf(sigma_i, u_i, beta_i), h_i = bf16(relu(p_i)).
@@ -51,38 +52,15 @@ __global__ void __launch_bounds__(256) k_train_gate_hidden(dmp::PolicyDev p, con
 struct SplitArgs { const uint16_t* in; const uint16_t* wp; int KS; const float* bias; const float* sig; const uint16_t* dp; int N, M; uint16_t *du, *da; };
 
 // The gate split of one hidden layer: p = fmaf(sigma, u, beta) sends dp to u (du = dp sigma), to beta (dp itself) and to sigma's pre-activation z (da = dp u dsigma/dz,
-// dsigma/dz = sigma (1 - sigma / 2) for sigma = 2 sigmoid(z)).  u is not stored by the forward: acc is recomputed by the chain of k_train_fwdm (the packed B fragments,
+// dsigma/dz = sigma (1 - sigma / 2) for sigma = 2 sigmoid(z)).  u is not stored by the forward: acc is recomputed by tile_chain_packed, the chain of k_train_fwdm (the packed B fragments,
 // k-steps ascending from a zero accumulator: the chain of k_policy_layer / k_policy_gemm), so u = acc + b has the bits the forward had.  Per element in fp32, one rounding
 // per written operation; the ReLU mask is already inside dp; sigma = 0 and sigma = 2 give da = 0 (times dp u); a NaN propagates.  A wavefront owns 32 rows x 32 columns.
 __global__ void __launch_bounds__(64) k_train_gate_split(SplitArgs a) {
     const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
     const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, n0 = ((int)blockIdx.x / rbn) * 32;      // consecutive workgroups walk down the rows under one block of W
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
-    const uint16_t* arow[2]; const uint16_t* bcol[2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const int row = m0 + 16 * i + c;
-        arow[i] = a.in + (size_t)(row < a.M ? row : 0) * (32 * a.KS) + 8 * g;
-        bcol[i] = a.wp + ((size_t)(n0 / 16 + i) * a.KS * 64 + l) * 8;
-    }
-    for (int ks = 0; ks < a.KS; ++ks) {
-        bf16x8 fa[2], fb[2];
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            fa[i] = *reinterpret_cast<const bf16x8*>(arow[i] + (size_t)ks * 32);
-            fb[i] = *reinterpret_cast<const bf16x8*>(bcol[i] + (size_t)ks * 512);
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i)
-#pragma unroll
-            for (int j = 0; j < 2; ++j) acc[i][j] = mfma16(fa[i], fb[j], acc[i][j]);
-    }
+    tile_zero(acc);
+    tile_chain_packed(acc, a.in, a.wp, a.KS, a.M, m0, n0, l, c, g);
 #pragma unroll
     for (int j = 0; j < 2; ++j) {
         const int col = n0 + 16 * j + c; const float b = a.bias[col];
@@ -111,12 +89,7 @@ __global__ void __launch_bounds__(64) k_train_dgrad2(Dgrad2Args a) {
     const int l = (int)threadIdx.x, c = l & 15, g = l >> 4;
     const int rbn = (a.M + 31) / 32, m0 = ((int)blockIdx.x % rbn) * 32, k0 = ((int)blockIdx.x / rbn) * 32;
     f32x4 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) acc[i][j][r] = 0.0f;
+    tile_zero(acc);
     for (int p = 0; p < 2; ++p) {
         const uint16_t* arow[2]; const float* wrow[2];
 #pragma unroll
@@ -156,40 +129,10 @@ __global__ void __launch_bounds__(64) k_train_dgrad2(Dgrad2Args a) {
             }
         }
     }
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = m0 + 16 * i + 4 * g + r, col = k0 + 16 * j + c;
-                if (row < a.M) {
-                    const size_t at = (size_t)row * a.H + col;
-                    a.out[at] = (a.h[at] & 0x7fffu) ? bf16_rne(acc[i][j][r]) : (uint16_t)0;
-                }
-            }
+    tile_store_masked(acc, a.h, a.out, a.H, a.M, m0, k0, c, g);
 }
 
-enum { GATED_ARRAYS = 20, GATED_MATRICES = 10 };
-
-struct GatedSgdArgs { float* w; float* v; const float* g; long long P, mat[GATED_MATRICES][2]; float lr, mom, wd, gs; unsigned blocks; };
-
-// k_train_sgd's step per element, with the ten matrices of the gated net under the weight decay: _weight_decay_loss (learning/tf_agent.py) drops only the variables whose
-// name contains "bias", and actor/gate{i}/dense/kernel -- the beta projection -- is not one
-__global__ void __launch_bounds__(256) k_train_gated_sgd(GatedSgdArgs a) {
-    for (long long i = (long long)blockIdx.x * 256 + (long long)threadIdx.x; i < a.P; i += (long long)a.blocks * 256) {
-        const float w = a.w[i];
-        double gg = (double)a.gs * (double)a.g[i];
-        bool matrix = false;
-        for (int k = 0; k < GATED_MATRICES; ++k) matrix = matrix || (i >= a.mat[k][0] && i < a.mat[k][1]);
-        if (matrix) gg += (double)a.wd * (double)w;
-        const float vv = (float)((double)a.mom * (double)a.v[i] + gg);
-        a.v[i] = vv;
-        a.w[i] = fmaf(-a.lr, vv, w);
-    }
-}
-
-// offsets (in floats) of the 20 arrays of a gated parameter block -- the six of Layout, then the gate's in the order of dm_policy_gate_params -- and its length;
+// offsets (in floats) of the GATED_ARRAYS = 20 arrays of a gated parameter block -- the six of Layout, then the gate's in the order of dm_policy_gate_params -- and its length;
 // array 2 k is a matrix, 2 k + 1 its bias vector
 struct GatedLayout { long long o[GATED_ARRAYS], P; };
 inline GatedLayout gated_layout_of(const dmp::PolicyDev& d, const dmp::GateDev& q) {
@@ -226,63 +169,44 @@ static int train_gated_ok(const char* fn, const dm_policy* p) {
 static int train_gated_grad(dm_policy* p, const char* fn, const float* params, const float* states, const float* goals, int goal_dim, int n, dmt::HeadArgs& ha, float* grads,
                             double* stats, void* ws, int64_t ws_bytes, void* hip_stream) {
     const dmp::PolicyDev& d = p->pd; const dmp::GateDev& q = p->gd;
-    if (train_args_ok(p, fn, params, states, goals, goal_dim, n, grads, stats, ws, ws_bytes, [&](int rows) { return dmt::carve_gated(d, q, rows, nullptr).bytes; },
-                      "dm_train_gated_workspace_bytes")) return -1;
     const dmt::GatedWork k = dmt::carve_gated(d, q, n, ws);
+    if (train_args_ok(p, fn, params, states, goals, goal_dim, n, grads, stats, ws, ws_bytes, k.bytes, "dm_train_gated_workspace_bytes")) return -1;
     DevGuard guard(p->device_id);
     rt_stream stream = (rt_stream)hip_stream;
     if (policy_grow(p, n, stream)) return -1;
-    // ---- forward: the per-layer gated route of policy_run, as policy_path chooses it for the widths, whatever DM_POLICY_* says
-    dmp::PolicyIO io; memset(&io, 0, sizeof(io));
-    io.states = states; io.M = n; io.goals = goal_dim ? goals : nullptr; io.G = goal_dim; io.exp_rate = 1.0f;
-    io.s16 = p->s16; io.h1 = p->h1; io.h2 = p->h2;
-    io.gsig0 = p->gbuf[0]; io.gbeta0 = p->gbuf[1]; io.gsig1 = p->gbuf[2]; io.gbeta1 = p->gbuf[3]; io.gate = p->gd_dev;
-    const int path = DM_POLICY_PATH_LAYERED(d.H1 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE, d.H2 % 128 == 0 ? DM_POLICY_LAYER_TILE64 : DM_POLICY_LAYER_ONE_WAVE);
-    RT_LAUNCH(dmp::k_policy_prep, n, stream, d, io);
-    RT_LAUNCH4(dmp::k_policy_gate, (n + 31) / 32, stream, d, io, q);
-    launch_layers<true>(path, n, stream, d, io);
-    RT_LAUNCH4(dmt::k_train_gate_hidden, (n + 31) / 32, stream, d, (const uint16_t*)p->s16, n, q, k.xg, k.c, k.e[0], k.e[1]);
-    const int groups = (n + 15) / 16, rb = (n + 31) / 32;
-    ha.M = n; ha.nf = (float)n; ha.z3 = k.w.z3; ha.dz3 = k.w.dz3; ha.part = k.w.part;
-    RT_LAUNCH(dmt::k_train_head, groups, stream, d, (const uint16_t*)p->h2, ha);
-    RT_LAUNCH4(dmt::k_train_fold, 1, stream, (const double*)k.w.part, groups, ha.kind, n, stats);
-    // ---- backward
+    train_forward(p, states, goals, goal_dim, n, stream);
+    const int rb = (n + 31) / 32;
+    RT_LAUNCH4(dmt::k_train_gate_hidden, rb, stream, d, (const uint16_t*)p->s16, n, q, k.xg, k.c, k.e[0], k.e[1]);
+    train_head(p, n, ha, k.w, stats, stream);
+    // ---- backward; o[a]: the offset of array `a` of the block (GatedLayout: a matrix and, behind it, its bias vector)
     const dmt::GatedLayout L = dmt::gated_layout_of(d, q);
-    // dW = in^T dz into array `arr` of the block and the column sums of dz into array arr + 1
-    auto wgrad_bgrad = [&](const uint16_t* in, int ldin, int K, const uint16_t* dz, int lddz, int N, int arr) {
-        dmt::WgradArgs wa; wa.in = in; wa.ldin = ldin; wa.K = K; wa.dz = dz; wa.lddz = lddz; wa.N = N; wa.M = n; wa.dW = grads + L.o[arr];
-        RT_LAUNCH(dmt::k_train_wgrad<false>, ((K + 31) / 32) * ((N + 31) / 32), stream, wa);
-        RT_LAUNCH4(dmt::k_train_bgrad<false>, (N + 63) / 64, stream, dz, lddz, N, n, grads + L.o[arr + 1], (const float*)nullptr, 0.0f);
-    };
-    auto dgrad = [&](const uint16_t* dz, int lddz, int arr, int ldw, const uint16_t* h, int H, uint16_t* out) {
-        dmt::DgradArgs da; da.dz = dz; da.lddz = lddz; da.W = params + L.o[arr]; da.ldw = ldw; da.h = h; da.H = H; da.M = n; da.out = out;
-        RT_LAUNCH(dmt::k_train_dgrad<false>, rb * (H / 32), stream, da);
-    };
+    const long long* const o = L.o;
+    const TrainBackward bw{stream, n, params, grads};
     auto split = [&](const uint16_t* in, const uint16_t* wp, int K, const float* bias, const float* sig, int N, int i) {
         dmt::SplitArgs sa; sa.in = in; sa.wp = wp; sa.KS = K / 32; sa.bias = bias; sa.sig = sig; sa.dp = i ? k.w.dz2 : k.w.dz1; sa.N = N; sa.M = n; sa.du = k.du[i]; sa.da = k.da[i];
         RT_LAUNCH(dmt::k_train_gate_split, rb * (N / 32), stream, sa);
     };
     auto dgrad2 = [&](const uint16_t* dz0, int arr0, const uint16_t* dz1, int arr1, int ld, const uint16_t* h, int H, uint16_t* out) {
-        dmt::Dgrad2Args da; da.dz[0] = dz0; da.dz[1] = dz1; da.W[0] = params + L.o[arr0]; da.W[1] = params + L.o[arr1]; da.ld = ld; da.h = h; da.H = H; da.M = n; da.out = out;
+        dmt::Dgrad2Args da; da.dz[0] = dz0; da.dz[1] = dz1; da.W[0] = params + o[arr0]; da.W[1] = params + o[arr1]; da.ld = ld; da.h = h; da.H = H; da.M = n; da.out = out;
         RT_LAUNCH(dmt::k_train_dgrad2, rb * (H / 32), stream, da);
     };
-    wgrad_bgrad(p->h2, d.H2, d.H2, k.w.dz3, d.N3, d.A, 4);
-    dgrad(k.w.dz3, d.N3, 4, d.A, p->h2, d.H2, k.w.dz2);                               // dp_1
+    bw.wgrad_bgrad(p->h2, d.H2, d.H2, k.w.dz3, d.N3, d.A, o[4], o[5]);
+    bw.dgrad(k.w.dz3, d.N3, o[4], d.A, p->h2, d.H2, k.w.dz2);                         // dp_1
     split(p->h1, d.w2p, d.H1, d.b2, p->gbuf[2], d.H2, 1);
-    wgrad_bgrad(p->h1, d.H1, d.H1, k.du[1], d.H2, d.H2, 2);
-    dgrad(k.du[1], d.H2, 2, d.H2, p->h1, d.H1, k.w.dz1);                              // dp_0
+    bw.wgrad_bgrad(p->h1, d.H1, d.H1, k.du[1], d.H2, d.H2, o[2], o[3]);
+    bw.dgrad(k.du[1], d.H2, o[2], d.H2, p->h1, d.H1, k.w.dz1);                        // dp_0
     split(p->s16, d.w1p, d.K1, d.b1, p->gbuf[0], d.H1, 0);
-    wgrad_bgrad(p->s16, d.K1, d.S, k.du[0], d.H1, d.H1, 0);
+    bw.wgrad_bgrad(p->s16, d.K1, d.S, k.du[0], d.H1, d.H1, o[0], o[1]);
     for (int i = 0; i < 2; ++i) {
         const int H = i ? d.H2 : d.H1, base = 8 + 6 * i;                              // We_i, be_i, Wb_i, bb_i, Ws_i, bs_i
         const uint16_t* const dp = i ? k.w.dz2 : k.w.dz1;
-        wgrad_bgrad(k.e[i], q.GH, q.GH, dp, H, H, base + 2);
-        wgrad_bgrad(k.e[i], q.GH, q.GH, k.da[i], H, H, base + 4);
+        bw.wgrad_bgrad(k.e[i], q.GH, q.GH, dp, H, H, o[base + 2], o[base + 3]);
+        bw.wgrad_bgrad(k.e[i], q.GH, q.GH, k.da[i], H, H, o[base + 4], o[base + 5]);
         dgrad2(dp, base + 2, k.da[i], base + 4, H, k.e[i], q.GH, k.dze[i]);
-        wgrad_bgrad(k.c, q.GC, q.GC, k.dze[i], q.GH, q.GH, base);
+        bw.wgrad_bgrad(k.c, q.GC, q.GC, k.dze[i], q.GH, q.GH, o[base], o[base + 1]);
     }
     dgrad2(k.dze[0], 8, k.dze[1], 14, q.GH, k.c, q.GC, k.dzc);
-    wgrad_bgrad(k.xg, q.KG, q.G, k.dzc, q.GC, q.GC, 6);
+    bw.wgrad_bgrad(k.xg, q.KG, q.G, k.dzc, q.GC, q.GC, o[6], o[7]);
     return launch_status(0);
 }
 
@@ -323,44 +247,18 @@ int dm_train_gated_sgd_step(dm_policy* net, float* params_dev, float* momentum_d
     const char* fn = "dm_train_gated_sgd_step";
     if (train_gated_ok(fn, net)) return -1;
     if (train_step_ok(fn, params_dev, momentum_dev, grads_dev, P, stepsize, momentum, weight_decay, grad_scale)) return -1;
-    const dmp::PolicyDev& d = net->pd; const dmp::GateDev& q = net->gd;
-    const dmt::GatedLayout L = dmt::gated_layout_of(d, q);
+    const dmt::GatedLayout L = dmt::gated_layout_of(net->pd, net->gd);
     if (P != L.P) return fail(std::string(fn) + ": P is " + std::to_string((long long)P) + ", the net has " + std::to_string(L.P) + " parameters (dm_train_gated_param_count)");
-    dmt::GatedSgdArgs a; memset(&a, 0, sizeof(a));
-    for (int k = 0; k < dmt::GATED_MATRICES; ++k) { a.mat[k][0] = L.o[2 * k]; a.mat[k][1] = L.o[2 * k + 1]; }
-    a.w = params_dev; a.v = momentum_dev; a.g = grads_dev; a.P = P; a.lr = (float)stepsize; a.mom = (float)momentum; a.wd = (float)weight_decay; a.gs = (float)grad_scale;
-    a.blocks = (unsigned)std::min<int64_t>((P + 255) / 256, 4096);
-    rt_stream stream = (rt_stream)hip_stream;
-    DevGuard guard(net->device_id);
-    RT_LAUNCH4(dmt::k_train_gated_sgd, a.blocks, stream, a);
-    if (launch_status(0)) return -1;
-    // the new masters into the context, the gate's included: "packed weights = RNE bf16 of the masters" stays true for all twenty arrays
-    dm_policy_params pp; memset(&pp, 0, sizeof(pp));
-    pp.state_dim = d.S; pp.hidden1 = d.H1; pp.hidden2 = d.H2; pp.action_dim = d.A;
-    dm_policy_gate_params gp; memset(&gp, 0, sizeof(gp));
-    gp.goal_dim = q.G; gp.gate_common = q.GC; gp.gate_hidden = q.GH;
-    const float** const arr[dmt::GATED_ARRAYS] = {&pp.w1, &pp.b1, &pp.w2, &pp.b2, &pp.w3, &pp.b3, &gp.gc_w, &gp.gc_b, &gp.g0_w, &gp.g0_b, &gp.g0_bias_w, &gp.g0_bias_b, &gp.g0_scale_w, &gp.g0_scale_b,
-                                                  &gp.g1_w, &gp.g1_b, &gp.g1_bias_w, &gp.g1_bias_b, &gp.g1_scale_w, &gp.g1_scale_b};
-    for (int k = 0; k < dmt::GATED_ARRAYS; ++k) *arr[k] = params_dev + L.o[k];
-    return policy_pack(net, pp, &gp, DM_DEVICE_PTRS, stream);
+    return train_sgd<dmt::GATED_MATRICES>(net, L.o, params_dev, momentum_dev, grads_dev, P, stepsize, momentum, weight_decay, grad_scale, hip_stream);
 }
 
 int dm_train_gated_read(dm_policy* net, int which, int n, void* host_out, size_t capacity) {
     const char* fn = "dm_train_gated_read";
     if (train_gated_ok(fn, net)) return -1;
-    if (!host_out) return fail(std::string(fn) + ": null argument");
-    if (which < 0 || which > 6) return fail(std::string(fn) + ": which must be 0 (s16), 1 (h1), 2 (h2) or 3 .. 6 (sigma_0, beta_0, sigma_1, beta_1)");
-    if (n < 1 || n > net->cap) return fail(std::string(fn) + ": n must be in [1, rows the context holds]");
     const dmp::PolicyDev& d = net->pd;
-    const void* const src[7] = {net->s16, net->h1, net->h2, net->gbuf[0], net->gbuf[1], net->gbuf[2], net->gbuf[3]};
-    const size_t row_bytes[7] = {(size_t)d.K1 * 2, (size_t)d.H1 * 2, (size_t)d.H2 * 2, (size_t)d.H1 * 4, (size_t)d.H1 * 4, (size_t)d.H2 * 4, (size_t)d.H2 * 4};
-    const size_t bytes = (size_t)n * row_bytes[which];
-    if (capacity < bytes) return fail(std::string(fn) + ": the host buffer is smaller than the array (" + std::to_string(bytes) + " bytes)");
-    DevGuard guard(net->device_id);
-#ifndef DM_EMU
-    if (hipDeviceSynchronize() != hipSuccess) return fail("device synchronize failed");
-#endif
-    return rt_d2h(host_out, src[which], bytes, 0) == 0 ? 0 : fail("device to host copy failed");
+    const TrainReadRow table[7] = {{net->s16, (size_t)d.K1 * 2}, {net->h1, (size_t)d.H1 * 2}, {net->h2, (size_t)d.H2 * 2}, {net->gbuf[0], (size_t)d.H1 * 4}, {net->gbuf[1], (size_t)d.H1 * 4},
+                                   {net->gbuf[2], (size_t)d.H2 * 4}, {net->gbuf[3], (size_t)d.H2 * 4}};
+    return train_read(fn, net, table, 7, "0 (s16), 1 (h1), 2 (h2) or 3 .. 6 (sigma_0, beta_0, sigma_1, beta_1)", which, n, host_out, capacity);
 }
 
 }  // extern "C"

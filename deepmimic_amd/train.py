@@ -44,25 +44,45 @@ class _ActorCfg(C.Structure):
 
 # ---- the parameter block and the workspace
 
-def layout(S: int, H1: int, H2: int, A: int) -> dict:
-    """{key: (offset in floats, shape)} of the parameter block, and "P" -> its length"""
-    shapes = dict(w1=(S, H1), b1=(H1,), w2=(H1, H2), b2=(H2,), w3=(H2, A), b3=(A,))
+# A block is its keys in order and their shapes: arrays back to back, matrices (even places) and their bias vectors (odd places) alternating.
+
+def _block_layout(keys, shapes: dict) -> dict:
     out, at = {}, 0
-    for k in KEYS:
+    for k in keys:
         out[k] = (at, shapes[k]); at += int(np.prod(shapes[k]))
     out["P"] = at
     return out
 
 
+def _block_pack(keys, arrays: dict, dtype=np.float32) -> np.ndarray:
+    """the arrays of a dict back to back (dtype None: as they are)"""
+    return np.concatenate([np.ascontiguousarray(arrays[k], dtype=dtype).reshape(-1) for k in keys])
+
+
+def _block_views(flat, keys, lay: dict) -> dict:
+    return {k: flat[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))].reshape(lay[k][1]) for k in keys}
+
+
+def _block_matrix_mask(keys, lay: dict) -> np.ndarray:
+    m = np.zeros(lay["P"], bool)
+    for v in _block_views(m, keys[0::2], lay).values():
+        v[...] = True
+    return m
+
+
+def layout(S: int, H1: int, H2: int, A: int) -> dict:
+    """{key: (offset in floats, shape)} of the parameter block, and "P" -> its length"""
+    return _block_layout(KEYS, dict(w1=(S, H1), b1=(H1,), w2=(H1, H2), b2=(H2,), w3=(H2, A), b3=(A,)))
+
+
 def pack_params(weights: dict) -> np.ndarray:
     """the float32 parameter block of a weights dict (w1 .. b3, tf.layers.dense layout)"""
-    return np.concatenate([np.ascontiguousarray(weights[k], dtype=np.float32).reshape(-1) for k in KEYS])
+    return _block_pack(KEYS, weights)
 
 
 def unpack_params(flat, S: int, H1: int, H2: int, A: int) -> dict:
     """views of a parameter block under the keys w1 .. b3 (numpy array or torch tensor)"""
-    lay = layout(S, H1, H2, A)
-    return {k: flat[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))].reshape(lay[k][1]) for k in KEYS}
+    return _block_views(flat, KEYS, layout(S, H1, H2, A))
 
 
 def workspace_layout(H1: int, H2: int, A: int, n: int) -> dict:
@@ -76,21 +96,27 @@ def workspace_layout(H1: int, H2: int, A: int, n: int) -> dict:
     return out
 
 
+def _need(policy, symbol: str):
+    """the library's entry point `symbol`; a library from before it refuses by name"""
+    call = getattr(policy.lib, symbol, None)
+    if call is None:
+        raise RuntimeError("libdm_hip: this library has no %s (rebuild it)" % symbol)
+    return call
+
+
+def _int_call(policy, symbol: str, *args) -> int:
+    """an entry point that returns a count or a size, < 0 where it refuses"""
+    v = _need(policy, symbol)(policy.h, *(int(a) for a in args))
+    check(policy.lib, v < 0)
+    return int(v)
+
+
 def param_count(policy) -> int:
-    n = policy.lib.dm_train_param_count(policy.h)
-    check(policy.lib, n < 0)
-    return int(n)
+    return _int_call(policy, "dm_train_param_count")
 
 
 def workspace_bytes(policy, n: int) -> int:
-    b = policy.lib.dm_train_workspace_bytes(policy.h, int(n))
-    check(policy.lib, b < 0)
-    return int(b)
-
-
-def _need(policy, gated: bool = False):
-    if not hasattr(policy.lib, "dm_train_gated_actor_grad" if gated else "dm_train_actor_grad"):
-        raise RuntimeError("libdm_hip: this library has no dm_train_%s* entry points (rebuild it)" % ("gated_" if gated else ""))
+    return _int_call(policy, "dm_train_workspace_bytes", n)
 
 
 def actor_grad_device(policy, params_ptr: int, states_ptr: int, n: int, actions_ptr: int, old_logp_ptr: int, adv_ptr: int, grads_ptr: int, stats_ptr: int,
@@ -98,7 +124,7 @@ def actor_grad_device(policy, params_ptr: int, states_ptr: int, n: int, actions_
                       goals_ptr: int = 0, goal_dim: int = 0, logp_ptr: int = 0, stream: int = 0, gated: bool = False):
     """raw device pointers (ints); a_bound_min / a_bound_max: host arrays of A un-normalised entries or None; asynchronous on `stream`.  gated: dm_train_gated_actor_grad,
     the same parameter list on a gated context and its block and workspace"""
-    _need(policy, gated)
+    call = _need(policy, "dm_train_gated_actor_grad" if gated else "dm_train_actor_grad")
     lo = None if a_bound_min is None else np.ascontiguousarray(a_bound_min, dtype=np.float32)
     hi = None if a_bound_max is None else np.ascontiguousarray(a_bound_max, dtype=np.float32)
     for b in (lo, hi):
@@ -106,15 +132,13 @@ def actor_grad_device(policy, params_ptr: int, states_ptr: int, n: int, actions_
             raise ValueError("action bounds must have %d entries" % policy.A)
     fp = lambda a: None if a is None else a.ctypes.data_as(C.POINTER(C.c_float))
     cfg = _ActorCfg(float(ratio_clip), float(bound_weight), fp(lo), fp(hi))
-    call = policy.lib.dm_train_gated_actor_grad if gated else policy.lib.dm_train_actor_grad
     check(policy.lib, call(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(actions_ptr), vp(old_logp_ptr), vp(adv_ptr),
                            C.cast(C.pointer(cfg), C.c_void_p), vp(grads_ptr), vp(stats_ptr), vp(logp_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
 
 
 def value_grad_device(policy, params_ptr: int, states_ptr: int, n: int, targets_ptr: int, grads_ptr: int, stats_ptr: int, workspace_ptr: int, workspace_nbytes: int,
                       goals_ptr: int = 0, goal_dim: int = 0, values_ptr: int = 0, stream: int = 0, gated: bool = False):
-    _need(policy, gated)
-    call = policy.lib.dm_train_gated_value_grad if gated else policy.lib.dm_train_value_grad
+    call = _need(policy, "dm_train_gated_value_grad" if gated else "dm_train_value_grad")
     check(policy.lib, call(policy.h, vp(params_ptr), vp(states_ptr), vp(goals_ptr), int(goal_dim), int(n), vp(targets_ptr), vp(grads_ptr), vp(stats_ptr), vp(values_ptr),
                            vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
 
@@ -131,7 +155,7 @@ def sgd_step_device(policy, params_ptr: int, momentum_ptr: int, grads_ptr: int, 
 
 def read_activations(policy, which: str, n: int) -> np.ndarray:
     """test support: the first n rows of "s16" [n, K1], "h1" or "h2" as the last call left them, bf16 bits (uint16); synchronises"""
-    _need(policy)
+    _need(policy, "dm_train_read_activations")
     width = dict(s16=policy.info()["K1"], h1=policy.H1, h2=policy.H2)[which]
     out = np.zeros((int(n), width), np.uint16)
     check(policy.lib, policy.lib.dm_train_read_activations(policy.h, ("s16", "h1", "h2").index(which), int(n), out.ctypes.data, out.nbytes))
@@ -154,7 +178,7 @@ class _Trainer:
 
     def __init__(self, policy, buf, stepsize: float, momentum: float, weight_decay: float):
         import torch
-        _need(policy, self.GATED)
+        _need(policy, "dm_train_gated_actor_grad" if self.GATED else "dm_train_actor_grad")
         self.policy, self.buf = policy, buf
         self.P = self._param_count(policy)
         tensor_arg("buf", buf, buf.device, torch.float32, [(3, self.P)])
@@ -162,7 +186,7 @@ class _Trainer:
         self.params, self.momentum, self.grads = buf[0], buf[1], buf[2]
         self.stepsize, self.mom, self.weight_decay = float(stepsize), float(momentum), float(weight_decay)
         self._stats = torch.zeros(self.N_STATS, dtype=torch.float64, device=self.device)
-        self._work, self._work_bytes, self._work_rows = None, 0, 0
+        self._work, self._work_bytes, self._work_key = None, 0, None
 
     @classmethod
     def from_policy(cls, policy, weights: dict, stepsize: float, momentum: float = 0.9, weight_decay: float = 0.0, device=None):
@@ -187,12 +211,15 @@ class _Trainer:
         """packs the masters into the context (the precondition of grad: its bf16 weights are the rounding of params)"""
         self.policy.set_weights_device({k: v.data_ptr() for k, v in self.views().items()}, stream=self._stream())
 
-    def _workspace(self, n: int):
-        import torch
-        if n > self._work_rows:
-            self._work_bytes = self._workspace_bytes(self.policy, n)
-            self._work = torch.zeros((self._work_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
-            self._work_rows = n
+    def _workspace(self, sizer, *rows: int):
+        """(pointer, bytes) of a workspace that holds a call of `rows` (one count, or one per batch): it grows to sizer(policy, *rows) and never shrinks in any count"""
+        if rows != self._work_key:                       # (the counts of the last growth again: the steady state of a learner, one comparison)
+            have = self._work_key or (0,) * len(rows)
+            if any(r > h for r, h in zip(rows, have)):
+                import torch
+                self._work_key = tuple(max(r, h) for r, h in zip(rows, have))
+                self._work_bytes = sizer(self.policy, *self._work_key)
+                self._work = torch.zeros((self._work_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
         return self._work.data_ptr(), self._work_bytes
 
     def _rows(self, states, goals):
@@ -224,7 +251,7 @@ class ActorTrainer(_Trainer):
         tensor_arg("old_logp", old_logp, self.device, torch.float32, [(n,)]); tensor_arg("adv", adv, self.device, torch.float32, [(n,)])
         if logp_out is not None:
             tensor_arg("logp_out", logp_out, self.device, torch.float32, [(n,)])
-        ws, nbytes = self._workspace(n)
+        ws, nbytes = self._workspace(self._workspace_bytes, n)
         actor_grad_device(self.policy, self.params.data_ptr(), states.data_ptr(), n, actions.data_ptr(), old_logp.data_ptr(), adv.data_ptr(), self.grads.data_ptr(),
                           self._stats.data_ptr(), ws, nbytes, ratio_clip, bound_weight, a_bound_min, a_bound_max, 0 if goals is None else goals.data_ptr(), G,
                           0 if logp_out is None else logp_out.data_ptr(), self._stream(), self.GATED)
@@ -240,7 +267,7 @@ class CriticTrainer(_Trainer):
         tensor_arg("targets", targets, self.device, torch.float32, [(n,)])
         if values_out is not None:
             tensor_arg("values_out", values_out, self.device, torch.float32, [(n,)])
-        ws, nbytes = self._workspace(n)
+        ws, nbytes = self._workspace(self._workspace_bytes, n)
         value_grad_device(self.policy, self.params.data_ptr(), states.data_ptr(), n, targets.data_ptr(), self.grads.data_ptr(), self._stats.data_ptr(), ws, nbytes,
                           0 if goals is None else goals.data_ptr(), G, 0 if values_out is None else values_out.data_ptr(), self._stream(), self.GATED)
 
@@ -252,11 +279,7 @@ def gated_layout(S: int, H1: int, H2: int, A: int, G: int, GC: int, GH: int) -> 
     shapes = dict(w1=(S, H1), b1=(H1,), w2=(H1, H2), b2=(H2,), w3=(H2, A), b3=(A,), gc_w=(G, GC), gc_b=(GC,))
     for i, H in ((0, H1), (1, H2)):
         shapes.update({"g%d_w" % i: (GC, GH), "g%d_b" % i: (GH,), "g%d_bias_w" % i: (GH, H), "g%d_bias_b" % i: (H,), "g%d_scale_w" % i: (GH, H), "g%d_scale_b" % i: (H,)})
-    out, at = {}, 0
-    for k in GATED_KEYS:
-        out[k] = (at, shapes[k]); at += int(np.prod(shapes[k]))
-    out["P"] = at
-    return out
+    return _block_layout(GATED_KEYS, shapes)
 
 
 def gated_dims(weights: dict) -> tuple:
@@ -267,13 +290,12 @@ def gated_dims(weights: dict) -> tuple:
 
 def pack_gated_params(weights: dict) -> np.ndarray:
     """the float32 parameter block of a gated weights dict (GATED_KEYS, tf.layers.dense layout)"""
-    return np.concatenate([np.ascontiguousarray(weights[k], dtype=np.float32).reshape(-1) for k in GATED_KEYS])
+    return _block_pack(GATED_KEYS, weights)
 
 
 def unpack_gated_params(flat, S: int, H1: int, H2: int, A: int, G: int, GC: int, GH: int) -> dict:
     """views of a gated parameter block under GATED_KEYS (numpy array or torch tensor)"""
-    lay = gated_layout(S, H1, H2, A, G, GC, GH)
-    return {k: flat[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))].reshape(lay[k][1]) for k in GATED_KEYS}
+    return _block_views(flat, GATED_KEYS, gated_layout(S, H1, H2, A, G, GC, GH))
 
 
 def gated_workspace_layout(H1: int, H2: int, A: int, G: int, GC: int, GH: int, n: int) -> dict:
@@ -289,23 +311,17 @@ def gated_workspace_layout(H1: int, H2: int, A: int, G: int, GC: int, GH: int, n
 
 
 def gated_param_count(policy) -> int:
-    _need(policy, True)
-    n = policy.lib.dm_train_gated_param_count(policy.h)
-    check(policy.lib, n < 0)
-    return int(n)
+    return _int_call(policy, "dm_train_gated_param_count")
 
 
 def gated_workspace_bytes(policy, n: int) -> int:
-    _need(policy, True)
-    b = policy.lib.dm_train_gated_workspace_bytes(policy.h, int(n))
-    check(policy.lib, b < 0)
-    return int(b)
+    return _int_call(policy, "dm_train_gated_workspace_bytes", n)
 
 
 def gated_sgd_step_device(policy, params_ptr: int, momentum_ptr: int, grads_ptr: int, P: int, stepsize: float, momentum: float, weight_decay: float = 0.0,
                           grad_scale: float = 1.0, stream: int = 0):
     """the momentum step on a gated block (weight decay on its ten matrices), then the refresh of the context, gate included; the net is required"""
-    _need(policy, True)
+    _need(policy, "dm_train_gated_sgd_step")
     check(policy.lib, policy.lib.dm_train_gated_sgd_step(policy.h, vp(params_ptr), vp(momentum_ptr), vp(grads_ptr), int(P), float(stepsize), float(momentum),
                                                          float(weight_decay), float(grad_scale), vp(stream)))
 
@@ -316,7 +332,7 @@ GATED_READ = ("s16", "h1", "h2", "sigma0", "beta0", "sigma1", "beta1")
 def read_gated(policy, which: str, n: int) -> np.ndarray:
     """test support: the first n rows of "s16" [n, K1], "h1", "h2" (bf16 bits, uint16) or "sigma0", "beta0" [n, H1], "sigma1", "beta1" [n, H2] (float32) as the last call
     left them; synchronises"""
-    _need(policy, True)
+    _need(policy, "dm_train_gated_read")
     i = GATED_READ.index(which)
     width = (policy.info()["K1"], policy.H1, policy.H2, policy.H1, policy.H1, policy.H2, policy.H2)[i]
     out = np.zeros((int(n), width), np.uint16 if i < 3 else np.float32)
@@ -365,22 +381,14 @@ def disc_workspace_layout(S: int, H1: int, H2: int, n_expert: int, n_agent: int)
 
 
 def disc_workspace_bytes(policy, n_expert: int, n_agent: int) -> int:
-    _need_disc(policy)
-    b = policy.lib.dm_train_disc_workspace_bytes(policy.h, int(n_expert), int(n_agent))
-    check(policy.lib, b < 0)
-    return int(b)
-
-
-def _need_disc(policy):
-    if not hasattr(policy.lib, "dm_train_disc_grad"):
-        raise RuntimeError("libdm_hip: this library has no dm_train_disc_grad (rebuild it)")
+    return _int_call(policy, "dm_train_disc_workspace_bytes", n_expert, n_agent)
 
 
 def disc_grad_device(policy, params_ptr: int, expert_ptr: int, n_expert: int, agent_ptr: int, n_agent: int, grads_ptr: int, stats_ptr: int, workspace_ptr: int,
                      workspace_nbytes: int, grad_penalty: float = 10.0, logit_reg: float = 0.05, logits_ptr: int = 0, stream: int = 0):
     """raw device pointers (ints): the two observation batches [n_expert, S] and [n_agent, S], stats double[8] (DISC_STATS), logits [n_expert + n_agent] optional,
     expert rows first; asynchronous on `stream`"""
-    _need_disc(policy)
+    _need(policy, "dm_train_disc_grad")
     cfg = _DiscCfg(float(grad_penalty), float(logit_reg))
     check(policy.lib, policy.lib.dm_train_disc_grad(policy.h, vp(params_ptr), vp(expert_ptr), int(n_expert), vp(agent_ptr), int(n_agent), C.cast(C.pointer(cfg), C.c_void_p),
                                                     vp(grads_ptr), vp(stats_ptr), vp(logits_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
@@ -395,18 +403,8 @@ class DiscTrainer(_Trainer):
 
     def __init__(self, *a, **kw):
         super().__init__(*a, **kw)
-        _need_disc(self.policy)
+        _need(self.policy, "dm_train_disc_grad")
         self._coef = (0.0, 0.0)
-        self._work_shape = (0, 0)
-
-    def _disc_workspace(self, ne: int, na: int):
-        import torch
-        if ne > self._work_shape[0] or na > self._work_shape[1]:
-            ne_c, na_c = max(ne, self._work_shape[0]), max(na, self._work_shape[1])
-            self._work_bytes = disc_workspace_bytes(self.policy, ne_c, na_c)
-            self._work = torch.zeros((self._work_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
-            self._work_shape = (ne_c, na_c)
-        return self._work.data_ptr(), self._work_bytes
 
     def grad(self, expert_obs, agent_obs, grad_penalty: float = 10.0, logit_reg: float = 0.05, logits_out=None):
         import torch
@@ -416,7 +414,7 @@ class DiscTrainer(_Trainer):
         tensor_arg("agent_obs", agent_obs, self.device, torch.float32, [(na, self.policy.S)])
         if logits_out is not None:
             tensor_arg("logits_out", logits_out, self.device, torch.float32, [(ne + na,)])
-        ws, nbytes = self._disc_workspace(ne, na)
+        ws, nbytes = self._workspace(disc_workspace_bytes, ne, na)
         disc_grad_device(self.policy, self.params.data_ptr(), expert_obs.data_ptr(), ne, agent_obs.data_ptr(), na, self.grads.data_ptr(), self._stats.data_ptr(), ws, nbytes,
                          grad_penalty, logit_reg, 0 if logits_out is None else logits_out.data_ptr(), self._stream())
         self._coef = (float(grad_penalty), float(logit_reg))
@@ -572,19 +570,23 @@ def reference_backward(weights: dict, s16, h1, h2, dz3_bits):
     dz1_bits = bf16_bits(np.where(h1 != 0, (dz2 @ bf16_round(weights["w2"]).astype(np.float64).T).astype(f), f(0)))
     dz1 = bf16_value(dz1_bits).astype(np.float64)
     g["w1"] = s16.astype(np.float64).T @ dz1; g["b1"] = dz1.sum(axis=0)
-    return dict(grads=np.concatenate([g[k].astype(f).reshape(-1) for k in KEYS]), dz2=dz2_bits, dz1=dz1_bits)
+    return dict(grads=_block_pack(KEYS, g), dz2=dz2_bits, dz1=dz1_bits)
+
+
+def _reference_head(z3, head: str, weights: dict, kw: dict) -> dict:
+    """the head of a *_grad call on z3 at the device's rounding points: reference_actor_head with a_mean / a_std / logstd from the weights (absent: 0 / 1 / 0), or
+    reference_value_head"""
+    if head != "actor":
+        return reference_value_head(z3, **kw)
+    dflt = lambda k, v: np.full(z3.shape[1], v, np.float32) if weights.get(k) is None else weights[k]
+    return reference_actor_head(z3, a_mean=dflt("a_mean", 0), a_std=dflt("a_std", 1), logstd=dflt("logstd", 0), **kw)
 
 
 def reference_grad(weights: dict, states, head: str, s_clip=np.inf, **kw):
     """The whole *_grad call in numpy.  head "actor": kw = actions, old_logp, adv[, ratio_clip, bound_weight, a_bound_min, a_bound_max] (a_mean, a_std, logstd from the
     weights); head "critic": kw = targets.  `states` holds the goal columns.  dict(grads, stats, dz3, dz2, dz1, z3, s16, h1, h2 and the head's own outputs)."""
     s16, h1, h2, z3 = reference_forward_bf16(weights, states, s_clip)
-    if head == "actor":
-        A = z3.shape[1]
-        dflt = lambda k, v: np.full(A, v, np.float32) if weights.get(k) is None else weights[k]
-        hd = reference_actor_head(z3, a_mean=dflt("a_mean", 0), a_std=dflt("a_std", 1), logstd=dflt("logstd", 0), **kw)
-    else:
-        hd = reference_value_head(z3, **kw)
+    hd = _reference_head(z3, head, weights, kw)
     out = dict(hd); out.update(reference_backward(weights, s16, h1, h2, hd["dz3"]))
     out.update(z3=z3, s16=s16, h1=h1, h2=h2)
     return out
@@ -608,11 +610,7 @@ def reference_step(params, momentum, grads, stepsize, mom, weight_decay=0.0, gra
 
 
 def matrix_mask_of(S: int, H1: int, H2: int, A: int) -> np.ndarray:
-    lay = layout(S, H1, H2, A)
-    m = np.zeros(lay["P"], bool)
-    for k in ("w1", "w2", "w3"):
-        m[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))] = True
-    return m
+    return _block_matrix_mask(KEYS, layout(S, H1, H2, A))
 
 
 # ---- the discriminator update in numpy
@@ -690,7 +688,7 @@ def reference_disc_grad(weights: dict, expert_obs, agent_obs, grad_penalty: floa
             g["w3"] = g["w3"] + f(0)
         if logit_reg > 0:
             g["w3"] = fma32(f(logit_reg), w["w3"], g["w3"])
-    out["grads"] = np.concatenate([g[k].astype(f).reshape(-1) for k in KEYS])
+    out["grads"] = _block_pack(KEYS, g)
     sqs = {k: (np.asarray(w[k], f).astype(d) ** 2).sum() for k in ("w1", "w2", "w3")}
     out["stats"] = np.concatenate([hd["stats"], [pen_stat, 0.5 * sqs["w3"], 0.5 * (sqs["w1"] + sqs["w2"] + sqs["w3"])]])
     return out
@@ -802,23 +800,14 @@ def reference_gated_grad(weights: dict, states, head: str, s_clip=np.inf, rounde
     if not rounded:
         dz3 = _head64(out["z3"], head, weights, kw)
     else:
-        A = out["z3"].shape[1]
-        if head == "actor":
-            dflt = lambda k, v: np.full(A, v, np.float32) if weights.get(k) is None else weights[k]
-            hd = reference_actor_head(out["z3"], a_mean=dflt("a_mean", 0), a_std=dflt("a_std", 1), logstd=dflt("logstd", 0), **kw)
-        else:
-            hd = reference_value_head(out["z3"], **kw)
+        hd = _reference_head(out["z3"], head, weights, kw)
         out.update(hd)
-        dz3 = bf16_value(hd["dz3"])[:, :A]
+        dz3 = bf16_value(hd["dz3"])[:, :out["z3"].shape[1]]
     out.update(reference_gated_backward(weights, out, dz3, rounded))
-    out["flat"] = np.concatenate([np.asarray(out["grads"][k]).reshape(-1) for k in GATED_KEYS])
+    out["flat"] = _block_pack(GATED_KEYS, out["grads"], dtype=None)
     return out
 
 
 def gated_matrix_mask_of(S: int, H1: int, H2: int, A: int, G: int, GC: int, GH: int) -> np.ndarray:
     """the entries of a gated block under the weight decay: its ten matrices"""
-    lay = gated_layout(S, H1, H2, A, G, GC, GH)
-    m = np.zeros(lay["P"], bool)
-    for k in GATED_KEYS[0::2]:
-        m[lay[k][0]:lay[k][0] + int(np.prod(lay[k][1]))] = True
-    return m
+    return _block_matrix_mask(GATED_KEYS, gated_layout(S, H1, H2, A, G, GC, GH))
