@@ -40,6 +40,9 @@ SIGNATURES = {
     "dm_replay_sample": ([_i, _p, _i, _p, _i, _u64, _u32, _p, _p, _p], None),
     "dm_episode_workspace_bytes": ([_i], _i64),
     "dm_episode_stats": ([_i, _i, _i] + [_p] * 10 + [_i, _i, _p, _i64, _p], None),
+    "dm_amp_batch_rewards_workspace": ([_i, _i], _i64),
+    "dm_amp_batch_rewards": ([_i, _i, _i] + [_p] * 4 + [_d] * 2 + [_p] * 5 + [_i64, _p], None),
+    "dm_amp_value_clip": ([_i, _i, _p, _p, _d, _p, _d, _p, _p], None),
     "dm_time_warp_dims": ([_p, _pi32], None),
     "dm_time_warp_sample": ([_p, _p, _p, _p, _i, _p], None),
     "dm_time_warp_align": ([_i, _i, _i, _i, _i, _p, _p, _p, _d, _p, _p, _p], None),

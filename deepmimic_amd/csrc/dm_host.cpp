@@ -1461,6 +1461,7 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_ppo_batch.h"     // PPO advantages, sample lists and shuffled minibatch gathers over a device-resident rollout
 #include "dm_replay.h"        // AMP discriminator data: device replay stores and expert draws (after dm_ppo_batch.h: feistel_perm)
 #include "dm_episode.h"       // episode returns, lengths and end-cause totals over a device-resident rollout (after dm_ppo_batch.h: its workgroup width and tree)
+#include "dm_amp_rewards.h"   // AMP batch rewards, reward statistics, running value bounds and the value clip (after dm_policy_host.h: the head's expressions; dm_ppo_batch.h: fold_groups)
 #include "dm_train.h"         // PPO actor / critic minibatch gradients and the momentum step on a live policy context (after dm_policy_host.h and dm_ppo_batch.h: its tree)
 #include "dm_train_gated.h"   // the same updates for the gated nets of the AMP task agents (after dm_train.h: its head, fold and gradient kernels)
 #include "dm_time_warp.h"     // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel

@@ -173,19 +173,21 @@ DMP_DEV float philox_normal(uint32_t env, uint32_t ctr, uint32_t seed_lo, uint32
 
 // The scalar head's epilogue for one row < M (ScalarHead above).  Every multiply-add that may be contracted is an explicit fmaf and no other product feeds a sum, so
 // device and emulator round at the same points: d (one rounding), d / 4 (exact), fmaf, the product with scale, 1 - lerp, its product with r, fmaf.  A NaN y gives
-// lo (fmaxf returns its other operand) / a style reward of 0.
+// lo (fmaxf returns its other operand) / a style reward of 0.  The three expressions are functions of their own: dm_amp_rewards.h evaluates the same ones over a stored rollout.
+DMP_DEV float value_clip(float y, float lo, float hi) { return fminf(fmaxf(y, lo), hi); }
+DMP_DEV float style_reward(float y, float scale) { const float d = 1.0f - y; return fmaxf(fmaf(-0.25f * d, d, 1.0f), 0.0f) * scale; }
+DMP_DEV float style_blend(float lerp, float task_r, float s) { return fmaf(lerp, task_r, (1.0f - lerp) * s); }
 DMP_DEV void scalar_head_store(const ScalarIO& io, int row, float y) {
     const ScalarHead& h = io.sh;
     float out = h.fill, raw = h.fill;
     if (!h.row_mask || h.row_mask[row] != 0) {
         raw = y;
         if (h.kind == HEAD_VALUE) {
-            out = fminf(fmaxf(y, h.lo), h.hi);
+            out = value_clip(y, h.lo, h.hi);
             if (h.terminate) { const int tm = h.terminate[row]; if (tm == 1) out = h.val_fail; else if (tm == 2) out = h.val_succ; }
         } else {
-            const float d = 1.0f - y;
-            out = fmaxf(fmaf(-0.25f * d, d, 1.0f), 0.0f) * h.scale;
-            if (h.task_r) out = fmaf(h.lerp, h.task_r[row], (1.0f - h.lerp) * out);
+            out = style_reward(y, h.scale);
+            if (h.task_r) out = style_blend(h.lerp, h.task_r[row], out);
         }
     }
     io.actions[row] = out;

@@ -220,3 +220,13 @@ def all_reduce_gradients(trainer, group=None):
     import torch.distributed as dist
     dist.all_reduce(trainer.grads, op=dist.ReduceOp.SUM, group=group)
     return trainer.grads
+
+
+def all_reduce_reward_bounds(tracker, group=None):
+    """The `mpi_util.reduce_min` of learning/amp_agent.py:415-419 for an `amp_rewards.AmpRewards` (or any object with a float32 [2] tensor `bounds`): MIN over the
+    ranks on bounds[0:1] (reward_min), MAX on bounds[1:2] (reward_max), IN PLACE (RCCL on a GPU, gloo on the CPU test harness), so every rank clips its critic to
+    the same value bounds.  Call it after `update_torch` / `update_from_disc` and before `clip_torch`.  Ordered on torch's current stream, like the tracker's own calls."""
+    import torch.distributed as dist
+    dist.all_reduce(tracker.bounds[0:1], op=dist.ReduceOp.MIN, group=group)
+    dist.all_reduce(tracker.bounds[1:2], op=dist.ReduceOp.MAX, group=group)
+    return tracker.bounds

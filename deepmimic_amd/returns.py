@@ -56,13 +56,16 @@ def td_lambda_returns_torch(rewards, values, term_values, terminate, done, valid
 
 
 def critic_returns_torch(critic, obs, goals, terminal_obs, terminal_goal, terminate, done, valid, rewards, gamma: float, td_lambda: float,
-                         lib_path: Optional[str] = None, return_values: bool = False):
+                         lib_path: Optional[str] = None, return_values: bool = False, bounds=None):
     """TD(lambda) targets of a stacked rollout straight from a `deepmimic_amd.heads.Critic`: obs [T + 1, N, S] (row T: the observation after the last step),
     goals [T + 1, N, G] or None, terminal_obs [T, N, S] / terminal_goal [T, N, G] (info["terminal_obs"] / info["terminal_goal"] of every step), the flags and
     rewards [T, N].  Two critic launches -- values on obs, and term_values on terminal_obs under row_mask = done, so tiles without a finished episode cost
     nothing -- then dm_td_lambda_returns with the critic's val_fail / val_succ.  The Fail / Succ override is td_lambda_returns' own rule, so the values stay
     the net's (clipped) output.  Returns (returns [T, N] float32, mask [T, N] int32), and the values [T + 1, N] behind them as a third item if
-    `return_values` (what `ppo_batch.advantages_torch` takes); all on torch's current stream."""
+    `return_values` (what `ppo_batch.advantages_torch` takes); all on torch's current stream.
+    bounds: an `amp_rewards.AmpRewards` -- the AMP agents' value clip (learning/amp_agent.py:441-443): both evaluations are clipped in place to the tracker's
+    device-resident bounds over 1 - discount (term_values under row_mask = done) before dm_td_lambda_returns, bit for bit what a `Critic(lo, hi)` rebuilt from a host
+    copy of the bounds gives, without the host read.  None: nothing changes."""
     import torch
     T = int(rewards.shape[0])
     if int(obs.shape[0]) != T + 1:
@@ -70,5 +73,8 @@ def critic_returns_torch(critic, obs, goals, terminal_obs, terminal_goal, termin
     done_i = done.to(torch.int32) if done.dtype == torch.bool else done
     values = critic.eval_torch(obs, goals)
     term_values = critic.eval_torch(terminal_obs, terminal_goal, row_mask=done_i, fill=0.0)
+    if bounds is not None:
+        bounds.clip_torch(values, out=values)
+        bounds.clip_torch(term_values, row_mask=done_i, fill=0.0, out=term_values)
     ret, mask = td_lambda_returns_torch(rewards, values, term_values, terminate, done_i, valid, gamma, td_lambda, critic.val_fail, critic.val_succ, lib_path=lib_path)
     return (ret, mask, values) if return_values else (ret, mask)

@@ -686,6 +686,49 @@ int dm_episode_stats(int device_id, int T, int N, const float* rewards_dev, cons
                      float* ep_return_out /* NULL or [T, N] */, int32_t* ep_len_out /* NULL or [T, N] */, void* totals_dev /* NULL or DM_EP_TOTALS_WORDS words, in/out */,
                      int64_t* hist_dev /* NULL or [bins], in/out */, int bins, int bin_steps, void* work_dev, int64_t work_bytes, void* hip_stream);
 
+/* ---- AMP batch rewards, reward statistics and the critic's value bounds over a device-resident rollout (deepmimic_amd/csrc/dm_amp_rewards.h,
+ * deepmimic_amd/amp_rewards.py): AMPAgent._batch_calc_reward (learning/amp_agent.py:393-421), _lerp_reward (:423-425) and the value clip of _compute_batch_vals
+ * (:436-443).  At train time the reference scores the WHOLE stored rollout with the discriminator as it is after _update_disc and clips the critic's values to the
+ * RUNNING extrema of that reward over 1 - discount.  Stateless like dm_td_lambda_returns: DEVICE pointers, time-major T x N arrays addressed by the flat index
+ * i = t * N + n, asynchronous on hip_stream of device device_id, no allocation, no host read, no synchronisation and no atomics inside; a refused call launches
+ * nothing, writes nothing and names its reason through dm_last_error.
+ *
+ * dm_amp_batch_rewards.  logits T x N: the discriminator's y (raw_out_dev of dm_policy_eval_scalar); task_reward T x N or NULL; done, valid T x N int32 (valid NULL:
+ * every episode valid, and done is then not read and may be NULL too).  reward_scale and task_reward_lerp are rounded to the floats a dm_scalar_head holds.
+ *   rewards_out T x N, EVERY row, counted or not: bit for bit what the DM_SCALAR_HEAD_STYLE head writes from the same logit (one device function serves both):
+ *     d = 1 - y;  s = fmaxf(fmaf(-0.25f * d, d, 1.0f), 0.0f) * scale;  r = fmaf(lerp, task_r, (1.0f - lerp) * s) with a task reward, r = s without.
+ *   mask_out T x N int32 (NULL: not wanted): exactly the mask of dm_td_lambda_returns from the same done / valid -- 0 for the steps of an episode that ended with
+ *     valid == 0 inside the window, back to the previous done or to t = 0, 1 elsewhere (an episode still running at T included).  It depends on the flags alone.
+ *     A row is COUNTED where the mask is 1.
+ *   stats_out double[DM_AMP_STATS_WORDS], over the counted rows: DM_AMP_STAT_N their number; DM_AMP_STAT_MEAN / DM_AMP_STAT_STD the mean and the POPULATION standard
+ *     deviation of s, the scaled style term before the blend (Disc_Reward_Mean / Disc_Reward_Std, amp_agent.py:400-403), in two passes (the mean, then the squared
+ *     deviations), fp64 from the fp32 values, no product contracted into a sum; DM_AMP_STAT_MIN / DM_AMP_STAT_MAX this call's min and max of r.  n = 0: mean = std = 0,
+ *     min = +inf, max = -inf.
+ *   bounds float[2], in/out: bounds[0] = min(bounds[0], cur_min), bounds[1] = max(bounds[1], cur_max); the initial state is {+inf, -inf} (amp_agent.py:46-47);
+ *     n = 0 leaves them untouched.  Every min / max here keeps a NaN, as np.amin / np.minimum do: a NaN r in a counted row makes this call's min and max, and with them
+ *     both bounds, NaN (and stays: a non-finite input remains visible); rows that are not counted reach neither the bounds nor the statistics.
+ * Order of every fp64 sum, fixed for given (T, N): a column's counted rows from t = T - 1 down to 0; the 64 columns of a group n / 64 by the tree x[j] += x[j + w],
+ * w = 32 .. 1 (columns past N: 0); the groups in contiguous runs of ceil(groups / 256) per thread of one 256-thread workgroup, each run in order, and the same tree with
+ * w = 128 .. 1.  Two calls on one input give the same bytes.  The group partials live in `workspace` (dm_amp_batch_rewards_workspace(T, N) bytes, the caller's,
+ * 8-byte aligned like stats_out).
+ * Refused: T < 1, N < 1, T * N > 2^31 - 1; a NULL logits / rewards_out / bounds / stats_out / workspace; valid without done; a task reward with task_reward_lerp
+ * outside [0, 1] (NaN: the agent has none); a workspace that is too small or misaligned; no HIP device or a device_id it does not have.
+ *
+ * dm_amp_value_clip.  out[i] = fminf(fmaxf(values[i], lo), hi) for i < n, with lo = (float)((double)bounds[0] / (1.0 - discount)) and hi likewise from bounds[1], read
+ * on the device: the expression of the DM_SCALAR_HEAD_VALUE head, so with finite bounds the result is bit-identical to that head evaluated with lo / hi set to the same
+ * floats.  row_mask int32[n] (NULL: every row): a row whose flag is 0 gets `fill`.  out may alias values.  The Fail / Succ override stays dm_td_lambda_returns' rule.
+ * A NaN bound does not clip on its side (fmaxf / fminf return their other operand); a NaN value comes out as lo (as hi where lo is NaN too).  The initial bounds
+ * {+inf, -inf} give -inf for every row.
+ * Refused: n < 1, a NULL values / bounds / out, discount outside [0, 1), no HIP device or a device_id it does not have. */
+enum { DM_AMP_STAT_N = 0, DM_AMP_STAT_MEAN = 1, DM_AMP_STAT_STD = 2, DM_AMP_STAT_MIN = 3, DM_AMP_STAT_MAX = 4, DM_AMP_STATS_WORDS = 5 };
+int64_t dm_amp_batch_rewards_workspace(int T, int N);  /* < 0: refused (dm_last_error) */
+int dm_amp_batch_rewards(int device_id, int T, int N, const float* logits_dev, const float* task_reward_dev /* NULL: style reward only */,
+                         const int32_t* done_dev, const int32_t* valid_dev /* NULL: all valid */, double reward_scale, double task_reward_lerp,
+                         float* rewards_out, int32_t* mask_out /* NULL or [T, N] */, float* bounds_dev /* [2] in/out */, double* stats_out /* [DM_AMP_STATS_WORDS] */,
+                         void* workspace, int64_t workspace_bytes, void* hip_stream);
+int dm_amp_value_clip(int device_id, int n, const float* values_dev, const float* bounds_dev /* [2] */, double discount, const int32_t* row_mask_dev /* NULL or [n] */,
+                      double fill, float* out_dev, void* hip_stream);
+
 /* ---- the test-mode time-warp return of `--scene imitate_amp` for a batch of envs (deepmimic_amd/csrc/dm_time_warp.h, dm_device.h k_time_warp_sample,
  * deepmimic_amd/time_warp.py): cSceneImitateAMP::CalcRewardTimeWarp (scenes/SceneImitateAMP.cpp:174-207, 417-480; util/DynamicTimeWarper.cpp:114-140), what the
  * reference's learner logs as Test_Return for an AMP imitation policy.  Stateless like dm_replay_* and dm_episode_stats: the caller owns every byte, DEVICE pointers
