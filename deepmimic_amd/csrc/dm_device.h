@@ -694,10 +694,16 @@ struct EnvSim {
     }
     // bias force C_k and row k of H (lower triangle, into the packed store): zero, then the ancestor-or-self dofs j <= k:
     // H_kj = a_j . Lq + g_j . Pm with the composite-body momentum (Pm, Lq about the root origin) of dof k's unit velocity
-    DM_DEV void dyn_row(int k, Real diag_scale) {
+    // MODE (two characters per wavefront, DuoSim::update): 0 = both, the row into the packed store; 1 = the bias force alone; 2 = the row alone, handed over in
+    // registers -- h2[p] = entries 2p, 2p + 1, zero right of the diagonal (the chain mask is cut at k) and all zero for a lane without a row (`has`) -- and
+    // without the diagonal term: for the phases with diag_scale == 0, where `H_kk + 0` is H_kk (H_kk > 0).
+    template <int MODE = 0>
+    DM_DEV void dyn_row(int k, Real diag_scale, R2* h2 = nullptr, bool has = true) {
+        static_assert(MODE == 0 || LW == 32, "the split forms belong to the two-per-wave kernel");
         const int di = s.mdl.dof_info[k], dj = DM_DI_JOINT(di), kind = DM_DI_KIND(di), ax = DM_DI_AXIS(di);
         const v3 a = (kind == DK_ROOT_LIN) ? ld3(&s.dofrec[k][3]) : ld3(&s.dofrec[k][0]);
-        s.dofrec[k][7] = (kind == DK_ROOT_LIN) ? s.Fs[0][ax] : dot(a, ld3(s.Ns[dj]));
+        if constexpr (MODE != 2) s.dofrec[k][7] = (kind == DK_ROOT_LIN) ? s.Fs[0][ax] : dot(a, ld3(s.Ns[dj]));
+        if constexpr (MODE == 1) return;
         const Real* ic = s.Ic[dj];
         v3 h = mk3(ic[1], ic[2], ic[3]), Pm, Lp;
         if (kind == DK_ROOT_LIN) { Pm = ic[0] * a; Lp = cross(h, a); }
@@ -711,7 +717,8 @@ struct EnvSim {
         // lane reads the same record dofrec[j] (one conflict-free LDS broadcast, requested ahead by the unrolled schedule) and keeps
         // the value when j is on its chain -- against a per-lane walk over the set bits, whose record gathers collide on the LDS banks
         // and whose trip count is the longest chain of the wave.
-        const uint32_t lo = s.mdl.chain_lo[dj] & ((k < 31) ? ((2u << k) - 1u) : ~0u), hi = (k < 32) ? 0u : (s.mdl.chain_hi[dj] & ((k < 63) ? ((2u << (k - 32)) - 1u) : ~0u));
+        const uint32_t lo_ = s.mdl.chain_lo[dj] & ((k < 31) ? ((2u << k) - 1u) : ~0u), hi_ = (k < 32) ? 0u : (s.mdl.chain_hi[dj] & ((k < 63) ? ((2u << (k - 32)) - 1u) : ~0u));
+        const uint32_t lo = (MODE == 2 && !has) ? 0u : lo_, hi = (MODE == 2 && !has) ? 0u : hi_;
         const Real dk = diag_scale * s.mdl.kd[dj];
         if constexpr (LW == 32) {      // (two characters per wavefront: 256 registers; the one-per-wave biped kernels run at 128)
         // (round 6) the records of pair p + 1 are requested before the dot products of pair p, and the pair is computed by every lane (only the store is
@@ -739,9 +746,11 @@ struct EnvSim {
                 }
                 v2[c] = v;
             });
-            if (2 * p <= k) *reinterpret_cast<R2*>(&row[2 * p]) = v2;
+            if constexpr (MODE == 2) h2[p] = v2;
+            else if (2 * p <= k) *reinterpret_cast<R2*>(&row[2 * p]) = v2;
             DM_SCHED_FENCE();      // one pair per scheduling region (without the fence: profiles/r06_ab_lds_lookahead.json)
         });
+        if constexpr (MODE == 2) return;
         // the diagonal term: the lane adds Kd dt to its own entry H_kk once, behind the loop (the chain bit of j == k is always set, so the word stored above is the
         // unmasked dot product and this is the add on the operands `if (j == k) v += dk` had inside the loop, at 3 VALU for each of the 34 entries of every lane).
         // In every phase, dk == 0 included: the stored word is the result of the same add.  LDS operations of one wave complete in order and the sync() of the

@@ -379,6 +379,9 @@ struct DuoSim {
     // checks it).  Except the profiling / tap instantiation, which keeps the loops of rounds 3-5 WITH the tests: without them the fp32 kernel spills 321 VGPRs instead of 56
     // (the taps' own live values) and its phase shares say nothing about the production kernel any more; its fp64 parity build runs the same loops.
     static constexpr bool YFULL = !TAPS;
+    // The substep phases hand the lane's row of H from dyn_row to chol_solve in registers (fp32 only; the tap build reads H out of Lt and keeps the LDS route, as does the
+    // stable-PD phase of every build, whose diagonal carries Kd dt): -1.9 % kernel time, profiles/ab_duo_dofrec.json
+    static constexpr bool HREG = sizeof(Real) == 4 && !TAPS;
     // Fallback class for a pair with a heavily contacted character: the narrow class (rows 32..63 in the HBM / L2 overflow block, requested two rows ahead), no scratch at all.
     // (A class with all 64 rows of A in VGPRs and the 64-row Gram on the matrix core: +8..13 % closed-loop throughput under an untrained policy, but its 64-register row file
     // pushes 10 kernel-long-lived values of the two-per-wave kernel into scratch -- 40 B / lane, +7.5 MB of HBM traffic per launch: rejected, profiles/r05_ab_fallback_rowfile.json.)
@@ -516,7 +519,9 @@ struct DuoSim {
     // v*, word 7 the bias force) -- the two divergent passes over the dof kinds are skipped.  DuoSim::update says so for its first substep, which runs at the pose of its
     // stable-PD phase.  After a park inside the update loop (k_env_step_duo: kin_pre(false) behind park) the next dynamics() is a phase-0 call, which rebuilds the
     // records: a skipped pass never meets records of another pose.
-    DM_DEV void dynamics(int iset, Real diag_scale, bool recs_in_place = false) {
+    // hrow_late (HREG kernels, the phases with diag_scale == 0): only the bias force is built here; the lane builds its row of H in registers at the head of chol_solve,
+    // behind the right-hand side, instead of storing it to Lt (17 predicated stores + the diagonal's read-modify-write) and reading it back (17 reads) across two barriers
+    DM_DEV void dynamics(int iset, Real diag_scale, bool recs_in_place = false, bool hrow_late = false) {
         const int D = m.D;
 #ifndef DM_EMU
         if constexpr (sizeof(Real) == 4) {
@@ -534,7 +539,7 @@ struct DuoSim {
             b.dyn_subtree();
             sync();
         }
-        if (hl + 3 < D) b.dyn_row(hl + 3, diag_scale);
+        if (hl + 3 < D) { if (HREG && hrow_late) b.template dyn_row<1>(hl + 3, diag_scale); else b.dyn_row(hl + 3, diag_scale); }
         if (hl == HW - 1) {
             for (int k = 0; k < 3; ++k) s.dofrec[k][7] = s.Fs[0][k];       // root translation: C_k = total force
             s.sc[7] = s.Ic[0][0];                                           // H_kk, k < 3: total mass (Ic is recycled before the factorisation)
@@ -544,17 +549,23 @@ struct DuoSim {
 
     // ------------------------------------------------------------------ Cholesky + solve, 31 row lanes per character
     // x := H^-1 x for the LDS vector xvec.  Same factor layout in LDS as EnvSim::chol_solve (diagonal slot = 1/L_kk).
-    DM_DEV void chol_solve(Real* xvec) {
+    // hrow_late: H is not in Lt -- the lane builds its row here, from the dof records and the Newton-Euler sums that dynamics(..., hrow_late) of the same pose left
+    // (Ic, Ns, Fs lie behind the words colbuf aliases, and nothing writes them between the two: the right-hand side reads tau and the bias force).  The entries right of
+    // the diagonal are zeros here and words of later rows on the LDS route; the factorisation consumes neither.
+    DM_DEV void chol_solve(Real* xvec, bool hrow_late = false) {
         const int D = m.D;
         const int own = hl + 3;                          // the row this lane owns
         const bool valid = own < D;
         R2 h2[NP2];
         const int rr = valid ? own : 3;
+        if (HREG && hrow_late) b.template dyn_row<2>(rr, (Real)0, h2, valid);
+        else {
 #pragma unroll
-        for (int p = 0; p < NP2; ++p) {
-            R2 v = *reinterpret_cast<const R2*>(&s.Lt[L::lrow(rr) + 2 * p]);
-            if (!valid) { v[0] = 0; v[1] = 0; }
-            h2[p] = v;
+            for (int p = 0; p < NP2; ++p) {
+                R2 v = *reinterpret_cast<const R2*>(&s.Lt[L::lrow(rr) + 2 * p]);
+                if (!valid) { v[0] = 0; v[1] = 0; }
+                h2[p] = v;
+            }
         }
         // Two columns per block, software-pipelined: the block's two columns are published through LDS for the trailing rank-2
         // update, but the NEXT block's pivot pair is brought up to date from registers (four in-register broadcasts of the
@@ -1187,7 +1198,7 @@ _Pragma("unroll") \
                 prio_low();
             }
             b.mark(ph == 0 ? 1 : 5);
-            dynamics(ph == 0 ? 0 : 1, ph == 0 ? rdt : (Real)0, ph == 1);      // (ph 1: the records of phase 0's pose)
+            dynamics(ph == 0 ? 0 : 1, ph == 0 ? rdt : (Real)0, ph == 1, ph != 0);      // (ph 1: the records of phase 0's pose; the substeps' rows of H are built in chol_solve)
             b.mark(ph == 0 ? 2 : 6);
             if (ph == 0) {
                 b.spd_rhs_pre(rdt);
@@ -1196,7 +1207,7 @@ _Pragma("unroll") \
             } else { for (int k = hl; k < D; k += HW) { Real r = s.tau[k] - s.dofrec[k][7]; if (PERT && pert) r += b.pert_gen_force(k); s.rhs[k] = r; } sync(); }
             DM_OPAQUE_V(hl); DM_OPAQUE_V(b.l);
             dm_setprio<kPrioChain>();
-            chol_solve(s.rhs);
+            chol_solve(s.rhs, ph != 0);
             prio_low();
             DM_OPAQUE_V(hl); DM_OPAQUE_V(b.l); DM_OPAQUE_V(b.li);
             if (ph == 0) {
