@@ -60,6 +60,8 @@ SIGNATURES = {
     "dm_train_gated_value_grad": ([_p] * 4 + [_i] * 2 + [_p] * 5 + [_i64, _p], None),
     "dm_train_gated_sgd_step": ([_p] * 4 + [_i64] + [_d] * 4 + [_p], None),
     "dm_train_gated_read": ([_p, _i, _i, _p, _sz], None),
+    "dm_train_opt_workspace_bytes": ([_i64], _i64),
+    "dm_train_opt_step": ([_p] * 6 + [_i64, _p, _p, _i64, _p], None),
     "dm_math_probe": ([_i, _i, _i, _i, _p, _p, _p], None),
     "dm_wave_probe": ([_i, _i, _i, _i, _i, _p, _p, _p], None),
 }

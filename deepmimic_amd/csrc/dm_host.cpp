@@ -1464,7 +1464,8 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_amp_rewards.h"   // AMP batch rewards, reward statistics, running value bounds and the value clip (after dm_policy_host.h: the head's expressions; dm_ppo_batch.h: fold_groups)
 #include "dm_train.h"         // PPO actor / critic minibatch gradients and the momentum step on a live policy context (after dm_policy_host.h and dm_ppo_batch.h: its tree)
 #include "dm_train_gated.h"   // the same updates for the gated nets of the AMP task agents (after dm_train.h: its head, fold and gradient kernels)
-#include "dm_time_warp.h"     // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
+#include "dm_optim.h"         // Adam, global-norm clipping and the non-finite guard: one optimiser step for every trainer (after dm_train_gated.h: the layouts, train_refresh)
+#include "dm_time_warp.h"    // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs
 
 // test support: one wave-level primitive of dm_device.h / dm_device_duo.h per launch.  The kernel (dm_wave_probe.h) is compiled into the object of DM_MISC_FAMILY, which

@@ -723,9 +723,23 @@ static int train_step_ok(const char* fn, const float* params_dev, const float* m
     return 0;
 }
 
+// The masters of a block into its context -- dm_policy_set_weights with DM_DEVICE_PTRS on views of params at the offsets o of the block's 2 NMAT arrays, the gate's
+// included: "packed weights = RNE bf16 of the masters" stays true for every array.  What every optimiser step ends with (train_sgd below, dm_optim.h).
+template <int NMAT>
+static int train_refresh(dm_policy* net, const long long* o, const float* params, rt_stream stream) {
+    const dmp::PolicyDev& d = net->pd;
+    dm_policy_params pp; memset(&pp, 0, sizeof(pp));
+    pp.state_dim = d.S; pp.hidden1 = d.H1; pp.hidden2 = d.H2; pp.action_dim = d.A;
+    dm_policy_gate_params gp; memset(&gp, 0, sizeof(gp));
+    if (net->gated) { gp.goal_dim = net->gd.G; gp.gate_common = net->gd.GC; gp.gate_hidden = net->gd.GH; }
+    const float** const arr[dmt::GATED_ARRAYS] = {&pp.w1, &pp.b1, &pp.w2, &pp.b2, &pp.w3, &pp.b3, &gp.gc_w, &gp.gc_b, &gp.g0_w, &gp.g0_b, &gp.g0_bias_w, &gp.g0_bias_b, &gp.g0_scale_w, &gp.g0_scale_b,
+                                                  &gp.g1_w, &gp.g1_b, &gp.g1_bias_w, &gp.g1_bias_b, &gp.g1_scale_w, &gp.g1_scale_b};
+    for (int k = 0; k < 2 * NMAT; ++k) *arr[k] = params + o[k];
+    return policy_pack(net, pp, net->gated ? &gp : nullptr, DM_DEVICE_PTRS, stream);
+}
+
 // What the plain and the gated step share behind their checks.  o: the offsets of the block's 2 NMAT arrays (a layout's o: array 2 k a matrix, under the weight decay,
-// 2 k + 1 its bias vector); null with no context: no matrix, the step alone.  k_train_sgd<NMAT>, then the new masters into the context -- dm_policy_set_weights with
-// DM_DEVICE_PTRS on views of params, the gate's arrays included: "packed weights = RNE bf16 of the masters" stays true for every array
+// 2 k + 1 its bias vector); null with no context: no matrix, the step alone.  k_train_sgd<NMAT>, then train_refresh
 template <int NMAT>
 static int train_sgd(dm_policy* net, const long long* o, float* params, float* momentum_dev, const float* grads, int64_t P, double stepsize, double momentum,
                      double weight_decay, double grad_scale, void* hip_stream) {
@@ -741,15 +755,7 @@ static int train_sgd(dm_policy* net, const long long* o, float* params, float* m
     DevGuard guard(net->device_id);
     RT_LAUNCH4(dmt::k_train_sgd<NMAT>, a.blocks, stream, a);
     if (launch_status(0)) return -1;
-    const dmp::PolicyDev& d = net->pd;
-    dm_policy_params pp; memset(&pp, 0, sizeof(pp));
-    pp.state_dim = d.S; pp.hidden1 = d.H1; pp.hidden2 = d.H2; pp.action_dim = d.A;
-    dm_policy_gate_params gp; memset(&gp, 0, sizeof(gp));
-    if (net->gated) { gp.goal_dim = net->gd.G; gp.gate_common = net->gd.GC; gp.gate_hidden = net->gd.GH; }
-    const float** const arr[dmt::GATED_ARRAYS] = {&pp.w1, &pp.b1, &pp.w2, &pp.b2, &pp.w3, &pp.b3, &gp.gc_w, &gp.gc_b, &gp.g0_w, &gp.g0_b, &gp.g0_bias_w, &gp.g0_bias_b, &gp.g0_scale_w, &gp.g0_scale_b,
-                                                  &gp.g1_w, &gp.g1_b, &gp.g1_bias_w, &gp.g1_bias_b, &gp.g1_scale_w, &gp.g1_scale_b};
-    for (int k = 0; k < 2 * NMAT; ++k) *arr[k] = params + o[k];
-    return policy_pack(net, pp, net->gated ? &gp : nullptr, DM_DEVICE_PTRS, stream);
+    return train_refresh<NMAT>(net, o, params, stream);
 }
 
 // what dm_train_read_activations and dm_train_gated_read share behind the check of the net: array `which` of `count` = {source, bytes per row}; `names`: what `which` may be

@@ -7,7 +7,12 @@ three-layer nets, on the `Policy` context that samples -- the forward pass runs 
     all_reduce_gradients(tr)                                                         # (deepmimic_amd/dist.py, several ranks)
     tr.step(grad_scale=1.0 / world)                                                  # momentum SGD on the fp32 masters, then the refresh of the context
 
-A checkpoint is `torch.save(tr.buf)`.  Adam, a fused training kernel and step-size schedules are out of scope.
+A checkpoint is `torch.save(tr.buf)`.  A fused training kernel is out of scope.
+
+Every trainer takes `optimizer="adam"`, `betas`, `eps`, `max_grad_norm` and `skip_nonfinite` (`dm_train_opt_step`, deepmimic_amd/csrc/dm_optim.h): Adam on the fp32
+masters, global-norm clipping of the (all-reduced, scaled) gradient and a step that is skipped when a gradient element is not finite, all decided on the device --
+`tr.grad_norm()`, `tr.grad_scale_applied()`, `tr.skipped()` are views of `tr.opt_state`, the [8] float64 device tensor, and the checkpoint is then `tr.buf` ([4, P] with
+Adam: row 3 is v) plus `tr.opt_state`.  With the defaults nothing changes: the old entry points, buf [3, P].  A step-size schedule is assigning `tr.stepsize`.
 
 The gated nets of the AMP task agents (fc_2layers_gated_1024units as ActorNet and CriticNet; `dm_train_gated_*`, deepmimic_amd/csrc/dm_train_gated.h) have trainers of
 their own with the same surface, `GatedActorTrainer` / `GatedCriticTrainer`, on a gated `Policy` or on the context inside a gated `heads.Critic`
@@ -153,6 +158,49 @@ def sgd_step_device(policy, params_ptr: int, momentum_ptr: int, grads_ptr: int, 
                                      float(weight_decay), float(grad_scale), vp(stream)))
 
 
+# ---- Adam, global-norm clipping and the non-finite guard (dm_train_opt_step, deepmimic_amd/csrc/dm_optim.h)
+
+class _OptCfg(C.Structure):
+    _fields_ = [("kind", C.c_int32), ("skip_nonfinite", C.c_int32), ("stepsize", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+                ("weight_decay", C.c_double), ("grad_scale", C.c_double), ("max_grad_norm", C.c_double)]
+
+
+OPT_KINDS = {"momentum": 0, "adam": 1}                      # DM_OPT_MOMENTUM, DM_OPT_ADAM
+OPT_STATE = ("t", "pow1", "pow2", "skipped", "norm", "scale", "nonfinite", "reserved")          # the eight words of state_dev
+OPT_CHUNK, OPT_THREADS = 1024, 256                          # elements per partial of the norm pass, threads per workgroup
+
+
+def opt_workspace_layout(P: int) -> dict:
+    """{name: (byte offset, dtype, shape)} of what dm_train_opt_step leaves in its workspace: the control record, then the norm pass's partials -- group b owns the
+    elements [OPT_CHUNK b, OPT_CHUNK (b + 1)), thread t of it the elements OPT_CHUNK b + t + OPT_THREADS k; "groups": their number; "bytes": the total"""
+    G = (int(P) + OPT_CHUNK - 1) // OPT_CHUNK
+    ctrl = np.dtype([("skip", np.int32), ("s", np.float32), ("alpha", np.float64), ("ic2", np.float64), ("pad", np.float64)])
+    return dict(ctrl=(0, ctrl, (1,)), sum=(32, np.float64, (G,)), count=(32 + 8 * G, np.float64, (G,)), groups=G, bytes=32 + 16 * G)
+
+
+def opt_workspace_bytes(P: int, lib) -> int:
+    if not hasattr(lib, "dm_train_opt_workspace_bytes"):
+        raise RuntimeError("libdm_hip: this library has no dm_train_opt_workspace_bytes (rebuild it)")
+    v = lib.dm_train_opt_workspace_bytes(int(P))
+    check(lib, v < 0)
+    return int(v)
+
+
+def opt_step_device(policy, params_ptr: int, m_ptr: int, v_ptr: int, grads_ptr: int, P: int, state_ptr: int, workspace_ptr: int, workspace_nbytes: int, stepsize: float,
+                    kind: str = "adam", beta1: float = 0.9, beta2: float = 0.999, eps: float = 1e-8, weight_decay: float = 0.0, grad_scale: float = 1.0,
+                    max_grad_norm=None, skip_nonfinite: bool = False, stream: int = 0, lib=None):
+    """raw device pointers (ints).  kind "momentum" (beta1 is the momentum, v_ptr may be 0) or "adam"; max_grad_norm None: no clipping; state_ptr: double[8], zero
+    before the first step.  policy None: the step alone (pass `lib`); with a policy -- plain, gated or a discriminator's -- its context is refreshed from the masters"""
+    lib = policy.lib if policy is not None else lib
+    if not hasattr(lib, "dm_train_opt_step"):
+        raise RuntimeError("libdm_hip: this library has no dm_train_opt_step (rebuild it)")
+    k = OPT_KINDS.get(kind, kind)
+    cfg = _OptCfg(int(k) if isinstance(k, (int, np.integer)) else -1, 1 if skip_nonfinite else 0, float(stepsize), float(beta1), float(beta2), float(eps),
+                  float(weight_decay), float(grad_scale), 0.0 if max_grad_norm is None else float(max_grad_norm))
+    check(lib, lib.dm_train_opt_step(policy.h if policy is not None else None, C.cast(C.pointer(cfg), C.c_void_p), vp(params_ptr), vp(m_ptr), vp(v_ptr), vp(grads_ptr),
+                                     int(P), vp(state_ptr), vp(workspace_ptr), int(workspace_nbytes), vp(stream)))
+
+
 def read_activations(policy, which: str, n: int) -> np.ndarray:
     """test support: the first n rows of "s16" [n, K1], "h1" or "h2" as the last call left them, bf16 bits (uint16); synchronises"""
     _need(policy, "dm_train_read_activations")
@@ -165,8 +213,8 @@ def read_activations(policy, which: str, n: int) -> np.ndarray:
 # ---- the trainers
 
 class _Trainer:
-    """Owns buf [3, P] float32 = (params, momentum, grads) and the workspace, on `device` (the policy's GPU; "cpu" with the emulator build of the tests, where device
-    memory is host memory).  Every call runs on torch's current stream."""
+    """Owns buf [3, P] float32 = (params, momentum, grads) -- with optimizer="adam" [4, P]: (params, m, grads, v) -- and the workspace, on `device` (the policy's GPU;
+    "cpu" with the emulator build of the tests, where device memory is host memory).  Every call runs on torch's current stream."""
     N_STATS = 0
     GATED = False
     # what a trainer of another kind of net replaces: the block's length, packing and views, the workspace's size and the step
@@ -176,27 +224,44 @@ class _Trainer:
     _workspace_bytes = staticmethod(workspace_bytes)
     _step = staticmethod(sgd_step_device)
 
-    def __init__(self, policy, buf, stepsize: float, momentum: float, weight_decay: float):
+    def __init__(self, policy, buf, stepsize: float, momentum: float, weight_decay: float, optimizer: str = "momentum", betas=(0.9, 0.999), eps: float = 1e-8,
+                 max_grad_norm=None, skip_nonfinite: bool = False):
+        """With the defaults the step is dm_train_sgd_step / dm_train_gated_sgd_step and buf is [3, P].  optimizer "adam" (buf [4, P]: row 1 is m, row 3 is v),
+        max_grad_norm (global-norm clipping of the scaled gradient) or skip_nonfinite (no step when a gradient element is NaN or +-inf) take the step through
+        dm_train_opt_step, which keeps its decisions in `opt_state`, the [8] float64 device tensor (OPT_STATE); a checkpoint is then buf plus opt_state.  `stepsize`
+        stays a plain attribute: a schedule is the caller assigning it between steps."""
         import torch
         _need(policy, "dm_train_gated_actor_grad" if self.GATED else "dm_train_actor_grad")
+        if optimizer not in OPT_KINDS:
+            raise ValueError("optimizer must be \"momentum\" or \"adam\"")
         self.policy, self.buf = policy, buf
         self.P = self._param_count(policy)
-        tensor_arg("buf", buf, buf.device, torch.float32, [(3, self.P)])
+        self.optimizer = optimizer
+        rows = 4 if optimizer == "adam" else 3
+        tensor_arg("buf", buf, buf.device, torch.float32, [(rows, self.P)])
         self.device = buf.device
         self.params, self.momentum, self.grads = buf[0], buf[1], buf[2]
+        self.second_moment = buf[3] if rows == 4 else None
         self.stepsize, self.mom, self.weight_decay = float(stepsize), float(momentum), float(weight_decay)
+        self.betas, self.eps, self.max_grad_norm, self.skip_nonfinite = (float(betas[0]), float(betas[1])), float(eps), max_grad_norm, bool(skip_nonfinite)
         self._stats = torch.zeros(self.N_STATS, dtype=torch.float64, device=self.device)
         self._work, self._work_bytes, self._work_key = None, 0, None
+        self.opt_state = None
+        if optimizer != "momentum" or max_grad_norm is not None or skip_nonfinite:
+            _need(policy, "dm_train_opt_step")
+            self.opt_state = torch.zeros(len(OPT_STATE), dtype=torch.float64, device=self.device)
+            self._opt_bytes = opt_workspace_bytes(self.P, policy.lib)
+            self._opt_work = torch.zeros((self._opt_bytes + 15) // 16 * 2, dtype=torch.float64, device=self.device)
 
     @classmethod
-    def from_policy(cls, policy, weights: dict, stepsize: float, momentum: float = 0.9, weight_decay: float = 0.0, device=None):
-        """masters from the weights dict the policy was built from (zero momentum), then `sync()`"""
+    def from_policy(cls, policy, weights: dict, stepsize: float, momentum: float = 0.9, weight_decay: float = 0.0, device=None, optimizer: str = "momentum", **opt):
+        """masters from the weights dict the policy was built from (zero momentum), then `sync()`.  opt: betas, eps, max_grad_norm, skip_nonfinite of __init__"""
         import torch
         dev = torch.device("cuda", policy.device_id) if device is None else torch.device(device)
         flat = cls._pack(weights)
-        buf = torch.zeros((3, flat.size), dtype=torch.float32, device=dev)
+        buf = torch.zeros((4 if optimizer == "adam" else 3, flat.size), dtype=torch.float32, device=dev)
         buf[0].copy_(torch.from_numpy(flat))
-        tr = cls(policy, buf, stepsize, momentum, weight_decay)
+        tr = cls(policy, buf, stepsize, momentum, weight_decay, optimizer=optimizer, **opt)
         tr.sync()
         return tr
 
@@ -232,8 +297,30 @@ class _Trainer:
         return n, G
 
     def step(self, grad_scale: float = 1.0):
-        self._step(self.policy, self.params.data_ptr(), self.momentum.data_ptr(), self.grads.data_ptr(), self.P, self.stepsize, self.mom, self.weight_decay,
-                   grad_scale, stream=self._stream())
+        if self.opt_state is None:
+            return self._step(self.policy, self.params.data_ptr(), self.momentum.data_ptr(), self.grads.data_ptr(), self.P, self.stepsize, self.mom, self.weight_decay,
+                              grad_scale, stream=self._stream())
+        adam = self.optimizer == "adam"
+        opt_step_device(self.policy, self.params.data_ptr(), self.momentum.data_ptr(), self.second_moment.data_ptr() if adam else 0, self.grads.data_ptr(), self.P,
+                        self.opt_state.data_ptr(), self._opt_work.data_ptr(), self._opt_bytes, self.stepsize, self.optimizer, self.betas[0] if adam else self.mom,
+                        self.betas[1], self.eps, self.weight_decay, grad_scale, self.max_grad_norm, self.skip_nonfinite, stream=self._stream())
+
+    def _opt_word(self, name: str):
+        if self.opt_state is None:
+            raise RuntimeError("this trainer keeps no optimiser state: the default momentum step measures nothing (max_grad_norm, skip_nonfinite or optimizer=\"adam\")")
+        return self.opt_state[OPT_STATE.index(name)]
+
+    def grad_norm(self):
+        """|grad_scale| |grads| of the last step, a 0-dim float64 device view of opt_state (no synchronisation); 0 when neither clipping nor the guard is on"""
+        return self._opt_word("norm")
+
+    def grad_scale_applied(self):
+        """the clipping factor min(1, max_grad_norm / (norm + 1e-6)) of the last step, a device view"""
+        return self._opt_word("scale")
+
+    def skipped(self):
+        """the number of steps the non-finite guard has skipped, a device view"""
+        return self._opt_word("skipped")
 
     def stats(self):
         """the statistics of the last grad call, a float64 device tensor (no synchronisation here)"""
@@ -607,6 +694,105 @@ def reference_step(params, momentum, grads, stepsize, mom, weight_decay=0.0, gra
     if exact:
         return fma32(f(-lr), vv, w), vv
     return (w64 - lr * vv.astype(np.float64)).astype(f), vv
+
+
+def _tree_fold(x: np.ndarray) -> np.ndarray:
+    """dmb::block_sum over the last axis (OPT_THREADS entries): x[t] += x[t + w], w = 128 .. 1"""
+    x = np.array(x, np.float64)
+    w = x.shape[-1] // 2
+    while w >= 1:
+        x[..., :w] = x[..., :w] + x[..., w:2 * w]
+        w //= 2
+    return x[..., 0]
+
+
+def reference_grad_norm(grads, partition: Optional[dict] = None, grad_scale: float = 1.0):
+    """k_opt_sq and the fold of k_opt_begin in their own order (partition: opt_workspace_layout(P), the default): thread t of group b adds the squares of its elements
+    OPT_CHUNK b + t + OPT_THREADS k in float64, k ascending, the threads by the tree, the groups by contiguous runs per thread and the tree.
+    Returns (sum, count of non-finite elements, norm = |grad_scale| sqrt(sum), the groups' (sums, counts))."""
+    g = np.asarray(grads, np.float32).reshape(-1)
+    G = (opt_workspace_layout(g.size) if partition is None else partition)["groups"]
+    pad = np.zeros(G * OPT_CHUNK, np.float32); pad[:g.size] = g                       # (an element past P adds + 0.0: the sum keeps its bits)
+    x = pad.reshape(G, OPT_CHUNK // OPT_THREADS, OPT_THREADS)
+    with np.errstate(invalid="ignore", over="ignore"):
+        s, bad = np.zeros((G, OPT_THREADS)), np.zeros((G, OPT_THREADS))
+        for k in range(x.shape[1]):
+            d = x[:, k].astype(np.float64)
+            s = s + d * d
+            bad = bad + ~np.isfinite(x[:, k])
+        gs, gc = _tree_fold(s), _tree_fold(bad)
+        per = (G + OPT_THREADS - 1) // OPT_THREADS
+        def fold(part):
+            runs = np.zeros(per * OPT_THREADS); runs[:G] = part
+            t = np.zeros(OPT_THREADS)
+            for k in range(per):
+                t = t + runs.reshape(OPT_THREADS, per)[:, k]
+            return float(_tree_fold(t))
+        total, count = fold(gs), fold(gc)
+        return total, count, float(abs(np.float64(grad_scale)) * np.sqrt(np.float64(total))), (gs, gc)
+
+
+def reference_opt_begin(state, cfg: dict, total: float, count: float):
+    """k_opt_begin: (the new state float64[8], dict(skip, s float32, alpha, ic2)).  cfg: kind, stepsize, beta1, beta2, grad_scale and optionally max_grad_norm,
+    skip_nonfinite; total / count: of reference_grad_norm -- 0, 0 when neither clipping nor the guard is on (the norm pass does not run)"""
+    d, f = np.float64, np.float32
+    st = np.array(state, d)
+    mx = cfg.get("max_grad_norm")
+    clip = mx is not None and mx > 0 and np.isfinite(mx)
+    guard = bool(cfg.get("skip_nonfinite"))
+    if not (clip or guard):
+        total, count = 0.0, 0.0
+    B1, B2, gsc = d(f(cfg["beta1"])), d(f(cfg.get("beta2", 0.999))), d(cfg.get("grad_scale", 1.0))
+    adam = OPT_KINDS.get(cfg["kind"], cfg["kind"]) == 1
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore"):
+        norm = abs(gsc) * np.sqrt(d(total))
+        scale = d(1.0)
+        if clip:
+            q = d(mx) / (norm + d(1e-6))
+            scale = q if (q < 1.0 or q != q) else d(1.0)
+        skip = guard and count > 0
+        t = st[0]
+        p1, p2 = (d(1.0), d(1.0)) if t == 0 else (st[1], st[2])
+        if skip:
+            st[3] += 1.0
+        else:
+            t = t + 1.0; p1 = p1 * B1; p2 = p2 * B2
+            st[0], st[1], st[2] = t, p1, p2
+        st[4], st[5], st[6] = norm, scale, count
+        ctrl = dict(skip=bool(skip), s=f(gsc * scale), alpha=d(cfg["stepsize"]) / (d(1.0) - p1) if adam else d(0.0), ic2=d(1.0) / (d(1.0) - p2) if adam else d(0.0))
+    return st, ctrl
+
+
+def reference_adam_step(params, m, v, grads, s, alpha, ic2, beta1, beta2, eps, weight_decay=0.0, matrix_mask=None):
+    """k_opt_step<ADAM> per element, every written operation one float64 rounding, m', v', w' rounded once to float32: g = s grad (+ wd w on matrix_mask),
+    m' = B1 m + (1 - B1) g, v' = B2 v + ((1 - B2) g) g, w' = w - (alpha m') / (sqrt(v' ic2) + eps) with the stored m', v'.  Returns (params, m, v)."""
+    d, f = np.float64, np.float32
+    w, m, v, g = (np.asarray(a, f) for a in (params, m, v, grads))
+    mask = np.zeros(w.shape, bool) if matrix_mask is None else np.asarray(matrix_mask, bool)
+    B1, B2, wd, e = (d(f(x)) for x in (beta1, beta2, weight_decay, eps))
+    with np.errstate(invalid="ignore", over="ignore", divide="ignore", under="ignore"):
+        w64 = w.astype(d)
+        gg = d(f(s)) * g.astype(d)
+        gg = np.where(mask, gg + wd * w64, gg)
+        m1 = (B1 * m.astype(d) + (d(1.0) - B1) * gg).astype(f)
+        v1 = (B2 * v.astype(d) + (d(1.0) - B2) * gg * gg).astype(f)
+        w1 = (w64 - d(alpha) * m1.astype(d) / (np.sqrt(v1.astype(d) * d(ic2)) + e)).astype(f)
+    return w1, m1, v1
+
+
+def reference_opt_step(state, cfg: dict, params, m, v, grads, matrix_mask=None):
+    """one whole dm_train_opt_step from the three mirrors and reference_step: (params, m, v, state); v passes through with kind "momentum" (None allowed)"""
+    total, count, _, _ = reference_grad_norm(grads, grad_scale=cfg.get("grad_scale", 1.0))
+    st, c = reference_opt_begin(state, cfg, total, count)
+    f = np.float32
+    if c["skip"]:
+        return np.asarray(params, f).copy(), np.asarray(m, f).copy(), None if v is None else np.asarray(v, f).copy(), st
+    wd = cfg.get("weight_decay", 0.0)
+    if OPT_KINDS.get(cfg["kind"], cfg["kind"]) == 1:
+        return reference_adam_step(params, m, v, grads, c["s"], c["alpha"], c["ic2"], cfg["beta1"], cfg.get("beta2", 0.999), cfg.get("eps", 1e-8), wd, matrix_mask) + (st,)
+    with np.errstate(invalid="ignore", over="ignore"):
+        w1, m1 = reference_step(params, m, grads, cfg["stepsize"], cfg["beta1"], wd, c["s"], matrix_mask)
+    return w1, m1, None if v is None else np.asarray(v, f).copy(), st
 
 
 def matrix_mask_of(S: int, H1: int, H2: int, A: int) -> np.ndarray:

@@ -766,7 +766,8 @@ int dm_time_warp_align(int device_id, int n_envs, int capacity, int dim, int f64
  * and names its reason through dm_last_error.  The one object is the dm_policy whose net is trained: its packed bf16 weights and its activation buffers s16 / h1 / h2 are
  * read and written; the buffers grow to the largest n as in dm_policy_forward_ex (the one allocation).  ORDERING: like dm_policy_set_weights, a training call must not
  * run while another stream runs a forward, a scalar evaluation, a refresh or another training call of the same context -- order them with events or use one stream.
- * Out of scope: Adam, one fused training kernel, step-size schedules (the step size is an argument).  The AMP discriminator update is dm_train_disc_grad below; gated
+ * Out of scope: one fused training kernel (Adam, gradient clipping and the non-finite guard: dm_train_opt_step below; a step-size schedule is the caller passing
+ * another step size, an argument of every step).  The AMP discriminator update is dm_train_disc_grad below; gated
  * contexts have entry points of their own, dm_train_gated_* further below, and these calls refuse them.
  *
  * Parameter block: P = dm_train_param_count(net) floats in the order w1 [S x H1], b1, w2 [H1 x H2], b2, w3 [H2 x A], b3; matrices in tf.layers.dense layout (in x out,
@@ -903,6 +904,49 @@ int dm_train_gated_value_grad(dm_policy* net, const float* params_dev, const flo
 int dm_train_gated_sgd_step(dm_policy* net, float* params_dev, float* momentum_dev, const float* grads_dev, int64_t P, double stepsize, double momentum,
                             double weight_decay, double grad_scale, void* hip_stream);
 int dm_train_gated_read(dm_policy* net, int which, int n, void* host_out, size_t capacity);
+
+/* ---- Adam, global-norm gradient clipping and a non-finite guard for the device trainers (deepmimic_amd/csrc/dm_optim.h, deepmimic_amd/train.py): ONE optimiser step for
+ * plain, gated and discriminator contexts beside dm_train_sgd_step / dm_train_gated_sgd_step, which stay as they are.  The rules of the sections above hold: DEVICE
+ * pointers, asynchronous on hip_stream, nothing read on the host or synchronised, a refused call launches and writes nothing and names its reason, the ORDERING rule.  With
+ * a net (plain: the block of dm_train_param_count, weight decay on its three matrices; gated: dm_train_gated_param_count, on its ten) the context is refreshed from the
+ * masters as those steps refresh it, gate included, after a skipped step too (the same bytes again); net NULL: the step alone on the current device, weight_decay 0.
+ *
+ * cfg: kind DM_OPT_MOMENTUM (beta1 is the momentum; beta2 and eps are not used, v_dev may be NULL) or DM_OPT_ADAM; max_grad_norm <= 0 or +inf: no clipping;
+ * skip_nonfinite != 0: the guard.  Below B1 = (double)(float)beta1, likewise B2, wd, eps; stepsize, grad_scale and max_grad_norm enter as the doubles they are.
+ * state_dev double[8], the caller's, ZERO before the first step, a checkpoint together with the arrays:
+ *   [0] t, the steps taken (an exact integer)   [1] B1^t   [2] B2^t (running fp64 products; t = 0 reads both as 1 whatever the words hold)   [3] the steps skipped
+ *   [4] the last norm   [5] the last scale   [6] the last number of non-finite gradient elements   [7] reserved
+ * Arithmetic (the specification; reference_grad_norm / reference_opt_begin / reference_adam_step / reference_step of deepmimic_amd/train.py state it in numpy), every
+ * written operation rounded once in fp64, no product contracted into a sum:
+ *   norm pass  only with clipping or the guard.  Group b of G = ceil(P / 1024) owns the elements from 1024 b; its thread t adds g_i^2 (exact in fp64) for
+ *              i = 1024 b + t + 256 k, k = 0 .. 3, in that order and counts its elements that are NaN or +-inf; the 256 threads by the tree x[t] += x[t + w],
+ *              w = 128 .. 1; the G partials by contiguous runs of ceil(G / 256) per thread, each in order, and the same tree.  Two calls give the same bytes.
+ *   decisions  norm = |grad_scale| sqrt(sum);  scale = min(1, max_grad_norm / (norm + 1e-6)) with clipping (torch.nn.utils.clip_grad_norm_'s rule; a NaN quotient
+ *              stays NaN, as np.minimum keeps it), else 1;  skip = guard and count > 0.  Without the norm pass sum = count = 0 and words 4 and 6 are written as 0.
+ *              Unless skip: t += 1, and the two powers are multiplied by B1 and B2 (MOMENTUM keeps them alike; B2 feeds nothing else there).  With skip: word 3 += 1,
+ *              words 0 to 2 and every array keep their bytes.  s = (float)(grad_scale scale);  ADAM: alpha_t = stepsize / (1 - B1^t), ic2 = 1 / (1 - B2^t).
+ *   step       per element g = (double)s (double)grad; on matrix entries g += wd w (L2 added to the gradient, as the momentum step and torch.optim.Adam do it; biases
+ *              exempt).  MOMENTUM: the step of dm_train_sgd_step with s in place of (float)grad_scale -- with no clipping and no guard the same bytes.
+ *              ADAM: m' = (float)(B1 m + (1 - B1) g);  v' = (float)(B2 v + ((1 - B2) g) g);  w' = (float)(w - (alpha_t m') / (sqrt(v' ic2) + eps)) with the stored
+ *              m' and v'; sqrt and the division correctly rounded.  Device and emulator round alike.
+ *   A non-finite gradient element with the guard off spreads as this arithmetic says: an infinite norm gives scale 0 and 0 inf = NaN in that element, a NaN norm
+ *   gives s = NaN and every element NaN.
+ * Workspace (dm_train_opt_workspace_bytes(P) = 32 + 16 G bytes, 16-byte aligned), left behind: [control record {int32 skip, float s, double alpha_t, double ic2}, padded
+ *   to 32 bytes][G doubles: the groups' sums][G doubles: their counts].
+ * Refused: a NULL cfg, params, m, grads, state or workspace; an unknown kind; ADAM without v_dev, with (float)beta1 or (float)beta2 outside [0, 1) or (float)eps not
+ * finite and > 0; MOMENTUM with a negative or non-finite beta1; stepsize or weight_decay negative or non-finite; a non-finite grad_scale; a NaN max_grad_norm; P < 1
+ * or > 2^40 or, with a net, P != its parameter count; weight_decay != 0 without a net; a state that is not 8-byte aligned; a workspace that is too small or not
+ * 16-byte aligned. */
+enum { DM_OPT_MOMENTUM = 0, DM_OPT_ADAM = 1 };
+typedef struct dm_train_opt_cfg {
+    int32_t kind, skip_nonfinite;
+    double stepsize, beta1 /* MOMENTUM: the momentum */, beta2, eps, weight_decay, grad_scale;
+    double max_grad_norm;            /* <= 0 or +inf: no clipping */
+} dm_train_opt_cfg;
+int64_t dm_train_opt_workspace_bytes(int64_t P);      /* < 0: refused (dm_last_error) */
+int dm_train_opt_step(dm_policy* net /* NULL: the step alone, weight_decay must be 0 */, const dm_train_opt_cfg* cfg, float* params_dev, float* m_dev,
+                      float* v_dev /* ADAM only, else NULL */, const float* grads_dev, int64_t P,
+                      double* state_dev /* [8], 8-byte aligned, caller-owned, zero before the first step */, void* workspace, int64_t workspace_bytes, void* hip_stream);
 
 /* ---- a probe for the device math helpers(deepmimic_amd/csrc/dm_math.h, dm_math_probe.h): TEST SUPPORT, nothing of the product calls it.  One launch evaluates the
  * helper `op` on n independent rows, one lane per row: row i reads in_dev[i * DM_MATH_PROBE_IN ..] and writes out_dev[i * DM_MATH_PROBE_OUT ..], doubles both, DEVICE
