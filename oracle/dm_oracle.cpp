@@ -170,6 +170,13 @@ int orc_dbg_num_rows(void* h) { return ((Scene*)h)->dbg_num_rows; }
 int orc_dbg_num_contacts(void* h) { return (int)((Scene*)h)->dbg_contacts.size(); }
 // out: n x 9 doubles (link, link_b, dist, x3, n3)
 void orc_dbg_contacts(void* h, double* out) { const auto& cs = ((Scene*)h)->dbg_contacts; for (size_t i = 0; i < cs.size(); ++i) { double* o = out + 9 * i; o[0] = cs[i].link; o[1] = cs[i].link_b; o[2] = (double)cs[i].dist; o[3] = (double)cs[i].x.x; o[4] = (double)cs[i].x.y; o[5] = (double)cs[i].x.z; o[6] = (double)cs[i].n.x; o[7] = (double)cs[i].n.y; o[8] = (double)cs[i].n.z; } }
+// out: n x 10 doubles: the nine columns above, then ContactPt::ball (0: link vs ground / link vs link, 1: body b is the ball, 2: body a is the ball, link = -1)
+void orc_dbg_contacts_ex(void* h, double* out) {
+    const auto& cs = ((Scene*)h)->dbg_contacts;
+    for (size_t i = 0; i < cs.size(); ++i) { double* o = out + 10 * i; o[0] = cs[i].link; o[1] = cs[i].link_b; o[2] = (double)cs[i].dist; o[3] = (double)cs[i].x.x; o[4] = (double)cs[i].x.y; o[5] = (double)cs[i].x.z; o[6] = (double)cs[i].n.x; o[7] = (double)cs[i].n.y; o[8] = (double)cs[i].n.z; o[9] = cs[i].ball; }
+}
+// the impulses of the last substep in row order (limit rows, normals, friction pairs contact-major): orc_dbg_num_rows doubles
+void orc_dbg_lambda(void* h, double* out) { const Vec& l = ((Scene*)h)->dbg_lambda; for (size_t i = 0; i < l.size(); ++i) out[i] = (double)l[i]; }
 int orc_dbg_num_self_contacts(void* h) { int n = 0; for (const auto& c : ((Scene*)h)->dbg_contacts) n += c.link_b >= 0; return n; }
 
 // ---- component taps (used by the known-answer and component parity tests) ----

@@ -140,7 +140,7 @@ struct Scene {
     std::vector<int> in_contact;         // per link: ground contact within contact_report_dist
     std::vector<LinkState> links;
     // debug taps for component-level parity tests
-    std::vector<ContactPt> dbg_contacts; int dbg_num_rows = 0; Vec dbg_vstar;
+    std::vector<ContactPt> dbg_contacts; int dbg_num_rows = 0; Vec dbg_vstar; Vec dbg_lambda;   // dbg_lambda: the impulses of the last substep, in row order
     // physics 2: per link the cached manifold points -- the point on the link in body coordinates, the point on the plane (x, z)
     struct ManifoldPt { V3 lp; real bx, bz; real dist; };
     std::vector<std::vector<ManifoldPt>> manifolds;
@@ -637,6 +637,7 @@ struct Scene {
                 row.lam = nl;
             }
         }
+        dbg_lambda.assign(R, 0); for (int r = 0; r < R; ++r) dbg_lambda[r] = rows[r].lam;
         Vec vnew = vstar;
         for (int r = 0; r < R; ++r) for (int i = 0; i < P; ++i) vnew[i] += rows[r].W[i] * rows[r].lam;
         clamp_coord_vel(vnew);

@@ -275,6 +275,19 @@ class Oracle:
         self.lib.orc_dbg_contacts(self.h, _d(out))
         return out[:n]
 
+    def contact_list_ex(self):
+        """contact_list() plus ContactPt::ball as column 9 (0: no ball, 1: body b is the ball, 2: ball vs ground, link = -1)"""
+        n = self.num_contacts()
+        out = np.zeros((max(n, 1), 10))
+        self.lib.orc_dbg_contacts_ex(self.h, _d(out))
+        return out[:n]
+
+    def lambdas(self):
+        """the impulses of the last substep in row order: limit rows, normals, friction pairs contact-major"""
+        out = np.zeros(max(self.num_rows(), 1))
+        self.lib.orc_dbg_lambda(self.h, _d(out))
+        return out[:self.num_rows()]
+
     def num_self_contacts(self):
         return int(self.lib.orc_dbg_num_self_contacts(self.h))
 
