@@ -569,10 +569,28 @@ class BatchEnv:
     def debug(self, name: str):
         shapes = {"H": (self.N, self.D, self.D), "C": (self.N, self.D), "vstar": (self.N, self.D), "lambda": (self.N, 64),
                   "rows": (self.N, 2), "tau": (self.N, self.D), "kin_pose": (self.N, self.P), "kin_vel": (self.N, self.P),
-                  "reward_terms": (self.N, 5), "links": (self.N, self.J, 21), "prof": (self.N, 16), "fallback": (self.N,), "borrowed": (self.N,),
+                  "reward_terms": (self.N, 5), "links": (self.N, self.J, 21), "contacts": (self.N, self.max_contacts, 8), "prof": (self.N, 16), "fallback": (self.N,), "borrowed": (self.N,),
                   "family": (self.N,)}
         out = np.zeros(shapes[name])
         self._chk(self.lib.dm_get_debug(self.h, name.encode(), _dp(out)))
+        return out
+
+    def contacts(self):
+        """The contact slots of the last tapped substep (taps "contacts" + "rows"), per env an n x 10 array in the columns of the oracle's contact list:
+        link a, link b, dist, x(3), n(3), kind.  Ground contact: b = -1, kind 0; self contact: a < b, kind 0, n from b to a; link against the free body:
+        b = -1, kind 1; the free body on the ground: a = b = -1, kind 2."""
+        raw, rows = self.debug("contacts"), self.debug("rows")
+        out = []
+        for e in range(self.N):
+            n = int(rows[e, 1])
+            c = np.zeros((n, 10))
+            for k in range(n):
+                code = int(raw[e, k, 7]); la, lb = code & 0xff, code >> 8
+                kind = 2 if la == 254 else (1 if lb == 254 else 0)
+                c[k, 0] = -1 if la == 254 else la
+                c[k, 1] = lb if lb < 254 else -1
+                c[k, 2] = raw[e, k, 6]; c[k, 3:6] = raw[e, k, 0:3]; c[k, 6:9] = raw[e, k, 3:6]; c[k, 9] = kind
+            out.append(c)
         return out
 
 

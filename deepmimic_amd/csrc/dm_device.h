@@ -1203,7 +1203,10 @@ struct EnvSim {
             if (e <= eps) { tp = 0; sp = dm_med3((Real)0, -c * ia, (Real)1); }
             else {
                 const Real b = dot(d1, d2), denom = a * e - b * b;
-                sp = (denom > eps) ? dm_med3((Real)0, (b * f - c * e) * dm_rcp(denom), (Real)1) : (Real)0;
+                // (denom <= eps, parallel axes: the limit of the clamped quotient, i.e. the end of segment 1 towards which the axes converge -- s = 0 regardless put the
+                // pair at the far end of axes 1e-7 rad apart, 2 L sin(angle) off; exactly parallel axes have num = 0 and keep s = 0)
+                const Real num = b * f - c * e;
+                sp = (denom > eps) ? dm_med3((Real)0, num * dm_rcp(denom), (Real)1) : ((num > (Real)0) ? (Real)1 : (Real)0);
                 tp = (b * sp + f) * ie;
                 if (tp < 0) { tp = 0; sp = dm_med3((Real)0, -c * ia, (Real)1); }
                 else if (tp > 1) { tp = 1; sp = dm_med3((Real)0, (b - c) * ia, (Real)1); }
@@ -1561,6 +1564,10 @@ struct EnvSim {
         const int R = NL + 3 * nc;
         if (l == 0) { s.flg[FLG_NROWS] = R; s.flg[FLG_NCONT] = nc; }
         sync();
+        if (TAPS && dbg.contacts) {       // the slot records as the rows below read them
+            const int nw = m.max_contacts * 8;
+            for (int i = l; i < nw; i += LW) dbg.contacts[(size_t)e * nw + i] = (i < nc * 8) ? s.ct[i >> 3][i & 7] : (Real)0;
+        }
 
         mark(8);
         // ---- constraint rows: lane = row.  limits | normals | frictions (2 per contact)

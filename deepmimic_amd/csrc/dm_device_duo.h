@@ -405,6 +405,7 @@ struct DuoSim {
     // the launch will wait for -- a one-round launch lasts as long as its slowest wave -- and keeps a raised level (PRIO_LATE) in the throughput phases too
     static constexpr int PRIO_LATE = 2;      // same-box A/B, closed-loop spinkick: 1: -0.9 %, 2: -1.6 %, 3: -1.4 % step time; open loop +-0; the chain phases at 3 too: no further gain and +1.1 % open loop (profiles/r06_ab_lane_borrowing.json)
     int late = 0;
+    Real* tapc = nullptr; int* tapr = nullptr;          // tap instantiation: this character's rows of DebugTaps::contacts / rows (set by the kernel), null otherwise
     DM_DEV void prio_low() const { if (late) dm_setprio<PRIO_LATE>(); else dm_setprio<0>(); }
     DM_DEV Real& Lx(int r, int c) const { return s.Lt[L::lrow(r) + c]; }
     static DM_DEV v3 zero3() { return mk3((Real)0, (Real)0, (Real)0); }
@@ -946,6 +947,13 @@ _Pragma("unroll") \
         }
         const int NL = m.NL;
         const int R = NL + 3 * nc;
+        if constexpr (TAPS) {
+            if (tapc) {                      // the slot records of this character, whichever routine builds the rows from them
+                sync();
+                for (int i = hl; i < maxc * 8; i += HW) tapc[i] = (i < nc * 8) ? s.ct[i >> 3][i & 7] : (Real)0;
+                if (tapr && hl == 0) { tapr[0] = R; tapr[1] = nc; }
+            }
+        }
         if (wave_ballot(R > HW) != 0) {      // a heavily contacted character: the caller decides between borrowed lanes and the one-per-wave routine (FLG_NROWS is published for it; V2: FLG_NCONT holds the ground slots)
             if (hl == 0) s.flg[FLG_NROWS] = R;
             sync();
@@ -1288,6 +1296,7 @@ __global__ void __launch_bounds__(64) DM_WAVES_PER_EU((DuoWaves<Real>::value)) k
     const int e = 2 * pair + half;
     DuoSim<Real, TAPS, CC> sim(m, lds, wl);
     if (TAPS && dbg.prof) sim.b.prof_begin(dbg.prof + (size_t)e * 16);
+    if constexpr (TAPS) { if (dbg.contacts) { sim.tapc = dbg.contacts + (size_t)e * m.max_contacts * 8; sim.tapr = dbg.rows ? dbg.rows + (size_t)e * 2 : nullptr; } }
     sim.load(st, e);
     if (io.open_loop) sim.b.set_action_from_clip();
     else if (io.actions) sim.b.set_action(io.actions + (size_t)e * m.A);

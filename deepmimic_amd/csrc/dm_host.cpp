@@ -593,8 +593,9 @@ struct CtxT : CtxBase {
         dbg.lambda = (Real*)dalloc(sizeof(Real) * N * kMaxRows); dbg.rows = (int*)dalloc(sizeof(int) * N * 2);
         dbg.kin_pose = (Real*)dalloc(sizeof(Real) * N * h.P); dbg.kin_vel = (Real*)dalloc(sizeof(Real) * N * h.P);
         dbg.reward_terms = (Real*)dalloc(sizeof(Real) * N * 5); dbg.links = (Real*)dalloc(sizeof(Real) * N * h.J * 21);
+        dbg.contacts = (Real*)dalloc(sizeof(Real) * N * max_contacts * 8);
         d_prof = (long long*)dalloc(sizeof(long long) * N * 16);
-        return dbg.links ? 0 : fail("device allocation failed");
+        return dbg.links && dbg.contacts ? 0 : fail("device allocation failed");
     }
     // every step-kernel launch goes through here: the family of (class, variant, packing) is recorded (dm_get_debug "family") and launched
     int launch_step(int variant, int packing, unsigned grid, const StepIO<Real>& io, const DebugTaps<Real>& d) {
@@ -786,6 +787,12 @@ struct CtxT : CtxBase {
             if (what == 4) io.actions = d_actions;
             return two_per_wave(true) ? launch_step(SV_TAPS, 2, N / 2, io, d2) : launch_step(SV_TAPS, 1, N, io, d2);
         }
+        if (what == 5) {                // one scene update (dm_update(dt, 1)) on the two-per-wave tap family, "contacts" and "rows" taps only: DuoSim's own collision routine
+            if (!two_per_wave(true)) return fail("dm_probe 5: no two-per-wavefront tap family serves this context (biped class, DM-physics v1, an even batch, wave_packing != 1)");
+            DebugTaps<Real> d2; memset(&d2, 0, sizeof(d2)); d2.contacts = dbg.contacts; d2.rows = dbg.rows;
+            StepIO<Real> io; memset(&io, 0, sizeof(io)); io.n_updates = 1; io.dt = dt;
+            return launch_step(SV_TAPS, 2, N / 2, io, d2);
+        }
         launch_table<Real>().probe[cls](N, stream, md, st, dbg, what, dt);
         return 0;
     }
@@ -837,6 +844,7 @@ struct CtxT : CtxBase {
         if (s == "kin_vel") return dl(dbg.kin_vel, n * h.P, out);
         if (s == "reward_terms") return dl(dbg.reward_terms, n * 5, out);
         if (s == "links") return dl(dbg.links, n * h.J * 21, out);
+        if (s == "contacts") return dl(dbg.contacts, n * max_contacts * 8, out);
         if (s == "prof") return dl(d_prof, n * 16, out);
         return fail("unknown debug tap: " + s);
     }

@@ -321,6 +321,7 @@ struct DebugTaps {
     Real* reward_terms; // N x 5
     Real* links;    // N x J x 21 (com3, Rb9, vcom3, w3, joint3)
     long long* prof; // N x 16 accumulated shader-clock cycles per phase (profiling build of the step kernel only)
+    Real* contacts; // N x max_contacts x 8  contact slots of the last substep, right after collision detection: x(3), n(3), dist, links a | b << 8 (Lds::ct; slots beyond `rows`[1] read 0)
 };
 
 }  // namespace dmk

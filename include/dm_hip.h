@@ -283,8 +283,14 @@ int dm_set_state(dm_ctx* ctx, const double* pose, const double* vel, const doubl
 
 /* Component taps used by the parity tests (no reference analogue): what = 0 SPD torque, 1 one rigid-body
  * substep of length `dt` with the latched torque, 2 SPD-model mass matrix / bias force.
+ * 5: one scene update of length `dt` (dm_update(dt, 1): no action, no outputs) on the tap instantiation of the
+ * two-characters-per-wavefront kernel, which writes the "contacts" and "rows" taps only -- the collision routine of that
+ * kernel on its own; fails where no such family serves the context (dm_get_debug "family" reports the one that ran).
  * After the call dm_get_debug copies the requested tap: name in {"H","C","vstar","lambda","rows","tau",
- * "kin_pose","kin_vel","reward_terms","links"}; out must hold the full N x ... array of doubles.
+ * "kin_pose","kin_vel","reward_terms","links","contacts"}; out must hold the full N x ... array of doubles.
+ * "contacts" (N x max_contacts x 8, max_contacts as dm_physics_info reports it): the contact slots of the last substep right
+ * after collision detection, in slot order: point x (3), normal n (3), distance, link ids a | b << 8 (b = 255: the ground,
+ * 254: the free body; a = 254: the free body on the ground).  The number of slots in use is "rows"[1]; the others read 0.
  * "tau" and "fallback" need no dm_probe.  "fallback" (N doubles): the number of rigid-body substeps the env has spent on
  * the 64-lane fallback of the two-characters-per-wavefront kernel (a pair of which one character had more than 32
  * constraint rows in that substep; both characters count it) since dm_create or the last dm_set_state -- a statistic

@@ -442,7 +442,9 @@ struct Scene {
             if (e <= eps) { t = 0; s = std::min((real)1, std::max((real)0, -c / a)); }
             else {
                 real b = dot(d1, d2), denom = a * e - b * b;
-                s = (denom > eps) ? std::min((real)1, std::max((real)0, (b * f - c * e) / denom)) : 0;
+                // parallel axes (denom <= eps): the limit of the clamped quotient -- the end of segment 1 towards which the axes converge; 0 when they do not
+                const real num = b * f - c * e;
+                s = (denom > eps) ? std::min((real)1, std::max((real)0, num / denom)) : ((num > 0) ? (real)1 : (real)0);
                 t = (b * s + f) / e;
                 if (t < 0) { t = 0; s = std::min((real)1, std::max((real)0, -c / a)); }
                 else if (t > 1) { t = 1; s = std::min((real)1, std::max((real)0, (b - c) / a)); }
