@@ -31,6 +31,7 @@ SIGNATURES = {
     "dm_norm_update": ([_p, _p], None),
     "dm_norm_set": ([_p, _p, _p, _i64, _p], None),
     "dm_norm_get": ([_p, _p, _p, _p, _p, _p], None),
+    "dm_norm_set_state": ([_p, _p, _p, _p, _i64, _p], None),
     "dm_norm_normalize": ([_p, _p, _i, _p, _p], None),
     "dm_td_lambda_returns": ([_i, _i, _i] + [_p] * 6 + [_d] * 4 + [_p] * 3, None),
     "dm_ppo_workspace_bytes": ([_i, _i], _i64),

@@ -226,6 +226,26 @@ int dm_norm_set(dm_normalizer* h, const double* mean, const double* std_, int64_
     return 0;
 }
 
+// the statistics as dm_norm_get hands them out, put back word for word (a learner's checkpoint): mean_sq is stored, not rebuilt from std, so the next
+// dm_norm_update continues from the bits the saved run held
+int dm_norm_set_state(dm_normalizer* h, const double* mean, const double* std_, const double* mean_sq, int64_t count, void* hip_stream) {
+    if (!h || !mean || !std_ || !mean_sq) return fail("null argument");
+    if (count < 0) return fail("dm_norm_set_state: count must be >= 0");
+    DevGuard guard(h->device_id);
+    rt_stream stream = (rt_stream)hip_stream;
+    h->order_on(stream);
+    const int size = h->size;
+    std::vector<double> st(1 + 3 * (size_t)size); std::vector<float> mf(size), sf(size);
+    st[0] = (double)count;
+    for (int c = 0; c < size; ++c) {
+        if (!(std_[c] > 0)) return fail("dm_norm_set_state: std must be positive");
+        st[1 + c] = mean[c]; st[1 + size + c] = mean_sq[c]; st[1 + 2 * (size_t)size + c] = std_[c];
+        mf[c] = (float)mean[c]; sf[c] = (float)(1.0 / std_[c]);
+    }
+    if (rt_h2d(h->state, st.data(), sizeof(double) * st.size(), stream) || rt_h2d(h->mean_f, mf.data(), sizeof(float) * size, stream) || rt_h2d(h->inv_std_f, sf.data(), sizeof(float) * size, stream)) return fail("copy failed");
+    return 0;
+}
+
 int dm_norm_get(dm_normalizer* h, double* mean, double* std_, double* mean_sq, int64_t* count, void* hip_stream) {
     if (!h) return fail("null argument");
     DevGuard guard(h->device_id);

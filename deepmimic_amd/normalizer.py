@@ -70,6 +70,20 @@ class DeviceNormalizer:
     mean_sq = property(lambda self: self._get()[2])
     count = property(lambda self: self._get()[3])
 
+    def state_host(self) -> dict:
+        """mean, std, mean_sq (float64 [size]) and count as the device holds them: what a checkpoint keeps; synchronises"""
+        m, s, q, c = self._get()
+        return dict(mean=m, std=s, mean_sq=q, count=c)
+
+    def set_state(self, mean, std, mean_sq, count: int):
+        """`state_host()` put back word for word: unlike set_mean_std, mean_sq is stored as given, so the next update() continues from the saved bits"""
+        if not hasattr(self.lib, "dm_norm_set_state"):
+            raise RuntimeError("libdm_hip: this library has no dm_norm_set_state (rebuild it)")
+        a = [np.ascontiguousarray(x, dtype=np.float64).ravel() for x in (mean, std, mean_sq)]
+        if any(x.size != self.size for x in a):
+            raise ValueError("Normalizer shape mismatch, expecting size %d" % self.size)
+        self._chk(self.lib.dm_norm_set_state(self.h, a[0].ctypes.data, a[1].ctypes.data, a[2].ctypes.data, int(count), vp(self.stream)))
+
     def get_size(self):
         return self.size
 

@@ -12,7 +12,9 @@ Variables of an agent (learning/pg_agent.py:141-188, learning/nets/fc_2layers_10
     agent/main/actor/dist_gauss_diag/mean/{kernel,bias}  [512, A]      agent/main/actor/dist_gauss_diag/logstd/bias  [A]
     agent/resource/{s_norm,g_norm,a_norm}/{mean,std}
 The AMP task policies use the gated net (learning/nets/fc_2layers_gated_1024units.py: `gate0`, `gate1`, `gate_common` variables): `gated_actor_weights`
-reads those for the gated device actor; `actor_weights`, which returns the plain net's dict, refuses them and says so."""
+reads those for the gated device actor; `actor_weights`, which returns the plain net's dict, refuses them and says so.
+
+`write_checkpoint` is the writer of the same format (what `agent.save_model` calls) and `agent_variables` the variable set of the three kinds of shipped agent checkpoints."""
 import os
 import struct
 from typing import Dict, Optional
@@ -320,3 +322,132 @@ def disc_weights(prefix: str, scope: str = "agent", verify_below: int = 1 << 16)
     if "s_mean" in w and w["s_mean"].size != w["w1"].shape[0]:
         raise ValueError("%s: the discriminator takes %d inputs, amp_obs_norm has %d" % (prefix, w["w1"].shape[0], w["s_mean"].size))
     return w
+
+
+# ---- the writer (the mirror of read_index / read_tensors: one shard, uncompressed table blocks, masked CRC-32C on every block and tensor)
+
+_DTYPE_IDS = {np.dtype(v): k for k, v in DTYPES.items()}
+
+
+def _put_varint(n: int) -> bytes:
+    out = b""
+    while True:
+        c = n & 0x7f; n >>= 7
+        if n:
+            out += bytes([c | 0x80])
+        else:
+            return out + bytes([c])
+
+
+def _entry_bytes(arr: np.ndarray, offset: int, crc: int) -> bytes:
+    """BundleEntryProto of one tensor; proto3 leaves a zero field out (offset 0, a dimension of size 0)"""
+    shape = b""
+    for d in arr.shape:
+        dim = b"\x08" + _put_varint(int(d)) if d else b""
+        shape += b"\x12" + _put_varint(len(dim)) + dim
+    v = b"\x08" + _put_varint(_DTYPE_IDS[arr.dtype]) + b"\x12" + _put_varint(len(shape)) + shape
+    if offset:
+        v += b"\x20" + _put_varint(offset)
+    if arr.nbytes:
+        v += b"\x28" + _put_varint(arr.nbytes)
+    return v + b"\x35" + struct.pack("<I", crc)
+
+
+def _table_block_bytes(entries, restart_interval: int = 16) -> bytes:
+    """a leveldb table block: prefix-compressed (key, value) entries, the restart array and its length"""
+    out, restarts, prev = b"", [], b""
+    for i, (k, v) in enumerate(entries):
+        shared = 0
+        if i % restart_interval == 0:
+            restarts.append(len(out))
+        else:
+            while shared < min(len(k), len(prev)) and k[shared] == prev[shared]:
+                shared += 1
+        out += _put_varint(shared) + _put_varint(len(k) - shared) + _put_varint(len(v)) + k[shared:] + v
+        prev = k
+    restarts = restarts or [0]
+    return out + b"".join(struct.pack("<I", r) for r in restarts) + struct.pack("<I", len(restarts))
+
+
+def write_checkpoint(prefix: str, tensors: Dict[str, np.ndarray]) -> None:
+    """`tensors` ({variable name: array of a dtype in DTYPES}) as a one-shard V2 checkpoint in tf.train.Saver's layout: `<prefix>.data-00000-of-00001` holds the
+    tensors raw, little-endian, back to back in name order; `<prefix>.index` is the sorted table -- the BundleHeaderProto under the empty key, a BundleEntryProto
+    per variable, one data block, an empty metaindex block, the index block, the 48-byte footer -- with the masked CRC-32C of every block and tensor.  What
+    read_index / read_tensors read back bit for bit.  Whether TensorFlow's own `saver.restore` accepts the files is not tested here (no TensorFlow)."""
+    if not tensors:
+        raise ValueError("write_checkpoint: no tensors")
+    names = sorted(tensors)
+    data, entries = [], [(b"", b"\x08\x01\x1a\x02\x08\x01")]          # BundleHeaderProto: one shard, little endian, version {producer 1}
+    pos = 0
+    for n in names:
+        if not n or not isinstance(n, str):
+            raise ValueError("write_checkpoint: variable names are non-empty strings")
+        a = np.asarray(tensors[n])
+        if a.dtype not in _DTYPE_IDS:
+            raise ValueError("%s: unsupported dtype %s" % (n, a.dtype))
+        raw = np.ascontiguousarray(a.astype(a.dtype.newbyteorder("<"))).tobytes()
+        entries.append((n.encode(), _entry_bytes(a, pos, masked_crc32c(raw))))
+        data.append(raw); pos += len(raw)
+    blocks, at = [], 0
+
+    def put(block: bytes) -> bytes:
+        nonlocal at
+        handle = _put_varint(at) + _put_varint(len(block))
+        body = block + b"\x00"                                          # block type 0: uncompressed
+        blocks.append(body + struct.pack("<I", masked_crc32c(body))); at += len(body) + 4
+        return handle
+    h_data = put(_table_block_bytes(entries))
+    h_meta = put(_table_block_bytes([]))
+    h_index = put(_table_block_bytes([(names[-1].encode() + b"\x00", h_data)], 1))
+    foot = h_meta + h_index
+    foot += b"\x00" * (40 - len(foot)) + struct.pack("<Q", TABLE_MAGIC)
+    os.makedirs(os.path.dirname(os.path.abspath(prefix)), exist_ok=True)
+    with open(prefix + ".data-00000-of-00001", "wb") as f:
+        f.write(b"".join(data))
+    with open(prefix + ".index", "wb") as f:
+        f.write(b"".join(blocks) + foot)
+
+
+# ---- the variable set of an agent's checkpoint (what agent.save_model writes)
+
+LEGACY_LOGSTD_WIDTH = 36         # agent/main/actor/dist_gauss_diag/logstd/bias_1 (and bias_2): see agent_variables
+_GATE_SHAPES = (("gate_common/0/dense", "gc"), ("gate0/0/dense", "g0"), ("gate0/dense", "g0_bias"), ("gate0/dense_1", "g0_scale"),
+                ("gate1/0/dense", "g1"), ("gate1/dense", "g1_bias"), ("gate1/dense_1", "g1_scale"))
+
+
+def agent_variables(S: int, G: int, A: int, amp_size: int = 0, gated: bool = False, reward_scale: bool = False, H1: int = 1024, H2: int = 512,
+                    gate_common: int = 128, gate_hidden: int = 64, scope: str = "agent") -> Dict[str, tuple]:
+    """{variable name: (numpy dtype, shape)} of the checkpoint of one agent kind, as the shipped checkpoints hold it (data/policies/*/*.ckpt.index):
+    plain PPO (amp_size 0), AMP single-clip (amp_size > 0) and the AMP task agents (gated actor and critic, a goal, `reward_scale`).  Every normaliser is
+    mean / std / count plus the `_ph` twins of TFNormalizer's assign placeholders; `val_norm` and `logstd/bias_1` (float32 [LEGACY_LOGSTD_WIDTH] on every
+    character; the single-clip AMP checkpoints also hold a `bias_2`) are leftovers of the graph the shipped policies were trained with: the current reference
+    graph reads none of them, they are listed so that a written checkpoint has the shipped variable set."""
+    f32, i32 = np.dtype(np.float32), np.dtype(np.int32)
+    v = {}
+
+    def mlp(base, out_name, out_dim, gate):
+        v[base + "0/dense/kernel"] = (f32, (S + G, H1)); v[base + "0/dense/bias"] = (f32, (H1,))
+        v[base + "1/dense/kernel"] = (f32, (H1, H2)); v[base + "1/dense/bias"] = (f32, (H2,))
+        v[base + out_name + "/kernel"] = (f32, (H2, out_dim)); v[base + out_name + "/bias"] = (f32, (out_dim,))
+        if gate:
+            dims = dict(gc=(G, gate_common), g0=(gate_common, gate_hidden), g0_bias=(gate_hidden, H1), g0_scale=(gate_hidden, H1),
+                        g1=(gate_common, gate_hidden), g1_bias=(gate_hidden, H2), g1_scale=(gate_hidden, H2))
+            for var, key in _GATE_SHAPES:
+                v[base + var + "/kernel"] = (f32, dims[key]); v[base + var + "/bias"] = (f32, (dims[key][1],))
+    mlp(scope + "/main/actor/", "dist_gauss_diag/mean", A, gated)
+    v[scope + "/main/actor/dist_gauss_diag/logstd/bias"] = (f32, (A,))
+    for k in range(2 if (amp_size and not gated) else 1):
+        v[scope + "/main/actor/dist_gauss_diag/logstd/bias_%d" % (k + 1)] = (f32, (LEGACY_LOGSTD_WIDTH,))
+    mlp(scope + "/main/critic/", "dense", 1, gated)
+    norms = [("s_norm", S), ("g_norm", G), ("a_norm", A), ("val_norm", 1)]
+    if amp_size:
+        v[scope + "/main/disc/0/dense/kernel"] = (f32, (amp_size, H1)); v[scope + "/main/disc/0/dense/bias"] = (f32, (H1,))
+        v[scope + "/main/disc/1/dense/kernel"] = (f32, (H1, H2)); v[scope + "/main/disc/1/dense/bias"] = (f32, (H2,))
+        v[scope + "/main/disc/disc_logits/kernel"] = (f32, (H2, 1)); v[scope + "/main/disc/disc_logits/bias"] = (f32, (1,))
+        norms.append(("amp_obs_norm", amp_size))
+    for name, size in norms:
+        for k, (dt, shape) in (("mean", (f32, (size,))), ("std", (f32, (size,))), ("count", (i32, (1,)))):
+            v["%s/resource/%s/%s" % (scope, name, k)] = (dt, shape); v["%s/resource/%s/%s_ph" % (scope, name, k)] = (dt, shape)
+    if reward_scale:
+        v[scope + "/reward_scale"] = (f32, (1,))
+    return v

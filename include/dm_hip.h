@@ -563,6 +563,9 @@ int dm_norm_update(dm_normalizer* norm, void* hip_stream);
 int dm_norm_set(dm_normalizer* norm, const double* mean, const double* std, int64_t count, void* hip_stream);
 /* host copies of the statistics (any pointer may be NULL); synchronises hip_stream */
 int dm_norm_get(dm_normalizer* norm, double* mean, double* std, double* mean_sq, int64_t* count, void* hip_stream);
+/* what dm_norm_get handed out, put back word for word (host arrays; a learner's checkpoint): mean_sq is stored as given, not rebuilt from std as dm_norm_set
+ * does, so the next dm_norm_update continues from the saved bits.  count >= 0, std > 0. */
+int dm_norm_set_state(dm_normalizer* norm, const double* mean, const double* std, const double* mean_sq, int64_t count, void* hip_stream);
 /* Normalizer.normalize (normalizer.py:95-98) of x[n x size] into out[n x size], DEVICE pointers, fp32 */
 int dm_norm_normalize(dm_normalizer* norm, const float* x_dev, int n, float* out_dev, void* hip_stream);
 /* make `norm` columns [first_column, first_column + size) of the observation normaliser of `policy` (a device-to-device copy of mean and 1 / std,
