@@ -570,7 +570,7 @@ class BatchEnv:
         shapes = {"H": (self.N, self.D, self.D), "C": (self.N, self.D), "vstar": (self.N, self.D), "lambda": (self.N, 64),
                   "rows": (self.N, 2), "tau": (self.N, self.D), "kin_pose": (self.N, self.P), "kin_vel": (self.N, self.P),
                   "reward_terms": (self.N, 5), "links": (self.N, self.J, 21), "contacts": (self.N, self.max_contacts, 8), "prof": (self.N, 16), "fallback": (self.N,), "borrowed": (self.N,),
-                  "family": (self.N,)}
+                  "family": (self.N,), "limit_rest": (self.N, 4)}
         out = np.zeros(shapes[name])
         self._chk(self.lib.dm_get_debug(self.h, name.encode(), _dp(out)))
         return out

@@ -28,6 +28,8 @@ constexpr int kPrioSweepBase = 1, kPrioSweepMid = 2, kPrioSweepLo = 16, kPrioSwe
 template <typename T> static inline T half_bcast(T v, int src, int half) { return wave_shfl(v, half * 32 + src); }
 template <int SRC, typename T> static inline T half_bcast_c(T v, int half) { return half_bcast(v, SRC, half); }
 template <int R, typename T> static inline T half_sel_c(T oldv, T newv, int hl, uint32_t) { return hl == R ? newv : oldv; }
+static inline uint64_t duo_ballot(bool p) { return wave_ballot(p); }
+template <typename T> static inline uint64_t duo_pos_zero_lanes(T v) { return wave_ballot(v == (T)0 && !__builtin_signbit(v)); }
 template <typename T> static inline T half_sum(T v) {
     T* x = reinterpret_cast<T*>(emu::g_xchg);
     x[threadIdx.x] = v; __syncthreads();
@@ -66,6 +68,12 @@ template <int R> __device__ __forceinline__ float half_sel_c(float oldv, float n
     return out;
 }
 template <int R> __device__ __forceinline__ double half_sel_c(double oldv, double newv, int hl, uint32_t) { return hl == R ? newv : oldv; }
+// The lanes of the resting-limit test of the sweep (DuoSim::substep_post): ballots of single compares, which lower to the v_cmp itself (the ballot of an AND of
+// compares goes through v_cndmask + v_cmp_ne).  Lanes whose value has the bit pattern of +0 (not -0): an integer compare, written as one -- from C++ the optimizer
+// makes it a v_cmp_class_f32 whose class mask sits in a kernel-long VGPR of a kernel that has none to spare.
+__device__ __forceinline__ uint64_t duo_ballot(bool p) { return __builtin_amdgcn_ballot_w64(p); }
+__device__ __forceinline__ uint64_t duo_pos_zero_lanes(float v) { uint64_t mk; asm("v_cmp_eq_u32_e64 %0, 0, %1" : "=s"(mk) : "v"(v)); return mk; }
+__device__ __forceinline__ uint64_t duo_pos_zero_lanes(double v) { return __builtin_amdgcn_ballot_w64(__double_as_longlong(v) == 0ll); }
 __device__ __forceinline__ float half_sum(float v) {
     v += DM_DPP_F(v, 0xB1, 0xf, true);     // quad_perm [1,0,3,2]
     v += DM_DPP_F(v, 0x4E, 0xf, true);     // quad_perm [2,3,0,1]
@@ -406,6 +414,7 @@ struct DuoSim {
     static constexpr int PRIO_LATE = 2;      // same-box A/B, closed-loop spinkick: 1: -0.9 %, 2: -1.6 %, 3: -1.4 % step time; open loop +-0; the chain phases at 3 too: no further gain and +1.1 % open loop (profiles/r06_ab_lane_borrowing.json)
     int late = 0;
     Real* tapc = nullptr; int* tapr = nullptr;          // tap instantiation: this character's rows of DebugTaps::contacts / rows (set by the kernel), null otherwise
+    int* tapl = nullptr;                                // tap instantiation: this character's "limit_rest" counters behind DebugTaps::rows, null otherwise
     DM_DEV void prio_low() const { if (late) dm_setprio<PRIO_LATE>(); else dm_setprio<0>(); }
     DM_DEV Real& Lx(int r, int c) const { return s.Lt[L::lrow(r) + c]; }
     static DM_DEV v3 zero3() { return mk3((Real)0, (Real)0, (Real)0); }
@@ -1129,14 +1138,46 @@ _Pragma("unroll") \
             // visits of the other groups issue no scalar test and no branch.  A not-taken s_cbranch costs this wave about 20 cycles, not the 4 of its issue slot
             // (tools/sweep_visit_probe.hip, profiles/sweep_visit_probe.json).  A choice per block of four inside the iteration costs more than it saves: NOTES.md.
             // The copies made opaque at the top of each iteration stay (NOTES.md: without them the compiler hoists 32 masks and 32 predicates out of the loop).
+            // Resting limit rows (docs/HISTORY.md, "Resting limit rows"): rows 0 .. NL - 1 are the joint limits, the first LB blocks of four of every iteration
+            // when NL == 4 LB (v1 humanoid: NL = 4, one block; DM-physics v2: NL = 8, two; LB is the instantiation's, a model it does not fit never skips).
+            // An iteration at whose top EVERY limit lane of BOTH halves holds lambda with the bits of +0 and t < 0, strictly (a NaN fails both tests), jumps
+            // over those blocks: their visits are the identity, bit for bit.
+            //   * a limit lane's lo is the literal +0 and never changes (only friction lanes refresh bounds), its hi = lim_max_impulse > 0: with t < 0,
+            //     med3(+0, t, hi) = +0, delta = +0 - +0 = +0, and the lambda select writes +0 over +0;
+            //   * every other lane computes fma(-a, +0, t) with a finite a: t for t != 0, and +0 for t = +0, which is what the lanes beyond R hold
+            //     (t = (0 - 0) * 0);
+            //   * limit rows are visited first, so at the top of an iteration t holds every earlier visit; a resting row 0 leaves the t of rows 1 .. as they
+            //     were, so what held for all limit lanes at the top still holds when each is visited.
+            // Three compares whose lane masks the scalar unit combines, one scalar test and one forward branch per iteration; the iteration still ends at the first
+            // block past Rv.  The skip assumes nothing about the other rows; a non-finite a or a t of -0 in another lane are the cases the argument leaves out.
+            // The break tests stay outside the guard and the guard holds row visits only: with a `break` inside it the structurizer turned the iteration into flagged
+            // regions with copies of t, lambda, lo and hi (docs/HISTORY.md).  NL is compared through a per-iteration opaque copy like the other sweep constants.
+            constexpr int LB = V2 ? 2 : 1;
+            // tap build: bits 0-7 iterations that skipped, 8-15 / 16-23 iterations that visited with limit rows of half 0 / half 1 not at rest (both where NL does not
+            // fit), 24 the decision changed between iterations, 25 the last decision, 26 there was one
+            [[maybe_unused]] uint32_t tapw = 0u;
             auto sweep = [&](auto hotc) {
                 constexpr unsigned HOT = decltype(hotc)::value;
                 for (int it = 0; it < m.solver_iters; ++it) {
                     uint32_t one = 1u;
-                    int rnf = rn_fric;
-                    DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one); DM_OPAQUE_V(rnf);
+                    int rnf = rn_fric, nl = NL;
+                    DM_OPAQUE_S(Rv); DM_OPAQUE_S(fmask); DM_OPAQUE_V(lv); DM_OPAQUE_S(one); DM_OPAQUE_V(rnf); DM_OPAQUE_S(nl);
+                    const uint64_t unrest = duo_ballot(lv < nl) & ~(duo_pos_zero_lanes(lam) & duo_ballot(t < (Real)0));
+                    const uint32_t misfit = (uint32_t)(nl ^ (4 * LB));
+                    const bool skip = (unrest | misfit) == 0;
+                    if constexpr (TAPS) {        // coverage of the decision, one wave-uniform word per sweep (fields: at tapw; solver_iters < 256)
+                        const uint32_t s = skip ? 1u : 0u, u0 = ((uint32_t)unrest | misfit) != 0u ? 1u : 0u, u1 = ((uint32_t)(unrest >> 32) | misfit) != 0u ? 1u : 0u;
+                        if (((tapw >> 26) & 1u) != 0u && ((tapw >> 25) & 1u) != s) tapw |= 1u << 24;
+                        tapw = ((tapw & ~(1u << 25)) | (s << 25) | (1u << 26)) + s + (u0 << 8) + (u1 << 16);
+                    }
                     do {
-                        DM_DUO_PGS_BLK(0) DM_DUO_PGS_BLK(1) DM_DUO_PGS_BLK(2) DM_DUO_PGS_BLK(3)
+                        if (0 >= Rv) break;
+                        if (!skip) {
+                            DM_DUO_PGS_ROW4(0, (HOT & 1u) != 0)
+                            if constexpr (LB == 2) { if (4 < Rv) { DM_DUO_PGS_ROW4(1, (HOT & 1u) != 0) } }
+                        }
+                        if constexpr (LB == 2) { if (4 >= Rv) break; } else { DM_DUO_PGS_BLK(1) }      // (a skipping pair has Rv >= NL = 4 LB)
+                        DM_DUO_PGS_BLK(2) DM_DUO_PGS_BLK(3)
                         DM_DUO_PGS_BLK(4) DM_DUO_PGS_BLK(5) DM_DUO_PGS_BLK(6) DM_DUO_PGS_BLK(7)
                     } while (0);
                 }
@@ -1146,6 +1187,12 @@ _Pragma("unroll") \
             else if ((fmask & 0xFFu) != 0u && (fmask & 0xFF00u) != 0u) sweep(std::integral_constant<unsigned, 0x3u>());
             else if ((fmask & 0xFF00u) != 0u) sweep(std::integral_constant<unsigned, 0x2u>());
             else sweep(std::integral_constant<unsigned, 0x1u>());
+            if constexpr (TAPS) {        // dm_get_debug "limit_rest", per env: see DebugTaps::rows.  A visited iteration in which the env's own rows rested is its partner's.
+                if (tapl && hl == 0) {
+                    const int sk = (int)(tapw & 255u), own = (int)((tapw >> (8 + 8 * half)) & 255u);
+                    tapl[0] += sk; tapl[1] += own; tapl[2] += (m.solver_iters - sk) - own; tapl[3] += (int)((tapw >> 24) & 1u);
+                }
+            }
 #undef DM_DUO_PGS_BLK
 #undef DM_DUO_PGS_ROW4
 #undef DM_DUO_PGS_ROW
@@ -1297,6 +1344,7 @@ __global__ void __launch_bounds__(64) DM_WAVES_PER_EU((DuoWaves<Real>::value)) k
     DuoSim<Real, TAPS, CC> sim(m, lds, wl);
     if (TAPS && dbg.prof) sim.b.prof_begin(dbg.prof + (size_t)e * 16);
     if constexpr (TAPS) { if (dbg.contacts) { sim.tapc = dbg.contacts + (size_t)e * m.max_contacts * 8; sim.tapr = dbg.rows ? dbg.rows + (size_t)e * 2 : nullptr; } }
+    if constexpr (TAPS) { if (sim.tapr) sim.tapl = dbg.rows + (size_t)st.N * 2 + (size_t)e * 4; }      // (the "limit_rest" counters lie behind the N x 2 rows: DebugTaps::rows)
     sim.load(st, e);
     if (io.open_loop) sim.b.set_action_from_clip();
     else if (io.actions) sim.b.set_action(io.actions + (size_t)e * m.A);

@@ -590,7 +590,7 @@ struct CtxT : CtxBase {
         if (dbg.H) return 0;
         const HostModel& h = hm;
         dbg.H = (Real*)dalloc(sizeof(Real) * N * h.D * h.D); dbg.C = (Real*)dalloc(sizeof(Real) * N * h.D); dbg.vstar = (Real*)dalloc(sizeof(Real) * N * h.D);
-        dbg.lambda = (Real*)dalloc(sizeof(Real) * N * kMaxRows); dbg.rows = (int*)dalloc(sizeof(int) * N * 2);
+        dbg.lambda = (Real*)dalloc(sizeof(Real) * N * kMaxRows); dbg.rows = (int*)dalloc(sizeof(int) * N * 6);      // (N x 2 rows + N x 4 "limit_rest" counters: DebugTaps::rows)
         dbg.kin_pose = (Real*)dalloc(sizeof(Real) * N * h.P); dbg.kin_vel = (Real*)dalloc(sizeof(Real) * N * h.P);
         dbg.reward_terms = (Real*)dalloc(sizeof(Real) * N * 5); dbg.links = (Real*)dalloc(sizeof(Real) * N * h.J * 21);
         dbg.contacts = (Real*)dalloc(sizeof(Real) * N * max_contacts * 8);
@@ -790,6 +790,7 @@ struct CtxT : CtxBase {
         if (what == 5) {                // one scene update (dm_update(dt, 1)) on the two-per-wave tap family, "contacts" and "rows" taps only: DuoSim's own collision routine
             if (!two_per_wave(true)) return fail("dm_probe 5: no two-per-wavefront tap family serves this context (biped class, DM-physics v1, an even batch, wave_packing != 1)");
             DebugTaps<Real> d2; memset(&d2, 0, sizeof(d2)); d2.contacts = dbg.contacts; d2.rows = dbg.rows;
+            if (rt_memset(dbg.rows + (size_t)N * 2, 0, sizeof(int) * N * 4, stream)) return fail("memset failed");      // the "limit_rest" counters count this update alone
             StepIO<Real> io; memset(&io, 0, sizeof(io)); io.n_updates = 1; io.dt = dt;
             return launch_step(SV_TAPS, 2, N / 2, io, d2);
         }
@@ -846,6 +847,7 @@ struct CtxT : CtxBase {
         if (s == "links") return dl(dbg.links, n * h.J * 21, out);
         if (s == "contacts") return dl(dbg.contacts, n * max_contacts * 8, out);
         if (s == "prof") return dl(d_prof, n * 16, out);
+        if (s == "limit_rest") return dl(dbg.rows + n * 2, n * 4, out);
         return fail("unknown debug tap: " + s);
     }
 };

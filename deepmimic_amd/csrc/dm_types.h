@@ -315,7 +315,9 @@ struct DebugTaps {
     Real* C;        // N x D      bias force of the last dynamics pass
     Real* vstar;    // N x D      unconstrained velocity of the last substep
     Real* lambda;   // N x 64     constraint impulses of the last substep
-    int* rows;      // N x 2      (num rows, num contacts) of the last substep
+    int* rows;      // N x 2      (num rows, num contacts) of the last substep; behind them N x 4 "limit_rest" counters of the two-per-wave tap kernel, counted by dm_probe 5 (the struct keeps its
+                    //            size: it is a kernel argument of every step kernel): sweep iterations that skipped the resting limit blocks | visited them because this env's own limit rows were
+                    //            not at rest | only because its partner's were not; sweeps in which the decision changed between iterations
     Real* kin_pose; // N x P      kin pose / vel used by the last reward evaluation
     Real* kin_vel;  // N x P
     Real* reward_terms; // N x 5

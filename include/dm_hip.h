@@ -284,10 +284,13 @@ int dm_set_state(dm_ctx* ctx, const double* pose, const double* vel, const doubl
 /* Component taps used by the parity tests (no reference analogue): what = 0 SPD torque, 1 one rigid-body
  * substep of length `dt` with the latched torque, 2 SPD-model mass matrix / bias force.
  * 5: one scene update of length `dt` (dm_update(dt, 1): no action, no outputs) on the tap instantiation of the
- * two-characters-per-wavefront kernel, which writes the "contacts" and "rows" taps only -- the collision routine of that
+ * two-characters-per-wavefront kernel, which writes the "contacts", "rows" and "limit_rest" taps only -- the collision routine of that
  * kernel on its own; fails where no such family serves the context (dm_get_debug "family" reports the one that ran).
+ * "limit_rest" (N x 4, counted over that one update): Gauss-Seidel sweep iterations that jumped over the resting joint-limit blocks |
+ * that visited them because this env's own limit rows were not at rest | only because its partner's were not; sweeps in which
+ * the decision changed between iterations.
  * After the call dm_get_debug copies the requested tap: name in {"H","C","vstar","lambda","rows","tau",
- * "kin_pose","kin_vel","reward_terms","links","contacts"}; out must hold the full N x ... array of doubles.
+ * "kin_pose","kin_vel","reward_terms","links","contacts","limit_rest"}; out must hold the full N x ... array of doubles.
  * "contacts" (N x max_contacts x 8, max_contacts as dm_physics_info reports it): the contact slots of the last substep right
  * after collision detection, in slot order: point x (3), normal n (3), distance, link ids a | b << 8 (b = 255: the ground,
  * 254: the free body; a = 254: the free body on the ground).  The number of slots in use is "rows"[1]; the others read 0.
