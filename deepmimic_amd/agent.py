@@ -20,7 +20,7 @@ from typing import Optional
 import numpy as np
 
 from . import amp_rewards, ppo_batch, replay, returns, tf_checkpoint, train
-from .binding import stream_handle
+from .binding import stream_handle, tensor_arg
 from .episodes import EpisodeStats
 from .heads import Critic, Discriminator
 from .normalizer import DeviceNormalizer
@@ -144,10 +144,13 @@ class PPOAgent:
     KIND = "PPO"
 
     def __init__(self, env, cfg: AgentConfig, rollout_steps: int = 32, seed: int = 0, mini_batch_size: Optional[int] = None, optimizer: str = "momentum",
-                 init_from: Optional[str] = None, **opt):
+                 init_from: Optional[str] = None, reward_fn=None, **opt):
         """env: a `TorchVecEnv` (an AMP agent: with amp_obs=True).  rollout_steps: T; a rollout is T x N samples, the file's BatchSize is logged next to it, not
         enforced.  mini_batch_size: M (None: the file's MiniBatchSize).  optimizer / **opt (max_grad_norm, skip_nonfinite, betas, eps): the trainers'.
-        init_from: a checkpoint prefix whose nets and normalisers the agent starts from instead of random weights."""
+        init_from: a checkpoint prefix whose nets and normalisers the agent starts from instead of random weights.
+        reward_fn: a task written in torch -- a callable (info, reward) -> float32 [N] tensor on the env's device, called behind every env.step of `collect` with
+        the step's info dict (info["link_state"] and the like with `TorchVecEnv(link_state=True, deferred_reset=True)`) and the env's reward; its result is stored
+        in the rollout IN PLACE OF the env's reward (an AMP agent: in place of the task reward the style reward is blended with).  None: the env's reward."""
         import torch
         self.torch = torch
         if cfg.agent_type != self.KIND:
@@ -156,6 +159,7 @@ class PPOAgent:
         if bad:
             raise TypeError("unknown optimiser option %s" % bad[0])
         self.env, self.cfg, self.seed = env, cfg, int(seed)
+        self.reward_fn = reward_fn
         self.device = env.device
         self.T, self.N, self.S, self.G, self.A = int(rollout_steps), env.n, env.obs_dim, env.goal_dim, env.act_dim
         self.AMP = 0
@@ -327,6 +331,8 @@ class PPOAgent:
                                          exp_flags_ptr=ro.flags[t].data_ptr(), exp_rate=self.exp_rate, sample=True, seed=k["actor_seed"], step=k["actor_step0"] + t,
                                          stream=stream)
             _, reward, done, info = env.step(ro.act[t])
+            if self.reward_fn is not None:
+                reward = tensor_arg("reward_fn's result", self.reward_fn(info, reward), self.device, self.torch.float32, [(self.N,)], contiguous=False)
             ro.reward[t].copy_(reward); ro.terminate[t].copy_(info["terminate"]); ro.done[t].copy_(done); ro.valid[t].copy_(info["valid"])
             ro.terminal_obs[t].copy_(info["terminal_obs"])
             if G:

@@ -47,6 +47,9 @@ SIGNATURES = {
     "dm_time_warp_dims": ([_p, _pi32], None),
     "dm_time_warp_sample": ([_p, _p, _p, _p, _i, _p], None),
     "dm_time_warp_align": ([_i, _i, _i, _i, _i, _p, _p, _p, _d, _p, _p, _p], None),
+    "dm_link_state_dims": ([_p, _pi32], None),
+    "dm_link_state": ([_p, _i, _p, _p, _p, _p, _p], None),
+    "dm_reset_where": ([_p, _p, _p, _p], None),
     "dm_train_param_count": ([_p], _i64),
     "dm_train_workspace_bytes": ([_p, _i], _i64),
     "dm_train_actor_grad": ([_p] * 4 + [_i] * 2 + [_p] * 8 + [_i64, _p], None),

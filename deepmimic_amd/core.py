@@ -191,6 +191,7 @@ class BatchEnv:
                  erp: float = 0.0, physics: int = 1, solver_iters: int = 0):
         self.lib = load_library(lib_path)
         self.tables = tables
+        self.device_id = int(device_id)
         c = tables.cfg
         st, self._keep = fill_scene_tables(tables, test_mode=test_mode, self_collision=self_collision, erp=erp, solver_iters=solver_iters)
         tmin, tmax = float(st.time_lim_min), float(st.time_lim_max)
@@ -466,6 +467,61 @@ class BatchEnv:
             return
         self._chk(self.lib.dm_step_batch(self.h, vp(actions_ptr), C.c_double(timestep), int(n_updates), vp(states_ptr),
                                          vp(rewards_ptr), vp(term_ptr), vp(valid_ptr), vp(end_ptr), flags))
+
+    # ---- link states / masked reset (deepmimic_amd/link_state.py): host conveniences around the device calls
+    def _dev_arrays(self, specs, init=None):
+        """device buffers for a host convenience: {name: (shape, numpy dtype)} -> ({name: address}, fetch) where fetch() waits for the context's stream and
+        returns {name: numpy array}.  The emulator build's device memory is host memory; on the GPU the buffers are torch tensors on the context's device.
+        init: {name: array} to upload first."""
+        init = init or {}
+        if self.lib.dm_is_emulator():
+            bufs = {k: (np.ascontiguousarray(init[k], dtype=dt).reshape(sh).copy() if k in init else np.zeros(sh, dt)) for k, (sh, dt) in specs.items()}
+
+            def fetch():
+                self.synchronize()
+                return bufs
+            return {k: b.ctypes.data for k, b in bufs.items()}, fetch
+        import torch
+        dev = torch.device("cuda", self.device_id)
+        bufs = {k: (torch.as_tensor(np.ascontiguousarray(init[k], dtype=dt).reshape(sh)).to(dev) if k in init else torch.zeros(sh, dtype=getattr(torch, np.dtype(dt).name), device=dev))
+                for k, (sh, dt) in specs.items()}
+        torch.cuda.synchronize(dev)                                 # the fills ran on torch's stream, the launch goes to the context's
+
+        def fetch():
+            self.synchronize()
+            return {k: b.cpu().numpy() for k, b in bufs.items()}
+        return {k: b.data_ptr() for k, b in bufs.items()}, fetch
+
+    def link_state(self, which: int = 0):
+        """include/dm_hip.h dm_link_state as host arrays (float32): {"links" [N, J, 22], "env" [N, 8], "pose" [N, P], "vel" [N, P]} and, for the simulated
+        character of a scene with a ball, "obj" [N, 13]; which 0: the simulated character, 1: the kinematic one.  Columns: deepmimic_amd/link_state.py."""
+        from . import link_state as ls
+        J, lw, ew, P, ow = ls.dims(self)
+        specs = {"links": ((self.N, J, lw), np.float32), "env": ((self.N, ew), np.float32), "pose": ((self.N, P), np.float32), "vel": ((self.N, P), np.float32)}
+        if ow and which == 0:
+            specs["obj"] = ((self.N, ow), np.float32)
+        ptr, fetch = self._dev_arrays(specs)
+        ls.link_state_device(self, which, ptr["links"], ptr["env"], ptr["pose"], ptr["vel"], ptr.get("obj", 0))
+        return fetch()
+
+    def reset_where(self, mask, states=None, goals=None):
+        """include/dm_hip.h dm_reset_where from a host mask (N, != 0: reset): the selected envs start a new episode as an auto-reset launch starts it.  Returns
+        {"state" [N, S]} and, in a goal scene, {"goal" [N, G]}: rows of the selected envs hold the first observation (goal) of the new episode, the others what
+        `states` / `goals` held (zeros if not given)."""
+        from . import link_state as ls
+        m = (np.asarray(mask).reshape(self.N) != 0).astype(np.int32) if np.asarray(mask).dtype == bool else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.N)
+        specs, init = {"mask": ((self.N,), np.int32), "state": ((self.N, self.S), np.float32)}, {"mask": m}
+        if states is not None:
+            init["state"] = states
+        if self.G:
+            specs["goal"] = ((self.N, self.G), np.float32)
+            if goals is not None:
+                init["goal"] = goals
+        ptr, fetch = self._dev_arrays(specs, init)
+        ls.reset_where_device(self, ptr["mask"], ptr["state"], ptr.get("goal", 0))
+        out = fetch()
+        out.pop("mask")
+        return out
 
     def set_terminal_outputs(self, term_states_ptr: int = 0, term_goals_ptr: int = 0):
         """include/dm_hip.h dm_set_terminal_outputs: bind device buffers (raw pointers: N x S float32, and N x G float32 for a goal scene) that every

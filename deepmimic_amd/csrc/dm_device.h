@@ -3143,6 +3143,95 @@ __global__ void __launch_bounds__(64) k_time_warp_sample(ModelDev<Real> m, EnvSt
     }
 }
 
+// Link-space state of every env as float32 device rows, for rewards and observations written outside this library (include/dm_hip.h dm_link_state): one wavefront per
+// env, kinematics() of the simulated character (which = 0: the env's own pose and velocity) or of the kinematic one (which = 1: kin_sample at the env's clip time, on
+// its own clip of a multi-clip dataset, about the origin of its kin row -- as k_time_warp_sample).  Reads the env record only.  Any output may be null.
+//   links [N][J][LS_LINK_W]: link COM (3), body frame row-major (9; cKinTree::BodyWorldTrans), COM velocity (3; CalcBodyPartVel), angular velocity (3;
+//         CalcJointWorldAngularVel), joint position (3; CalcJointPos), in contact (1.0 where bit j of the env's contact mask is set; 0 for the kinematic character)
+//   env   [N][LS_ENV_W]: character COM (3) and COM velocity (3) (cRBDUtil::CalcCoM: mass-weighted, summed in link order by lane 0), root heading (calc_heading of the
+//         root rotation: BuildOriginTrans rotates by its negative), one zero
+//   pose, vel [N][P]: what the link state was computed from;  obj [N][LS_OBJ_W]: the free body of an OBJ class (position, rotation w x y z, linear, angular velocity)
+// An env's J x LS_LINK_W block is contiguous: lane j stages row j in LDS and the wave writes the block with consecutive lanes on consecutive words.  No atomics, one
+// summation order: two launches give the same bytes.  (LS_*: the row widths, dm_types.h)
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_link_state(ModelDev<Real> m, EnvState<Real> st, int which, float* links, float* env_out, float* pose_out, float* vel_out, float* obj_out) {
+    __shared__ Lds<Real, C> lds;
+    __shared__ float stage[C::NJ * LS_LINK_W];
+    const int e = blockIdx.x, l = threadIdx.x, J = m.J;
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.load(st, e);
+    const Real* p = lds.pose; const Real* v = lds.vel;
+    if (which == 1) {
+        Real* kp = sim.scratch(); Real* kv = kp + C::NP;
+        if (st.goal && m.num_clips > 1) {
+            const ModelDev<Real> mc = sim.model_of_clip((int)st.goal[(size_t)e * GS_WIDTH + GS_CLIP]);
+            EnvSim<Real, C> cs(mc, lds, l);
+            cs.li = sim.li;
+            cs.kin_sample(lds.clk[CLK_KIN], kp, kv);
+        } else sim.kin_sample(lds.clk[CLK_KIN], kp, kv);
+        p = kp; v = kv;
+    }
+    sim.kinematics(p, v, sim.zero3());
+    Real* red = sim.scratch() + 2 * C::NP;            // J x 6: mass * COM, mass * COM velocity (behind the kin pose / vel; Lds::Lt holds 2 NP + 7 NJ words)
+    const int contact = (which == 0) ? lds.flg[FLG_CONTACT] : 0;
+    if (l < J) {
+        const V3<Real> com = ld3(lds.com[l]), vc = sim.link_vcom(l), w = ld3(lds.w[l]), pj = ld3(lds.p[l]);
+        const Real mj = lds.mdl.mass[l];
+        st3(red + l * 6, mj * com); st3(red + l * 6 + 3, mj * vc);
+        float* o = stage + l * LS_LINK_W;
+        const Real* Rb = sim.Rbp(l);
+        o[0] = (float)com.x; o[1] = (float)com.y; o[2] = (float)com.z;
+        for (int k = 0; k < 9; ++k) o[3 + k] = (float)Rb[k];
+        o[12] = (float)vc.x; o[13] = (float)vc.y; o[14] = (float)vc.z;
+        o[15] = (float)w.x; o[16] = (float)w.y; o[17] = (float)w.z;
+        o[18] = (float)pj.x; o[19] = (float)pj.y; o[20] = (float)pj.z;
+        o[21] = ((contact >> l) & 1) ? 1.0f : 0.0f;
+    }
+    sim.sync();
+    if (links) { float* o = links + (size_t)e * J * LS_LINK_W; for (int i = l; i < J * LS_LINK_W; i += kWave) o[i] = stage[i]; }
+    if (env_out && l == 0) {
+        V3<Real> c = sim.zero3(), cv = c; Real tm = 0;
+        for (int j = 0; j < J; ++j) { c = c + ld3(red + j * 6); cv = cv + ld3(red + j * 6 + 3); tm += lds.mdl.mass[j]; }
+        c = ((Real)1 / tm) * c; cv = ((Real)1 / tm) * cv;
+        float* o = env_out + (size_t)e * LS_ENV_W;
+        o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z; o[3] = (float)cv.x; o[4] = (float)cv.y; o[5] = (float)cv.z;
+        o[6] = (float)calc_heading(ldq(p + 3)); o[7] = 0.0f;
+    }
+    for (int i = l; i < m.P; i += kWave) {
+        if (pose_out) pose_out[(size_t)e * m.P + i] = (float)p[i];
+        if (vel_out) vel_out[(size_t)e * m.P + i] = (float)v[i];
+    }
+    if (C::OBJ && obj_out && l < LS_OBJ_W) obj_out[(size_t)e * LS_OBJ_W + l] = (float)lds.obj[C::OBJ ? l : 0];
+}
+
+// The start of a new episode for the envs a device mask selects (include/dm_hip.h dm_reset_where): what a DM_AUTO_RESET launch does behind pass 0 of its emit loop,
+// as a launch of its own, so that a caller can look at the end-of-step state first.  Grid N; a workgroup whose mask word is 0 returns before it touches anything
+// (wave-uniform).  A selected env: goal_sync_flags, reset_episode with every draw the device's (keyed by the env's episode counter), then pass 1 of emit: RecordState
+// of the new episode into row e of `states`, RecordGoal into row e of the context's last-goals table (`goals_own`) and of `goals` (null: not wanted).  No reward, flag
+// or AMP row is written -- the auto-reset's pass 1 writes none.
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_env_reset_where(ModelDev<Real> m, EnvState<Real> st, const int* mask, float* states, float* goals_own, float* goals) {
+    __shared__ Lds<Real, C> lds;
+    const int e = blockIdx.x, l = threadIdx.x;
+    if (mask[e] == 0) return;
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.load(st, e);
+    // emit() reads the invalid latch of the launch that ended the episode (FLG_OVER bit 1), which the env record keeps as valid == 0: a recovery episode
+    // (try_recovery_reset) leaves both alone, reset_env clears them
+    if (l == 0 && !lds.flg[FLG_VALID]) lds.flg[FLG_OVER] = 2;
+    sim.sync();
+    if (st.goal) sim.goal_sync_flags(st, e);
+    reset_episode<true, true>(sim, st, e, st.pert ? st.pert + (size_t)e * PT_WIDTH : nullptr, l == 0);
+    StepIO<Real> io = StepIO<Real>();
+    io.states = states; io.goals = goals_own;
+    sim.emit(io, DebugTaps<Real>(), e, false);
+    if (st.goal && m.scene_goal) {
+        sim.emit_goal(io, st, e, false);      // (ends behind a barrier: the row lane 0 stored is visible to this workgroup's loads, as in emit_terminal)
+        if (goals && goals_own && l < m.goal_dim) goals[(size_t)e * m.goal_dim + l] = goals_own[(size_t)e * m.goal_dim + l];
+    }
+    sim.store(st, e);
+}
+
 // component taps for parity tests: SPD torque for the stored state / one substep with the stored torque
 template <typename Real, typename C>
 __global__ void __launch_bounds__(64) k_env_probe(ModelDev<Real> m, EnvState<Real> st, DebugTaps<Real> dbg, int what, double dt) {

@@ -322,12 +322,15 @@ struct LaunchTable {
     decltype(&launch_probe<Real, ClsBiped>) probe[kNumCls];
     decltype(&launch_amp_expert<Real, ClsBiped>) expert[kNumCls];
     decltype(&launch_time_warp_sample<Real, ClsBiped>) tw_sample[kNumCls];
+    decltype(&launch_link_state<Real, ClsBiped>) link_state[kNumCls];
+    decltype(&launch_reset_where<Real, ClsBiped>) reset_where[kNumCls];
     int base[kNumCls];
-    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, base{} {
+    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, link_state{}, reset_where{}, base{} {
 #define DM_ROW(id, pack, Cls, V) if (!step[k##Cls][V][pack - 1].launch) step[k##Cls][V][pack - 1] = {id, &launch_step_family<Real, id>};      // (of two rows for one combination the first is dispatched)
         DM_STEP_FAMILIES(DM_ROW)
 #undef DM_ROW
-#define DM_ROW(Cls) reset[k##Cls] = &launch_reset<Real, Cls>; query[k##Cls] = &launch_query<Real, Cls>; probe[k##Cls] = &launch_probe<Real, Cls>;
+#define DM_ROW(Cls) reset[k##Cls] = &launch_reset<Real, Cls>; query[k##Cls] = &launch_query<Real, Cls>; probe[k##Cls] = &launch_probe<Real, Cls>; \
+                    link_state[k##Cls] = &launch_link_state<Real, Cls>; reset_where[k##Cls] = &launch_reset_where<Real, Cls>;
         DM_MISC_CLASSES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls) expert[k##Cls] = &launch_amp_expert<Real, Cls>; tw_sample[k##Cls] = &launch_time_warp_sample<Real, Cls>;
@@ -388,6 +391,9 @@ struct CtxBase {
     virtual int manifolds(double* out, const double* in) = 0;
     virtual int amp_expert_clips(int n, const int* clips_dev /* null: the model's own clip */, const double* times_dev, const double* gh_dev, float* out_dev) = 0;
     virtual int time_warp_sample(void* samples_dev, int* count_dev, const int* restart_dev, int capacity, int* overflow_dev) = 0;      // dm_time_warp.h
+    virtual int link_state(int which, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev, float* obj_dev) = 0;      // dm_link_state.h
+    virtual int reset_where(const int* mask_dev, float* states_dev, float* goals_dev) = 0;
+    virtual bool has_obj() const = 0; virtual bool has_tape() const = 0;
     virtual int probe(int what, double dt) = 0;
     virtual int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) = 0;
     virtual int set_state(const double* pose, const double* vel, const double* tar, const double* kin, const double* clk, const int* flg) = 0;
@@ -685,6 +691,16 @@ struct CtxT : CtxBase {
         launch_table<Real>().tw_sample[cls](N, stream, md, st, (Real*)samples_dev, count_dev, restart_dev, capacity, overflow_dev);      // (the sampler of the base class)
         return 0;
     }
+    int link_state(int which, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev, float* obj_dev) override {
+        launch_table<Real>().link_state[cls](N, stream, md, st, which, links_dev, env_dev, pose_dev, vel_dev, obj_dev);
+        return 0;
+    }
+    int reset_where(const int* mask_dev, float* states_dev, float* goals_dev) override {
+        launch_table<Real>().reset_where[cls](N, stream, md, st, mask_dev, states_dev, d_goals, goals_dev);
+        return 0;
+    }
+    bool has_obj() const override { return st.obj != nullptr; }
+    bool has_tape() const override { return md.draw_tape != nullptr; }
     int clips(int* out, const int* in) override {                     // N: GS_CLIP, the clip the env was reset to
         if (!st.goal) { if (in) return no_goal(); for (int e = 0; e < N; ++e) out[e] = 0; return 0; }
         for (int e = 0; in && e < N; ++e) if (in[e] < 0 || in[e] >= hm.num_clips) return fail("clip id out of range");
@@ -1475,6 +1491,7 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_train.h"         // PPO actor / critic minibatch gradients and the momentum step on a live policy context (after dm_policy_host.h and dm_ppo_batch.h: its tree)
 #include "dm_train_gated.h"   // the same updates for the gated nets of the AMP task agents (after dm_train.h: its head, fold and gradient kernels)
 #include "dm_optim.h"         // Adam, global-norm clipping and the non-finite guard: one optimiser step for every trainer (after dm_train_gated.h: the layouts, train_refresh)
+#include "dm_link_state.h"   // link states as device tensors and the reset selected by a device mask: the entry points of k_link_state / k_env_reset_where
 #include "dm_time_warp.h"    // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs
 

@@ -48,6 +48,14 @@ template <typename Real, typename C>
 void launch_time_warp_sample(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, Real* samples, int* count, const int* restart, int capacity, int* overflow) {
     RT_LAUNCH((k_time_warp_sample<Real, C>), grid, s, m, st, samples, count, restart, capacity, overflow);
 }
+template <typename Real, typename C>
+void launch_link_state(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, int which, float* links, float* env_out, float* pose_out, float* vel_out, float* obj_out) {
+    RT_LAUNCH((k_link_state<Real, C>), grid, s, m, st, which, links, env_out, pose_out, vel_out, obj_out);
+}
+template <typename Real, typename C>
+void launch_reset_where(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, float* states, float* goals_own, float* goals) {
+    RT_LAUNCH((k_env_reset_where<Real, C>), grid, s, m, st, mask, states, goals_own, goals);
+}
 
 // this object's family (dm_families.h): the reset / query / probe family expands its class lists, any other id instantiates the launcher of its row
 #if DM_TU_F64
@@ -60,8 +68,10 @@ typedef float TuReal;
 #define DM_INST_MISC(C)                                                                                                                                  \
     template void launch_reset<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, const double*, const double*); \
     template void launch_query<TuReal, C>(DM_STEP_ARGS);                                                                                                 \
-    template void launch_probe<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const DebugTaps<TuReal>&, int, double);
-#define DM_INST_EXPERT(C)                                                                                                                                 \
+    template void launch_probe<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const DebugTaps<TuReal>&, int, double); \
+    template void launch_link_state<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, int, float*, float*, float*, float*, float*); \
+    template void launch_reset_where<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, float*, float*, float*);
+#define DM_INST_EXPERT(C)                                                                                                                                \
     template void launch_amp_expert<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const double*, const double*, float*, const int*);            \
     template void launch_time_warp_sample<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, TuReal*, int*, const int*, int, int*);
 DM_MISC_CLASSES(DM_INST_MISC)

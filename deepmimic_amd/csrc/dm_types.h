@@ -266,6 +266,8 @@ enum { TP_POS_G = 0, TP_POS_M, TP_NAVAIL, TP_NSAVED,      // raw positions consu
 enum { PT_TIMER = 0, PT_NEXT, PT_DRAWS, PT_SLOT0, PT_LINK = 0, PT_FX, PT_FY, PT_FZ, PT_DUR, PT_TIME, PT_SLOT_W = 6, PT_SLOTS = 2, PT_KSEED = 15 /* own draw key + 1 (0: the ctx's), see GS_KSEED */, PT_WIDTH = 16 };
 // the free body's record (EnvState::obj, OBJ classes): position, rotation (w, x, y, z), linear and angular velocity
 enum { OB_PX = 0, OB_QW = 3, OB_VX = 7, OB_WX = 10, OB_WIDTH = 16 };
+// row widths of dm_link_state's float32 outputs (k_link_state, dm_device.h): per link, per env, the free body
+enum { LS_LINK_W = 22, LS_ENV_W = 8, LS_OBJ_W = 13 };
 
 template <typename Real>
 struct EnvState {

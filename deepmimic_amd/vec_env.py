@@ -14,6 +14,7 @@ from typing import Dict, Tuple
 from .binding import stream_handle, tensor_arg
 from .core import BatchEnv
 from .episodes import EpisodeStats, decode_block, merge_blocks
+from .link_state import KIN, SIM, LinkState, reset_where_device
 from .model import SceneTables
 from .time_warp import TimeWarp, buffer_size, why_no_warper
 
@@ -21,7 +22,8 @@ from .time_warp import TimeWarp, buffer_size, why_no_warper
 class TorchVecEnv:
     def __init__(self, tables: SceneTables, num_envs: int, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
                  updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
-                 episode_bin_steps: int = 1, time_warp: bool = False, **env_kwargs):
+                 episode_bin_steps: int = 1, time_warp: bool = False, link_state: bool = False, kin_link_state: bool = False, deferred_reset: bool = False,
+                 **env_kwargs):
         """terminal_obs (default on): keep `terminal_obs` / `terminal_goal` tensors bound to the context (BatchEnv.set_terminal_outputs), handed out as
         info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent.
         episode_stats (default off: no extra launch, no extra key): `step` runs deepmimic_amd.episodes.EpisodeStats.update behind the step launch on the same
@@ -33,7 +35,19 @@ class TorchVecEnv:
         alignment cost plus 1 per sample the episode fell short of the buffer where done[i] is set in THIS step, 0 elsewhere.  `reward` stays what the launch
         wrote.  With `episode_stats` as well the statistics accumulate time_warp_return IN PLACE OF reward (episode_return included), so that `episode_totals()`
         is the reference's Test_Return for these scenes.  Memory: N * 2 * capacity * 3J * sizeof(Real) for the samples, capacity = ceil(30 * episode length) + 2
-        -- 0.89 GB for 4096 humanoids and 20 s episodes in fp32."""
+        -- 0.89 GB for 4096 humanoids and 20 s episodes in fp32.
+        link_state / kin_link_state / deferred_reset (all off by default: `step` launches and returns exactly what it does without them) serve tasks written in
+        torch (deepmimic_amd/link_state.py has the column constants).
+        link_state: `step` runs dm_link_state behind the step launch on the same stream and hands out info["link_state"] [N, J, 22], info["link_env"] [N, 8],
+        info["pose"] / info["vel"] [N, P] and, where the scene has a ball, info["obj_state"] [N, 13] -- float32 tensors of the SIMULATED character; `link_names` names
+        the J rows.  kin_link_state adds the same of the KINEMATIC character (the clip the env tracks) under "kin_link_state", "kin_link_env", "kin_pose", "kin_vel".
+        `update_link_state()` refreshes the tensors from the context's current state at any time, e.g. behind `reset()`.
+        WITHOUT deferred_reset the link-state rows of envs that are done in this step describe the first state of the NEW episode, as `obs` does: the launch has
+        reset them already.  deferred_reset: `step` launches without the in-kernel auto-reset (ending an episode at the update that ends it, as before), takes the
+        link states -- which then describe the END OF THE STEP for every env, finished ones included: the state a task reward has to see --, copies the `obs` /
+        `goal` rows of done envs into `terminal_obs` / `terminal_goal` and resets the done envs with dm_reset_where, which overwrites those `obs` / `goal` rows with
+        the new episode's.  (obs, reward, done, info) hold the same bytes as the auto-reset step's; it is three or four launches and two small torch kernels
+        instead of one launch, with no host read."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -69,6 +83,11 @@ class TorchVecEnv:
             self.tw = TimeWarp(self.env, tables, device=self.device)
             self.time_warp_return = torch.zeros(self.n, **f32)
             self._tw_restart = torch.ones(self.n, **i32)            # envs reset since their last sample: all before the first step, `done` of the last step after it
+        self.link_names = list(tables.joint_names)
+        self.deferred_reset = bool(deferred_reset)
+        self.ls = LinkState(self.env, SIM, device=self.device) if link_state else None
+        self.kin_ls = LinkState(self.env, KIN, device=self.device) if kin_link_state else None
+        self._done_i32 = torch.zeros(self.n, **i32) if deferred_reset else None      # dm_reset_where's mask
 
     def _enter(self):
         h = stream_handle(self.device)
@@ -78,9 +97,9 @@ class TorchVecEnv:
     def _leave(self):
         pass
 
-    def _launch(self, actions_ptr, n_updates, auto_reset):
+    def _launch(self, actions_ptr, n_updates, auto_reset, end_early=None):
         self.env.step_device(actions_ptr, self.obs.data_ptr(), self.reward.data_ptr(), self.terminate.data_ptr(), self.valid.data_ptr(),
-                             self.episode_end.data_ptr(), timestep=self.timestep, n_updates=n_updates, auto_reset=auto_reset,
+                             self.episode_end.data_ptr(), timestep=self.timestep, n_updates=n_updates, auto_reset=auto_reset, end_early=end_early,
                              amp_ptr=self.amp_obs.data_ptr() if self.amp_obs is not None else 0)
 
     def reset(self):
@@ -112,8 +131,7 @@ class TorchVecEnv:
         self._enter()
         if self.tw is not None:
             self.tw.sample(self._tw_restart)                        # the state at entry of the control step (cRLSceneSimChar::PreUpdate)
-        self._launch(actions.data_ptr(), self.updates, True)
-        self._leave()
+        self._launch(actions.data_ptr(), self.updates, not self.deferred_reset, end_early=True)      # (an episode ends at the update that ends it, on both routes)
         info = {"terminate": self.terminate, "valid": self.valid}
         if self.amp_obs is not None:
             info["amp_obs"] = self.amp_obs
@@ -125,6 +143,18 @@ class TorchVecEnv:
             if self.terminal_goal is not None:
                 info["terminal_goal"] = self.terminal_goal
         done = (self.episode_end != 0) | (self.valid == 0)
+        self._link_info(info)                                       # (auto-reset: done envs are in their new episode; deferred: every env at the end of the step)
+        if self.deferred_reset:
+            # what the auto-reset launch does behind its outputs, as launches of their own: the rows of the moment the episode ended go to terminal_obs /
+            # terminal_goal (other rows keep their bytes), then the done envs start their next episode and obs / goal get its first rows
+            d = done.unsqueeze(1)
+            if self.terminal_obs is not None:
+                self.torch.where(d, self.obs, self.terminal_obs, out=self.terminal_obs)
+                if self.terminal_goal is not None:
+                    self.torch.where(d, self.goal, self.terminal_goal, out=self.terminal_goal)
+            self._done_i32.copy_(done)
+            reset_where_device(self.env, self._done_i32.data_ptr(), self.obs.data_ptr(), self.goal.data_ptr() if self.goal_dim else 0)
+        self._leave()
         if self.tw is not None:
             self._tw_restart.copy_(done)                            # (done is bool: its int32 form is both the alignment's selection and the next step's restart marks)
             self.tw.align(self._tw_restart, out=(self.time_warp_return, None), stream=self._stream_handle)
@@ -133,6 +163,21 @@ class TorchVecEnv:
             self.stats.update(self.reward if self.tw is None else self.time_warp_return, self.terminate, done, self.valid, out=(self.episode_return, self.episode_length))
             info["episode_return"], info["episode_length"] = self.episode_return, self.episode_length
         return self.obs, self.reward, done, info
+
+    def _link_info(self, info):
+        for ls, prefix in ((self.ls, ""), (self.kin_ls, "kin_")):
+            if ls is not None:
+                info.update(ls.update().info(prefix))
+
+    def update_link_state(self) -> dict:
+        """refresh the link-state tensors from the context's current state (e.g. behind `reset()`), on torch's current stream; returns them under their info keys"""
+        if self.ls is None and self.kin_ls is None:
+            raise RuntimeError("update_link_state needs link_state=True or kin_link_state=True")
+        self._enter()
+        info = {}
+        self._link_info(info)
+        self._leave()
+        return info
 
     def episode_totals(self) -> dict:
         """figures of the episodes finished since construction or the last `stats.clear_totals()` (episodes.decode_block): one device-to-host copy"""

@@ -771,6 +771,35 @@ int dm_time_warp_align(int device_id, int n_envs, int capacity, int dim, int f64
                        const int32_t* select_dev /* NULL: all */, double term_step_cost, float* reward_out_dev /* [N] */, double* cost_out_dev /* NULL or [N] */,
                        void* hip_stream);
 
+/* ---- Link states as device tensors and a reset selected by a device mask, for tasks written in torch (deepmimic_amd/csrc/dm_link_state.h, k_link_state and
+ * k_env_reset_where of dm_device.h, deepmimic_amd/link_state.py).  Every pointer but the ctx is a DEVICE pointer; both calls are asynchronous on the ctx's stream, read
+ * nothing back and synchronise nothing; a refused call launches nothing and names its reason through dm_last_error.
+ *
+ * dm_link_state_dims: out[5] = J, 22, 8, P, 13 (0 on a context without a free body) -- the row widths of the outputs below.
+ *
+ * dm_link_state: the forward kinematics of the env record as it stands, float32 whatever the context's precision; a NULL output is skipped.
+ *   which     0: the simulated character (the env's pose and velocity); 1: the kinematic character (the env's clip -- its own in a multi-clip dataset -- sampled at the
+ *             env's clip time, about the origin of the env's kin row)
+ *   links_dev [N][J][22]: 0:3 link COM world position; 3:12 body world rotation, row-major (cKinTree::BodyWorldTrans); 12:15 COM linear velocity
+ *             (cKinTree::CalcBodyPartVel); 15:18 angular velocity (cKinTree::CalcJointWorldAngularVel); 18:21 joint world position (cKinTree::CalcJointPos);
+ *             21 in contact: 1.0 where bit j of the env's contact mask (flags column 1 of dm_get_state: the last substep) is set, else 0.0; 0 for which = 1
+ *   env_dev   [N][8]: character COM (3) and COM velocity (3) as cRBDUtil::CalcCoM; the root heading (cKinTree::BuildOriginTrans rotates about y by its negative); 0
+ *   pose_dev, vel_dev [N][P]: the pose and velocity the link state was computed from (which = 1: the sampled clip pose)
+ *   obj_dev   [N][13]: the free body of dribble_amp (position, rotation w x y z, linear and angular velocity), the columns of dm_get_obj_state
+ * Behind a DM_AUTO_RESET launch the rows of envs it reset describe the first state of the new episode, as `states` does.  No atomics: two calls give the same bytes.
+ * Refused: a NULL ctx; which outside {0, 1}; which = 1 on a scene without motion frames; obj_dev on a context without a free body.
+ *
+ * dm_reset_where: the start of a new episode for every env with mask_dev[i] != 0 (int32[N]), exactly what a DM_AUTO_RESET launch does for an env whose episode ended,
+ * behind its outputs: every draw is the device's, keyed by the env's episode counter; RecordState of the new episode goes to row i of states_dev [N][S], RecordGoal
+ * (goal scenes) to row i of goals_dev [N][dm_goal_size()] (may be NULL) and of the table dm_last_goals / dm_last_goals_device read.  No reward, flag or AMP row is
+ * written.  Rows of unselected envs keep their bytes, in the context and in the outputs.  A control step launched without DM_AUTO_RESET (and with
+ * DM_END_EPISODE_EARLY), then dm_reset_where of the envs that ended, leaves the context and `states` as the DM_AUTO_RESET launch leaves them -- with the end-of-step
+ * state of every env, finished ones included, visible in between (tests/test_reset_where.py).
+ * Refused: a NULL ctx, mask_dev or states_dev; goals_dev on a scene without a goal; a context with a draw tape bound (dm_set_draw_tape: that route draws on the host). */
+int dm_link_state_dims(const dm_ctx* ctx, int32_t* out /* [5] */);
+int dm_link_state(dm_ctx* ctx, int which, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev, float* obj_dev);
+int dm_reset_where(dm_ctx* ctx, const int32_t* mask_dev, float* states_dev, float* goals_dev);
+
 /* ---- PPO actor and critic minibatch updates on the device (deepmimic_amd/csrc/dm_train.h, deepmimic_amd/train.py): PPOAgent._update_actor / _update_critic and
  * MPISolver.update (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples, so that
  * exp(logp_new - logp_old) is 1 (to rounding) at the weights that sampled.  Stateless like dm_ppo_*, dm_replay_* and dm_episode_stats: the caller owns every byte, all
