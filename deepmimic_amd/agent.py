@@ -144,13 +144,19 @@ class PPOAgent:
     KIND = "PPO"
 
     def __init__(self, env, cfg: AgentConfig, rollout_steps: int = 32, seed: int = 0, mini_batch_size: Optional[int] = None, optimizer: str = "momentum",
-                 init_from: Optional[str] = None, reward_fn=None, **opt):
+                 init_from: Optional[str] = None, reward_fn=None, goal_fn=None, goal_dim: int = 0, **opt):
         """env: a `TorchVecEnv` (an AMP agent: with amp_obs=True).  rollout_steps: T; a rollout is T x N samples, the file's BatchSize is logged next to it, not
         enforced.  mini_batch_size: M (None: the file's MiniBatchSize).  optimizer / **opt (max_grad_norm, skip_nonfinite, betas, eps): the trainers'.
         init_from: a checkpoint prefix whose nets and normalisers the agent starts from instead of random weights.
         reward_fn: a task written in torch -- a callable (info, reward) -> float32 [N] tensor on the env's device, called behind every env.step of `collect` with
         the step's info dict (info["link_state"] and the like with `TorchVecEnv(link_state=True, deferred_reset=True)`) and the env's reward; its result is stored
-        in the rollout IN PLACE OF the env's reward (an AMP agent: in place of the task reward the style reward is blended with).  None: the env's reward."""
+        in the rollout IN PLACE OF the env's reward (an AMP agent: in place of the task reward the style reward is blended with).  None: the env's reward.
+        goal_fn / goal_dim: an observation written in torch -- goal_fn(info) -> float32 [N, goal_dim] on the env's device becomes the goal block of actor and
+        critic, as the goal of a goal scene does (G = goal_dim: goal normaliser, rollout goal / terminal_goal, gated nets, checkpoints).  It needs a scene without
+        a goal of its own and `TorchVecEnv(..., deferred_reset=True)` with link states or kin_lookahead (info is what `env.update_link_state()` returns, plus the
+        step's keys behind a step).  Per step of `collect` and `test`: env.step; reward_fn and goal_fn on the end-of-step tensors -- that goal is the terminal
+        goal where done; env.update_link_state(), after which the done envs show their new episode (the others the same bytes); goal_fn again: the goal the
+        next action is taken from."""
         import torch
         self.torch = torch
         if cfg.agent_type != self.KIND:
@@ -159,9 +165,20 @@ class PPOAgent:
         if bad:
             raise TypeError("unknown optimiser option %s" % bad[0])
         self.env, self.cfg, self.seed = env, cfg, int(seed)
-        self.reward_fn = reward_fn
+        self.reward_fn, self.goal_fn = reward_fn, goal_fn
         self.device = env.device
         self.T, self.N, self.S, self.G, self.A = int(rollout_steps), env.n, env.obs_dim, env.goal_dim, env.act_dim
+        if goal_fn is None and goal_dim:
+            raise ValueError("goal_dim without goal_fn")
+        if goal_fn is not None:
+            if env.goal_dim:
+                raise ValueError("goal_fn: the scene has a goal of its own (env.goal_dim = %d)" % env.goal_dim)
+            if int(goal_dim) < 1:
+                raise ValueError("goal_fn needs goal_dim >= 1")
+            if not getattr(env, "deferred_reset", False):
+                raise ValueError("goal_fn needs TorchVecEnv(..., deferred_reset=True): the terminal goal is computed from the end-of-step link states")
+            self.G = int(goal_dim)
+            self._goal = torch.zeros((self.N, self.G), dtype=torch.float32, device=self.device)        # the goal the next action is taken from
         self.AMP = 0
         if self.T < 1:
             raise ValueError("rollout_steps must be >= 1")
@@ -306,9 +323,26 @@ class PPOAgent:
 
     def _begin(self, obs):
         """behind a reset of every env: the goal of the new episodes (the step launches keep it current from here on), no episode in flight"""
-        if self.G:
+        if self.goal_fn is not None:
+            self._goal.copy_(self._call_goal_fn(self.env.update_link_state()))
+        elif self.G:
             self.env.goal.copy_(self.torch.from_numpy(np.ascontiguousarray(self.env.env.query_goal(), dtype=np.float32)))
         self.stats.reset_carry()
+
+    def _call_goal_fn(self, info):
+        return tensor_arg("goal_fn's result", self.goal_fn(info), self.device, self.torch.float32, [(self.N, self.G)], contiguous=False)
+
+    def _cur_goal(self):
+        """the goal block of the next forward pass: the env's (goal scenes) or goal_fn's"""
+        return self._goal if self.goal_fn is not None else self.env.goal
+
+    def _after_step(self, info):
+        """goal_fn agents, behind env.step: (the terminal goal -- goal_fn on the end-of-step tensors, meaningful where done) and the next goal in self._goal --
+        goal_fn behind update_link_state(), where the done envs show their new episode"""
+        term = self._call_goal_fn(info).clone()
+        info.update(self.env.update_link_state())
+        self._goal.copy_(self._call_goal_fn(info))
+        return term
 
     def restart_envs(self, key: int):
         """every env reset under a draw key derived from (seed, key): what `load_state` does with the iteration number, env state not being part of a checkpoint.
@@ -326,7 +360,7 @@ class PPOAgent:
         for t in range(self.T):
             ro.obs[t].copy_(env.obs)
             if G:
-                ro.goal[t].copy_(env.goal)
+                ro.goal[t].copy_(self._cur_goal())
             self.actor.forward_device_ex(ro.obs[t].data_ptr(), self.N, ro.act[t].data_ptr(), ro.goal[t].data_ptr() if G else 0, G, logp_ptr=ro.logp[t].data_ptr(),
                                          exp_flags_ptr=ro.flags[t].data_ptr(), exp_rate=self.exp_rate, sample=True, seed=k["actor_seed"], step=k["actor_step0"] + t,
                                          stream=stream)
@@ -336,7 +370,7 @@ class PPOAgent:
             ro.reward[t].copy_(reward); ro.terminate[t].copy_(info["terminate"]); ro.done[t].copy_(done); ro.valid[t].copy_(info["valid"])
             ro.terminal_obs[t].copy_(info["terminal_obs"])
             if G:
-                ro.terminal_goal[t].copy_(info["terminal_goal"])
+                ro.terminal_goal[t].copy_(info["terminal_goal"] if self.goal_fn is None else self._after_step(info))
             if ro.amp_obs is not None:
                 ro.amp_obs[t].copy_(info["amp_obs"])
             if self.recording:                                       # rl_agent.py:463-476
@@ -345,7 +379,7 @@ class PPOAgent:
                     self.g_norm.record_device(ro.goal[t].data_ptr(), self.N)
         ro.obs[self.T].copy_(env.obs)
         if G:
-            ro.goal[self.T].copy_(env.goal)
+            ro.goal[self.T].copy_(self._cur_goal())
         return ro
 
     # ---- the update
@@ -523,8 +557,10 @@ class PPOAgent:
         limit = 40 * 30 * max(1, -(-episodes // self.N)) + 64       # no episode of the reference's scenes outlasts 40 s of 30 Hz steps
         while done_eps < episodes and steps < limit:
             for _ in range(8):                                      # one host read per eight steps
-                self.actor.forward_device_ex(env.obs.data_ptr(), self.N, actions.data_ptr(), env.goal.data_ptr() if G else 0, G, sample=False, stream=stream)
+                self.actor.forward_device_ex(env.obs.data_ptr(), self.N, actions.data_ptr(), self._cur_goal().data_ptr() if G else 0, G, sample=False, stream=stream)
                 _, reward, done, info = env.step(actions)
+                if self.goal_fn is not None:
+                    self._after_step(info)
                 st.update(reward, info["terminate"], done, info["valid"], per_step=False)
                 steps += 1
             totals = st.totals()

@@ -523,6 +523,52 @@ class BatchEnv:
         out.pop("mask")
         return out
 
+    # ---- the kinematic character at chosen times / a masked reset at a chosen start (deepmimic_amd/kin_query.py): host conveniences around the device calls
+    def kin_query(self, times, clips=None, absolute: bool = False, identity_origin: bool = False):
+        """include/dm_hip.h dm_kin_query as host arrays (float32): {"links" [N, K, J, 22], "env" [N, K, 8], "pose" [N, K, P], "vel" [N, K, P]} of the kinematic
+        character at `times`: [K] shared by all envs or [N, K]; offsets from every env's clip clock, or clip times with absolute=True (only then may `clips`, N ids,
+        name another clip of the dataset).  identity_origin: about the identity origin instead of the env's own."""
+        from . import kin_query as kq
+        from . import link_state as ls
+        t = np.ascontiguousarray(times, dtype=np.float64)
+        if t.ndim not in (1, 2) or (t.ndim == 2 and t.shape[0] != self.N):
+            raise ValueError("times must have shape [K] or [N, K]")
+        K = int(t.shape[-1])
+        J, lw, ew, P, _ = ls.dims(self)
+        specs = {"times": (t.shape, np.float64), "links": ((self.N, K, J, lw), np.float32), "env": ((self.N, K, ew), np.float32),
+                 "pose": ((self.N, K, P), np.float32), "vel": ((self.N, K, P), np.float32)}
+        init = {"times": t}
+        if clips is not None:
+            specs["clips"] = ((self.N,), np.int32); init["clips"] = np.ascontiguousarray(clips, dtype=np.int32).reshape(self.N)
+        ptr, fetch = self._dev_arrays(specs, init)
+        kq.kin_query_device(self, K, ptr["times"], ptr.get("clips", 0), kq.flags_of(t.ndim == 2, absolute, identity_origin), ptr["links"], ptr["env"], ptr["pose"], ptr["vel"])
+        out = fetch()
+        out.pop("times"); out.pop("clips", None)
+        return out
+
+    def reset_where_at(self, mask, clips=None, times=None, yaw=None, states=None, goals=None):
+        """include/dm_hip.h dm_reset_where_at from host arrays: `reset_where(mask)` where per selected env clips[i] >= 0, a finite times[i] and a finite yaw[i] are
+        taken and -1 / NaN / None are drawn.  Returns what reset_where returns and "bad": 1 if some selected env had an invalid value (that env kept every byte)."""
+        from . import kin_query as kq
+        m = (np.asarray(mask).reshape(self.N) != 0).astype(np.int32) if np.asarray(mask).dtype == bool else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.N)
+        specs, init = {"mask": ((self.N,), np.int32), "state": ((self.N, self.S), np.float32), "bad": ((1,), np.int32)}, {"mask": m}
+        for key, val, dt in (("clips", clips, np.int32), ("times", times, np.float64), ("yaw", yaw, np.float64)):
+            if val is not None:
+                specs[key] = ((self.N,), dt); init[key] = np.ascontiguousarray(val, dtype=dt).reshape(self.N)
+        if states is not None:
+            init["state"] = states
+        if self.G:
+            specs["goal"] = ((self.N, self.G), np.float32)
+            if goals is not None:
+                init["goal"] = goals
+        ptr, fetch = self._dev_arrays(specs, init)
+        kq.reset_where_at_device(self, ptr["mask"], ptr.get("clips", 0), ptr.get("times", 0), ptr.get("yaw", 0), ptr["state"], ptr.get("goal", 0), ptr["bad"])
+        out = fetch()
+        for key in ("mask", "clips", "times", "yaw"):
+            out.pop(key, None)
+        out["bad"] = int(out["bad"][0])
+        return out
+
     def set_terminal_outputs(self, term_states_ptr: int = 0, term_goals_ptr: int = 0):
         """include/dm_hip.h dm_set_terminal_outputs: bind device buffers (raw pointers: N x S float32, and N x G float32 for a goal scene) that every
         auto-reset launch fills, for the envs it resets, with RecordState / RecordGoal of the moment the episode ended; (0, 0) unbinds.  Rows of envs that

@@ -3153,27 +3153,12 @@ __global__ void __launch_bounds__(64) k_time_warp_sample(ModelDev<Real> m, EnvSt
 //   pose, vel [N][P]: what the link state was computed from;  obj [N][LS_OBJ_W]: the free body of an OBJ class (position, rotation w x y z, linear, angular velocity)
 // An env's J x LS_LINK_W block is contiguous: lane j stages row j in LDS and the wave writes the block with consecutive lanes on consecutive words.  No atomics, one
 // summation order: two launches give the same bytes.  (LS_*: the row widths, dm_types.h)
+// The write-out k_link_state and k_kin_query share, behind kinematics(p, v): row `row` of every output that is not null.  `stage`: J x LS_LINK_W words of LDS.
 template <typename Real, typename C>
-__global__ void __launch_bounds__(64) k_link_state(ModelDev<Real> m, EnvState<Real> st, int which, float* links, float* env_out, float* pose_out, float* vel_out, float* obj_out) {
-    __shared__ Lds<Real, C> lds;
-    __shared__ float stage[C::NJ * LS_LINK_W];
-    const int e = blockIdx.x, l = threadIdx.x, J = m.J;
-    EnvSim<Real, C> sim(m, lds, l);
-    sim.load(st, e);
-    const Real* p = lds.pose; const Real* v = lds.vel;
-    if (which == 1) {
-        Real* kp = sim.scratch(); Real* kv = kp + C::NP;
-        if (st.goal && m.num_clips > 1) {
-            const ModelDev<Real> mc = sim.model_of_clip((int)st.goal[(size_t)e * GS_WIDTH + GS_CLIP]);
-            EnvSim<Real, C> cs(mc, lds, l);
-            cs.li = sim.li;
-            cs.kin_sample(lds.clk[CLK_KIN], kp, kv);
-        } else sim.kin_sample(lds.clk[CLK_KIN], kp, kv);
-        p = kp; v = kv;
-    }
-    sim.kinematics(p, v, sim.zero3());
+DM_DEV void link_state_write(EnvSim<Real, C>& sim, Lds<Real, C>& lds, float* stage, const Real* p, const Real* v, int contact, size_t row,
+                             float* links, float* env_out, float* pose_out, float* vel_out) {
+    const int l = threadIdx.x, J = sim.m.J, P = sim.m.P;
     Real* red = sim.scratch() + 2 * C::NP;            // J x 6: mass * COM, mass * COM velocity (behind the kin pose / vel; Lds::Lt holds 2 NP + 7 NJ words)
-    const int contact = (which == 0) ? lds.flg[FLG_CONTACT] : 0;
     if (l < J) {
         const V3<Real> com = ld3(lds.com[l]), vc = sim.link_vcom(l), w = ld3(lds.w[l]), pj = ld3(lds.p[l]);
         const Real mj = lds.mdl.mass[l];
@@ -3188,20 +3173,89 @@ __global__ void __launch_bounds__(64) k_link_state(ModelDev<Real> m, EnvState<Re
         o[21] = ((contact >> l) & 1) ? 1.0f : 0.0f;
     }
     sim.sync();
-    if (links) { float* o = links + (size_t)e * J * LS_LINK_W; for (int i = l; i < J * LS_LINK_W; i += kWave) o[i] = stage[i]; }
+    if (links) { float* o = links + row * J * LS_LINK_W; for (int i = l; i < J * LS_LINK_W; i += kWave) o[i] = stage[i]; }
     if (env_out && l == 0) {
         V3<Real> c = sim.zero3(), cv = c; Real tm = 0;
         for (int j = 0; j < J; ++j) { c = c + ld3(red + j * 6); cv = cv + ld3(red + j * 6 + 3); tm += lds.mdl.mass[j]; }
         c = ((Real)1 / tm) * c; cv = ((Real)1 / tm) * cv;
-        float* o = env_out + (size_t)e * LS_ENV_W;
+        float* o = env_out + row * LS_ENV_W;
         o[0] = (float)c.x; o[1] = (float)c.y; o[2] = (float)c.z; o[3] = (float)cv.x; o[4] = (float)cv.y; o[5] = (float)cv.z;
         o[6] = (float)calc_heading(ldq(p + 3)); o[7] = 0.0f;
     }
-    for (int i = l; i < m.P; i += kWave) {
-        if (pose_out) pose_out[(size_t)e * m.P + i] = (float)p[i];
-        if (vel_out) vel_out[(size_t)e * m.P + i] = (float)v[i];
+    for (int i = l; i < P; i += kWave) {
+        if (pose_out) pose_out[row * P + i] = (float)p[i];
+        if (vel_out) vel_out[row * P + i] = (float)v[i];
     }
+}
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_link_state(ModelDev<Real> m, EnvState<Real> st, int which, float* links, float* env_out, float* pose_out, float* vel_out, float* obj_out) {
+    __shared__ Lds<Real, C> lds;
+    __shared__ float stage[C::NJ * LS_LINK_W];
+    const int e = blockIdx.x, l = threadIdx.x;
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.load(st, e);
+    const Real* p = lds.pose; const Real* v = lds.vel;
+    if (which == 1) {
+        Real* kp = sim.scratch(); Real* kv = kp + C::NP;
+        if (st.goal && m.num_clips > 1) {
+            const ModelDev<Real> mc = sim.model_of_clip((int)st.goal[(size_t)e * GS_WIDTH + GS_CLIP]);
+            EnvSim<Real, C> cs(mc, lds, l);
+            cs.li = sim.li;
+            cs.kin_sample(lds.clk[CLK_KIN], kp, kv);
+        } else sim.kin_sample(lds.clk[CLK_KIN], kp, kv);
+        p = kp; v = kv;
+    }
+    sim.kinematics(p, v, sim.zero3());
+    link_state_write(sim, lds, stage, p, v, (which == 0) ? lds.flg[FLG_CONTACT] : 0, (size_t)e, links, env_out, pose_out, vel_out);
     if (C::OBJ && obj_out && l < LS_OBJ_W) obj_out[(size_t)e * LS_OBJ_W + l] = (float)lds.obj[C::OBJ ? l : 0];
+}
+
+// The kinematic character at K times per env (include/dm_hip.h dm_kin_query): the frames k_link_state's which = 1 computes at the env's clip clock, at times the
+// caller hands in.  One wavefront per env: the env record and the model tables are loaded once, then every frame is kin_sample + kinematics + the staged write-out of
+// k_link_state into row e * K + k of the outputs (links [N][K][J][LS_LINK_W], env [N][K][LS_ENV_W], pose, vel [N][K][P]; any may be null).
+//   times  [K], or [N][K] with KQ_TIMES_PER_ENV: an offset added to the env's CLK_KIN, or a clip time with KQ_TIMES_ABSOLUTE
+//   clips  [N] or null (KQ_TIMES_ABSOLUTE only, the host refuses it otherwise): the clip of the dataset to sample; null: the env's own, as k_link_state picks it
+//   KQ_ORIGIN_IDENTITY: about the identity origin instead of the env's kin row (the copy in LDS is overwritten; nothing is stored back)
+// A non-finite time or a clip id outside [0, num_clips) gives NaN rows for that (env, k); the tests stand before any table is indexed, and both are wave-uniform.
+// kin_sample(t) is cKinCharacter::CalcPose / CalcVel: cycle x cycle_delta on a looping clip, clamped and at rest past the end of one that does not loop; the root
+// sync of a phase wrap between the env's clock and t is not anticipated.  No atomics: two launches give the same bytes.
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_kin_query(ModelDev<Real> m, EnvState<Real> st, int K, const double* times, const int* clips, int flags,
+                                                  float* links, float* env_out, float* pose_out, float* vel_out) {
+    __shared__ Lds<Real, C> lds;
+    __shared__ float stage[C::NJ * LS_LINK_W];
+    const int e = blockIdx.x, l = threadIdx.x, J = m.J;
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.load(st, e);
+    int clip = (st.goal && m.num_clips > 1) ? (int)st.goal[(size_t)e * GS_WIDTH + GS_CLIP] : 0;
+    bool bad_clip = false;
+    if (clips) { clip = clips[e]; bad_clip = clip < 0 || clip >= m.num_clips; if (bad_clip) clip = 0; }
+    const ModelDev<Real> mc = sim.model_of_clip(clip);
+    EnvSim<Real, C> cs(mc, lds, l);
+    cs.li = sim.li;
+    const double base = (flags & KQ_TIMES_ABSOLUTE) ? 0.0 : lds.clk[CLK_KIN];
+    if (flags & KQ_ORIGIN_IDENTITY) {
+        sim.sync();
+        if (l == 0) { lds.kin[0] = lds.kin[1] = lds.kin[2] = 0; lds.kin[3] = 1; lds.kin[4] = lds.kin[5] = lds.kin[6] = 0; }
+        sim.sync();
+    }
+    const double* tk = times + ((flags & KQ_TIMES_PER_ENV) ? (size_t)e * K : 0);
+    Real* kp = sim.scratch(); Real* kv = kp + C::NP;
+    for (int k = 0; k < K; ++k) {
+        const size_t row = (size_t)e * K + k;
+        const double t = (flags & KQ_TIMES_ABSOLUTE) ? tk[k] : base + tk[k];
+        if (bad_clip || !(t - t == 0.0)) {             // (t - t: NaN for NaN and for either infinity)
+            const float nan = __builtin_nanf("");
+            if (links) for (int i = l; i < J * LS_LINK_W; i += kWave) links[row * J * LS_LINK_W + i] = nan;
+            if (env_out && l < LS_ENV_W) env_out[row * LS_ENV_W + l] = nan;
+            for (int i = l; i < m.P; i += kWave) { if (pose_out) pose_out[row * m.P + i] = nan; if (vel_out) vel_out[row * m.P + i] = nan; }
+            continue;
+        }
+        cs.kin_sample(t, kp, kv);
+        sim.kinematics(kp, kv, sim.zero3());
+        link_state_write(sim, lds, stage, (const Real*)kp, (const Real*)kv, 0, row, links, env_out, pose_out, vel_out);
+        sim.sync();                                    // the next frame overwrites kp / kv / the staging block
+    }
 }
 
 // The start of a new episode for the envs a device mask selects (include/dm_hip.h dm_reset_where): what a DM_AUTO_RESET launch does behind pass 0 of its emit loop,
@@ -3227,6 +3281,73 @@ __global__ void __launch_bounds__(64) k_env_reset_where(ModelDev<Real> m, EnvSta
     sim.emit(io, DebugTaps<Real>(), e, false);
     if (st.goal && m.scene_goal) {
         sim.emit_goal(io, st, e, false);      // (ends behind a barrier: the row lane 0 stored is visible to this workgroup's loads, as in emit_terminal)
+        if (goals && goals_own && l < m.goal_dim) goals[(size_t)e * m.goal_dim + l] = goals_own[(size_t)e * m.goal_dim + l];
+    }
+    sim.store(st, e);
+}
+
+// The scene reset of k_env_reset_where_at for an env whose clip (gc >= 0), clip time (has_t) or yaw (has_y) the caller gave: the steps of reset_episode /
+// reset_goal_env written out beside them (threading the three values through those two would change every AMP two-per-wave object, see reset_episode).  No recovery
+// episode -- the rule reset_episode applies to a given kin_time.  The time limit is drawn as always (stream 1); a clip that is not given by weight (stream 3); a time
+// that is not given uniformly over the clip the episode starts on (stream 0 -- the caller named the clip, or the time belongs to the one drawn here; the reference's
+// "duration of the clip before the reset" is the rule of its own draw order only); a yaw that is not given is 0 beside a given time (dm_reset's rule), else the
+// scene's (enable_rand_rot_reset, stream 4).  An env without a goal row (single clip, no yaw rule) takes the same path: model_of_clip(0) is the model itself.
+template <typename Real, typename C>
+DM_DEV void reset_episode_at(EnvSim<Real, C>& sim, Lds<Real, C>& lds, const EnvState<Real>& st, int e, double* pert, bool lane0, int gc, bool has_t, double gt, bool has_y, double gy) {
+    const ModelDev<Real>& m = sim.m;
+    const uint64_t ep = (uint64_t)lds.flg[FLG_EPISODE];
+    const double* grow = st.goal ? st.goal + (size_t)e * GS_WIDTH : nullptr;
+    const double mt = draw_time_limit<true>(m, e, ep, grow);
+    const bool own = grow && grow[GS_KON] != 0.0;              // (dm_set_env_keys)
+    const uint64_t gid = own ? 0ull : (uint64_t)(e + m.env_off), ksd = own ? (uint64_t)grow[GS_KSEED] : m.seed;
+    const int clip = gc >= 0 ? gc : sim.draw_clip(dm_rand01(ksd, gid, ep, 3));
+    const ModelDev<Real> mc = sim.model_of_clip(clip);
+    const double kt = has_t ? gt : mc.duration * dm_rand01(ksd, gid, ep, 0);
+    const Real yaw = has_y ? (Real)gy : (m.enable_rand_rot_reset && !has_t) ? (Real)(-3.141592653589793 + 6.283185307179586 * dm_rand01(ksd, gid, ep, 4)) : (Real)0;
+    if (st.goal) sim.obj_reset(st, e);             // dribble_amp: the ball first, around the OLD root (cSceneDribbleAMP::Reset)
+    EnvSim<Real, C> rs(mc, lds, sim.l);
+    rs.li = sim.li;
+    rs.reset_env(kt, mt, yaw);
+    sim.manif_clear(st, e);
+    if (st.hist) rs.init_hist(st, e);
+    if (st.goal) {
+        if (lane0) st.goal[(size_t)e * GS_WIDTH + GS_CLIP] = (double)clip;
+        sim.clip = clip;
+        if (m.scene_goal) sim.goal_reset(st, e);
+    }
+    if (pert && lane0) sim.pert_reset(pert, e);
+}
+
+// dm_reset_where with the start handed in (include/dm_hip.h dm_reset_where_at): per selected env clips[e] >= 0, a finite times[e], a finite yaws[e] are taken; -1, NaN
+// or a null array are drawn.  Nothing given: exactly k_env_reset_where (reset_episode, recovery episodes included).  Anything given: reset_episode_at.  An env with
+// an invalid value -- a clip id >= num_clips or < -1, a negative or infinite time, an infinite yaw -- returns before it touches anything, as an unselected one does,
+// and lane 0 stores 1 to bad[0] (null: not wanted): the same value from any wave, a plain store, and the caller zeroes the word.  All tests are wave-uniform.
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_env_reset_where_at(ModelDev<Real> m, EnvState<Real> st, const int* mask, const int* clips, const double* times, const double* yaws,
+                                                           float* states, float* goals_own, float* goals, int* bad) {
+    __shared__ Lds<Real, C> lds;
+    const int e = blockIdx.x, l = threadIdx.x;
+    if (mask[e] == 0) return;
+    const int gc = clips ? clips[e] : -1;
+    const double gt = times ? times[e] : (double)NAN, gy = yaws ? yaws[e] : (double)NAN;
+    const bool has_t = gt == gt, has_y = gy == gy;
+    if (gc < -1 || gc >= m.num_clips || (has_t && !(gt >= 0.0 && gt - gt == 0.0)) || (has_y && !(gy - gy == 0.0))) {
+        if (bad && l == 0) bad[0] = 1;
+        return;
+    }
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.load(st, e);
+    if (l == 0 && !lds.flg[FLG_VALID]) lds.flg[FLG_OVER] = 2;      // (as k_env_reset_where)
+    sim.sync();
+    if (st.goal) sim.goal_sync_flags(st, e);
+    double* pert = st.pert ? st.pert + (size_t)e * PT_WIDTH : nullptr;
+    if (gc < 0 && !has_t && !has_y) reset_episode<true, true>(sim, st, e, pert, l == 0);
+    else reset_episode_at(sim, lds, st, e, pert, l == 0, gc, has_t, gt, has_y, gy);
+    StepIO<Real> io = StepIO<Real>();
+    io.states = states; io.goals = goals_own;
+    sim.emit(io, DebugTaps<Real>(), e, false);
+    if (st.goal && m.scene_goal) {
+        sim.emit_goal(io, st, e, false);
         if (goals && goals_own && l < m.goal_dim) goals[(size_t)e * m.goal_dim + l] = goals_own[(size_t)e * m.goal_dim + l];
     }
     sim.store(st, e);

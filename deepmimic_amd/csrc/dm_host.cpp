@@ -324,13 +324,16 @@ struct LaunchTable {
     decltype(&launch_time_warp_sample<Real, ClsBiped>) tw_sample[kNumCls];
     decltype(&launch_link_state<Real, ClsBiped>) link_state[kNumCls];
     decltype(&launch_reset_where<Real, ClsBiped>) reset_where[kNumCls];
+    decltype(&launch_kin_query<Real, ClsBiped>) kin_query[kNumCls];
+    decltype(&launch_reset_where_at<Real, ClsBiped>) reset_where_at[kNumCls];
     int base[kNumCls];
-    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, link_state{}, reset_where{}, base{} {
+    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, link_state{}, reset_where{}, kin_query{}, reset_where_at{}, base{} {
 #define DM_ROW(id, pack, Cls, V) if (!step[k##Cls][V][pack - 1].launch) step[k##Cls][V][pack - 1] = {id, &launch_step_family<Real, id>};      // (of two rows for one combination the first is dispatched)
         DM_STEP_FAMILIES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls) reset[k##Cls] = &launch_reset<Real, Cls>; query[k##Cls] = &launch_query<Real, Cls>; probe[k##Cls] = &launch_probe<Real, Cls>; \
-                    link_state[k##Cls] = &launch_link_state<Real, Cls>; reset_where[k##Cls] = &launch_reset_where<Real, Cls>;
+                    link_state[k##Cls] = &launch_link_state<Real, Cls>; reset_where[k##Cls] = &launch_reset_where<Real, Cls>; \
+                    kin_query[k##Cls] = &launch_kin_query<Real, Cls>; reset_where_at[k##Cls] = &launch_reset_where_at<Real, Cls>;
         DM_MISC_CLASSES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls) expert[k##Cls] = &launch_amp_expert<Real, Cls>; tw_sample[k##Cls] = &launch_time_warp_sample<Real, Cls>;
@@ -393,6 +396,8 @@ struct CtxBase {
     virtual int time_warp_sample(void* samples_dev, int* count_dev, const int* restart_dev, int capacity, int* overflow_dev) = 0;      // dm_time_warp.h
     virtual int link_state(int which, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev, float* obj_dev) = 0;      // dm_link_state.h
     virtual int reset_where(const int* mask_dev, float* states_dev, float* goals_dev) = 0;
+    virtual int kin_query(int K, const double* times_dev, const int* clips_dev, int flags, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev) = 0;      // dm_kin_query.h
+    virtual int reset_where_at(const int* mask_dev, const int* clips_dev, const double* times_dev, const double* yaw_dev, float* states_dev, float* goals_dev, int* bad_dev) = 0;
     virtual bool has_obj() const = 0; virtual bool has_tape() const = 0;
     virtual int probe(int what, double dt) = 0;
     virtual int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) = 0;
@@ -697,6 +702,14 @@ struct CtxT : CtxBase {
     }
     int reset_where(const int* mask_dev, float* states_dev, float* goals_dev) override {
         launch_table<Real>().reset_where[cls](N, stream, md, st, mask_dev, states_dev, d_goals, goals_dev);
+        return 0;
+    }
+    int kin_query(int K, const double* times_dev, const int* clips_dev, int flags, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev) override {
+        launch_table<Real>().kin_query[cls](N, stream, md, st, K, times_dev, clips_dev, flags, links_dev, env_dev, pose_dev, vel_dev);
+        return 0;
+    }
+    int reset_where_at(const int* mask_dev, const int* clips_dev, const double* times_dev, const double* yaw_dev, float* states_dev, float* goals_dev, int* bad_dev) override {
+        launch_table<Real>().reset_where_at[cls](N, stream, md, st, mask_dev, clips_dev, times_dev, yaw_dev, states_dev, d_goals, goals_dev, bad_dev);
         return 0;
     }
     bool has_obj() const override { return st.obj != nullptr; }
@@ -1492,6 +1505,7 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_train_gated.h"   // the same updates for the gated nets of the AMP task agents (after dm_train.h: its head, fold and gradient kernels)
 #include "dm_optim.h"         // Adam, global-norm clipping and the non-finite guard: one optimiser step for every trainer (after dm_train_gated.h: the layouts, train_refresh)
 #include "dm_link_state.h"   // link states as device tensors and the reset selected by a device mask: the entry points of k_link_state / k_env_reset_where
+#include "dm_kin_query.h"    // the kinematic character at caller-given times and a masked reset at a caller-given start: the entry points of k_kin_query / k_env_reset_where_at
 #include "dm_time_warp.h"    // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs
 

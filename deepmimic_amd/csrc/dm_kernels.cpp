@@ -56,6 +56,14 @@ template <typename Real, typename C>
 void launch_reset_where(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, float* states, float* goals_own, float* goals) {
     RT_LAUNCH((k_env_reset_where<Real, C>), grid, s, m, st, mask, states, goals_own, goals);
 }
+template <typename Real, typename C>
+void launch_kin_query(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, int K, const double* times, const int* clips, int flags, float* links, float* env_out, float* pose_out, float* vel_out) {
+    RT_LAUNCH((k_kin_query<Real, C>), grid, s, m, st, K, times, clips, flags, links, env_out, pose_out, vel_out);
+}
+template <typename Real, typename C>
+void launch_reset_where_at(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, const int* clips, const double* times, const double* yaws, float* states, float* goals_own, float* goals, int* bad) {
+    RT_LAUNCH((k_env_reset_where_at<Real, C>), grid, s, m, st, mask, clips, times, yaws, states, goals_own, goals, bad);
+}
 
 // this object's family (dm_families.h): the reset / query / probe family expands its class lists, any other id instantiates the launcher of its row
 #if DM_TU_F64
@@ -70,7 +78,9 @@ typedef float TuReal;
     template void launch_query<TuReal, C>(DM_STEP_ARGS);                                                                                                 \
     template void launch_probe<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const DebugTaps<TuReal>&, int, double); \
     template void launch_link_state<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, int, float*, float*, float*, float*, float*); \
-    template void launch_reset_where<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, float*, float*, float*);
+    template void launch_reset_where<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, float*, float*, float*); \
+    template void launch_kin_query<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, int, const double*, const int*, int, float*, float*, float*, float*); \
+    template void launch_reset_where_at<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, const int*, const double*, const double*, float*, float*, float*, int*);
 #define DM_INST_EXPERT(C)                                                                                                                                \
     template void launch_amp_expert<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const double*, const double*, float*, const int*);            \
     template void launch_time_warp_sample<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, TuReal*, int*, const int*, int, int*);

@@ -268,6 +268,8 @@ enum { PT_TIMER = 0, PT_NEXT, PT_DRAWS, PT_SLOT0, PT_LINK = 0, PT_FX, PT_FY, PT_
 enum { OB_PX = 0, OB_QW = 3, OB_VX = 7, OB_WX = 10, OB_WIDTH = 16 };
 // row widths of dm_link_state's float32 outputs (k_link_state, dm_device.h): per link, per env, the free body
 enum { LS_LINK_W = 22, LS_ENV_W = 8, LS_OBJ_W = 13 };
+// flags of dm_kin_query (k_kin_query, dm_device.h; DM_KIN_* of include/dm_hip.h) and its largest number of times per env
+enum { KQ_TIMES_PER_ENV = 1, KQ_TIMES_ABSOLUTE = 2, KQ_ORIGIN_IDENTITY = 4, KQ_ALL_FLAGS = 7, KQ_MAX_K = 64 };
 
 template <typename Real>
 struct EnvState {

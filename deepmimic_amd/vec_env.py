@@ -14,6 +14,7 @@ from typing import Dict, Tuple
 from .binding import stream_handle, tensor_arg
 from .core import BatchEnv
 from .episodes import EpisodeStats, decode_block, merge_blocks
+from .kin_query import KinQuery, reset_where_at_device
 from .link_state import KIN, SIM, LinkState, reset_where_device
 from .model import SceneTables
 from .time_warp import TimeWarp, buffer_size, why_no_warper
@@ -23,7 +24,7 @@ class TorchVecEnv:
     def __init__(self, tables: SceneTables, num_envs: int, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
                  updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
                  episode_bin_steps: int = 1, time_warp: bool = False, link_state: bool = False, kin_link_state: bool = False, deferred_reset: bool = False,
-                 **env_kwargs):
+                 kin_lookahead=(), **env_kwargs):
         """terminal_obs (default on): keep `terminal_obs` / `terminal_goal` tensors bound to the context (BatchEnv.set_terminal_outputs), handed out as
         info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent.
         episode_stats (default off: no extra launch, no extra key): `step` runs deepmimic_amd.episodes.EpisodeStats.update behind the step launch on the same
@@ -47,7 +48,12 @@ class TorchVecEnv:
         link states -- which then describe the END OF THE STEP for every env, finished ones included: the state a task reward has to see --, copies the `obs` /
         `goal` rows of done envs into `terminal_obs` / `terminal_goal` and resets the done envs with dm_reset_where, which overwrites those `obs` / `goal` rows with
         the new episode's.  (obs, reward, done, info) hold the same bytes as the auto-reset step's; it is three or four launches and two small torch kernels
-        instead of one launch, with no host read."""
+        instead of one launch, with no host read.
+        kin_lookahead=(o_1, ..., o_K) (default none: no extra launch, no extra key): offsets in seconds from every env's clip clock.  Wherever the kinematic link
+        state is refreshed -- in `step` and in `update_link_state()` -- dm_kin_query samples the kinematic character at clock + o_k and hands out
+        info["kin_ahead_link_state"] [N, K, J, 22], info["kin_ahead_link_env"] [N, K, 8], info["kin_ahead_pose"] / info["kin_ahead_vel"] [N, K, P]: the target
+        frames a tracking policy is fed (deepmimic_amd/kin_query.py).  `kin_query()` asks for other times, clips or the clip's own frame; `set_start_sampler()`
+        lets the task choose where new episodes start."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -88,6 +94,13 @@ class TorchVecEnv:
         self.ls = LinkState(self.env, SIM, device=self.device) if link_state else None
         self.kin_ls = LinkState(self.env, KIN, device=self.device) if kin_link_state else None
         self._done_i32 = torch.zeros(self.n, **i32) if deferred_reset else None      # dm_reset_where's mask
+        offsets = [float(o) for o in kin_lookahead]
+        self.kin_ahead = KinQuery(self.env, len(offsets), device=self.device) if offsets else None
+        self.kin_ahead_times = torch.tensor(offsets, dtype=torch.float64, device=self.device) if offsets else None
+        self._queries = {}                                          # kin_query(): one KinQuery per K
+        self._clip_table = None
+        self._start_sampler = None
+        self.start_bad = None                                       # int32 [1], set_start_sampler: becomes 1 when a sampler handed in an invalid start
 
     def _enter(self):
         h = stream_handle(self.device)
@@ -153,7 +166,10 @@ class TorchVecEnv:
                 if self.terminal_goal is not None:
                     self.torch.where(d, self.goal, self.terminal_goal, out=self.terminal_goal)
             self._done_i32.copy_(done)
-            reset_where_device(self.env, self._done_i32.data_ptr(), self.obs.data_ptr(), self.goal.data_ptr() if self.goal_dim else 0)
+            if self._start_sampler is None:
+                reset_where_device(self.env, self._done_i32.data_ptr(), self.obs.data_ptr(), self.goal.data_ptr() if self.goal_dim else 0)
+            else:
+                self._reset_at(self._start_sampler(self._done_i32, info))
         self._leave()
         if self.tw is not None:
             self._tw_restart.copy_(done)                            # (done is bool: its int32 form is both the alignment's selection and the next step's restart marks)
@@ -168,16 +184,66 @@ class TorchVecEnv:
         for ls, prefix in ((self.ls, ""), (self.kin_ls, "kin_")):
             if ls is not None:
                 info.update(ls.update().info(prefix))
+        if self.kin_ahead is not None:
+            info.update(self.kin_ahead.update(self.kin_ahead_times).info())
 
     def update_link_state(self) -> dict:
         """refresh the link-state tensors from the context's current state (e.g. behind `reset()`), on torch's current stream; returns them under their info keys"""
-        if self.ls is None and self.kin_ls is None:
-            raise RuntimeError("update_link_state needs link_state=True or kin_link_state=True")
+        if self.ls is None and self.kin_ls is None and self.kin_ahead is None:
+            raise RuntimeError("update_link_state needs link_state=True, kin_link_state=True or kin_lookahead")
         self._enter()
         info = {}
         self._link_info(info)
         self._leave()
         return info
+
+    def kin_query(self, times, clips=None, absolute: bool = False, identity_origin: bool = False) -> dict:
+        """the kinematic character at `times` (float64 tensor on this device, [K] shared by all envs or [N, K]; offsets from every env's clip clock, or clip times
+        with absolute=True -- only then may `clips`, int32 [N], name another clip of the dataset; identity_origin: the clip in its own frame), on torch's current
+        stream: {"link_state" [N, K, J, 22], "link_env" [N, K, 8], "pose", "vel" [N, K, P]}.  The tensors belong to the env and are overwritten by the next
+        call with the same K (deepmimic_amd/kin_query.py)."""
+        K = int(times.shape[-1]) if times.dim() in (1, 2) else 0
+        q = self._queries.get(K)
+        if q is None:
+            q = self._queries[K] = KinQuery(self.env, K, device=self.device)
+        self._enter()
+        q.update(times, clips, absolute=absolute, identity_origin=identity_origin)
+        self._leave()
+        return q.info(prefix="")
+
+    def clip_table(self):
+        """(durations, cdf) of the dataset's clips as float64 tensors [num_clips] on this device: what a start sampler scales its times by"""
+        if self._clip_table is None:
+            d, c = self.env.clip_table()
+            self._clip_table = (self.torch.as_tensor(d, device=self.device), self.torch.as_tensor(c, device=self.device))
+        return self._clip_table
+
+    def set_start_sampler(self, fn):
+        """let the task choose where new episodes start (deferred_reset=True only; None: back to the device's own draws).  `step` calls
+        fn(done_i32, info) -> dict before it resets the done envs -- done_i32: int32 [N], 1 where the env's episode ended in this step; info: the step's info, link
+        states included, describing the END of the step -- and resets through dm_reset_where_at with the dict's optional "clips" (int32 [N], -1: drawn), "times"
+        (float64 [N] clip times, NaN: drawn) and "yaw" (float64 [N], NaN: the scene's rule) on this device; rows of envs that are not done are ignored.  An invalid
+        value (clip id outside the dataset, negative or infinite time, infinite yaw) leaves that env as it is and sets `start_bad[0]`, which nobody reads on the
+        way: check it when a run misbehaves."""
+        if not self.deferred_reset:
+            raise ValueError("set_start_sampler needs deferred_reset=True: the in-kernel auto-reset draws every start on the device")
+        self._start_sampler = fn
+        if fn is not None and self.start_bad is None:
+            self.start_bad = self.torch.zeros(1, dtype=self.torch.int32, device=self.device)
+
+    def _reset_at(self, start):
+        t = self.torch
+        ptr = {}
+        for key, dtype in (("clips", t.int32), ("times", t.float64), ("yaw", t.float64)):
+            x = (start or {}).get(key)
+            if x is not None:
+                tensor_arg("start sampler's " + key, x, self.device, dtype, [(self.n,)])
+            ptr[key] = x.data_ptr() if x is not None else 0
+        unknown = set(start or {}) - {"clips", "times", "yaw"}
+        if unknown:
+            raise ValueError("start sampler: unknown keys %s" % sorted(unknown))
+        reset_where_at_device(self.env, self._done_i32.data_ptr(), ptr["clips"], ptr["times"], ptr["yaw"], self.obs.data_ptr(),
+                              self.goal.data_ptr() if self.goal_dim else 0, self.start_bad.data_ptr())
 
     def episode_totals(self) -> dict:
         """figures of the episodes finished since construction or the last `stats.clear_totals()` (episodes.decode_block): one device-to-host copy"""

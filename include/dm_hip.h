@@ -800,6 +800,39 @@ int dm_link_state_dims(const dm_ctx* ctx, int32_t* out /* [5] */);
 int dm_link_state(dm_ctx* ctx, int which, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev, float* obj_dev);
 int dm_reset_where(dm_ctx* ctx, const int32_t* mask_dev, float* states_dev, float* goals_dev);
 
+/* ---- The kinematic character at times the caller chooses, and a masked reset whose clip, clip time and yaw the caller may give (deepmimic_amd/csrc/dm_kin_query.h,
+ * k_kin_query and k_env_reset_where_at of dm_device.h, deepmimic_amd/kin_query.py).  As above: every pointer but the ctx is a DEVICE pointer, both calls are asynchronous
+ * on the ctx's stream, read nothing back and synchronise nothing; a refused call launches nothing and names its reason through dm_last_error.
+ *
+ * dm_kin_query: K frames of the kinematic character per env, float32 whatever the context's precision; a NULL output is skipped.  The columns are those of
+ * dm_link_state(which = 1) (dm_link_state_dims), the contact column is 0:
+ *   links_dev [N][K][J][22], env_dev [N][K][8], pose_dev, vel_dev [N][K][P]
+ *   times_dev float64 [K], shared by all envs, or [N][K] with DM_KIN_TIMES_PER_ENV.  A time is an offset added to the env's clip clock (negative offsets are allowed);
+ *             with DM_KIN_TIMES_ABSOLUTE it is a clip time.
+ *   clips_dev int32 [N], only with DM_KIN_TIMES_ABSOLUTE: the clip of the dataset to sample; NULL: the env's own clip, as dm_link_state picks it
+ *   DM_KIN_ORIGIN_IDENTITY: about the identity origin instead of the origin of the env's kin row -- the clip in its own frame
+ * A frame is cKinCharacter::CalcPose(t) / CalcVel(t) of the chosen clip about the chosen origin, then the forward kinematics of dm_link_state: a looping clip adds
+ * cycle x cycle_delta to the root, a clip that does not loop clamps to its first / last frame and its velocity is 0 from its end on.  The root sync a phase wrap of the
+ * env's clock applies (SyncKinCharNewCycle) is not anticipated.  An offset of 0 gives the bytes of dm_link_state(which = 1).  A non-finite time, or a clip id outside
+ * [0, num_clips), makes every output row of that (env, k) NaN; no table is indexed with either.  No atomics: two calls give the same bytes.
+ * Refused: a NULL ctx or times_dev; K outside [1, 64]; a scene without motion frames; clips_dev without DM_KIN_TIMES_ABSOLUTE; unknown flag bits.
+ *
+ * dm_reset_where_at: dm_reset_where for every env with mask_dev[i] != 0, where each of clip, clip time and yaw is given or drawn per env: clips_dev[i] >= 0 gives
+ * the clip (-1 or a NULL array: drawn), a finite times_dev[i] the clip time (NaN or NULL: drawn), a finite yaw_dev[i] the yaw about +y (NaN or NULL: the rule below).
+ *   nothing given:  exactly dm_reset_where, recovery episodes of a get-up scene included
+ *   anything given: a full scene reset without a recovery episode (the rule dm_reset applies to a given kin_time).  The time limit is drawn as always (stream 1); a
+ *                   clip that is not given by weight (stream 3); a time that is not given uniformly over the duration of the clip the episode starts on (stream 0);
+ *                   a yaw that is not given is 0 when the time is given, else the scene's rule (enable_rand_rot_reset, stream 4).  A given yaw applies in a plain
+ *                   scene too.  clips = 0 and a time, nothing else: the context and the rows are those of dm_reset(ids, kin_times).
+ * Invalid: a clip id >= num_clips or < -1, a negative or infinite time, an infinite yaw.  Such an env keeps every byte of its state and of its output rows, and the
+ * kernel stores 1 to bad_dev[0] (int32, may be NULL; the caller zeroes it before the call).
+ * Refused: as dm_reset_where -- a NULL ctx, mask_dev or states_dev; goals_dev on a scene without a goal; a context with a draw tape bound. */
+enum { DM_KIN_TIMES_PER_ENV = 1, DM_KIN_TIMES_ABSOLUTE = 2, DM_KIN_ORIGIN_IDENTITY = 4 };
+int dm_kin_query(dm_ctx* ctx, int K, const double* times_dev, const int32_t* clips_dev /* NULL */, int flags, float* links_dev, float* env_dev, float* pose_dev,
+                 float* vel_dev);
+int dm_reset_where_at(dm_ctx* ctx, const int32_t* mask_dev, const int32_t* clips_dev, const double* times_dev, const double* yaw_dev, float* states_dev,
+                      float* goals_dev, int32_t* bad_dev /* NULL */);
+
 /* ---- PPO actor and critic minibatch updates on the device (deepmimic_amd/csrc/dm_train.h, deepmimic_amd/train.py): PPOAgent._update_actor / _update_critic and
  * MPISolver.update (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples, so that
  * exp(logp_new - logp_old) is 1 (to rounding) at the weights that sampled.  Stateless like dm_ppo_*, dm_replay_* and dm_episode_stats: the caller owns every byte, all
