@@ -569,6 +569,55 @@ class BatchEnv:
         out["bad"] = int(out["bad"][0])
         return out
 
+    # ---- a pool of whole env records (deepmimic_amd/state_pool.py): host conveniences around the device calls; the pool is a host array that travels with each call
+    def state_pool(self, slots: int):
+        """an empty pool of `slots` records of this context: uint8 [slots, slot bytes] (include/dm_hip.h dm_state_pool_bytes)"""
+        from . import state_pool as sp
+        return np.zeros((int(slots), sp.pool_bytes(self, 1)), np.uint8)
+
+    def _pool_call(self, pool, mask, slots):
+        from . import state_pool as sp
+        pool = np.ascontiguousarray(pool, dtype=np.uint8)
+        if pool.ndim != 2 or pool.shape[0] < 1 or pool.shape[1] != sp.pool_bytes(self, 1):
+            raise ValueError("pool must be a uint8 array [slots, %d]: a pool of this scene and precision" % sp.pool_bytes(self, 1))
+        m = (np.asarray(mask).reshape(self.N) != 0).astype(np.int32) if np.asarray(mask).dtype == bool else np.ascontiguousarray(mask, dtype=np.int32).reshape(self.N)
+        specs = {"pool": (pool.shape, np.uint8), "mask": ((self.N,), np.int32), "slots": ((self.N,), np.int32), "bad": ((1,), np.int32)}
+        return specs, {"pool": pool, "mask": m, "slots": np.ascontiguousarray(slots, dtype=np.int32).reshape(self.N)}
+
+    def state_save(self, pool, mask, slots):
+        """include/dm_hip.h dm_state_save from host arrays: the envs with mask[i] != 0 write their record into slot slots[i].  Returns (the pool with those slots
+        written, bad) -- bad: 1 if some selected env named a slot outside the pool (nothing was written for it)."""
+        from . import state_pool as sp
+        specs, init = self._pool_call(pool, mask, slots)
+        ptr, fetch = self._dev_arrays(specs, init)
+        sp.save_device(self, ptr["pool"], init["pool"].shape[0], ptr["mask"], ptr["slots"], ptr["bad"])
+        out = fetch()
+        return out["pool"], int(out["bad"][0])
+
+    def state_restore(self, pool, mask, slots, new_episode: bool = False, states=None, goals=None, want_states: bool = True, want_goals: bool = True):
+        """include/dm_hip.h dm_state_restore from host arrays: the envs with mask[i] != 0 take the record of slot slots[i], as stored (new_episode=False:
+        DM_POOL_REWIND) or as the start of a new episode (DM_POOL_NEW_EPISODE).  Returns {"state" [N, S]}, in a goal scene {"goal" [N, G]} -- rows of the selected
+        envs hold RecordState / RecordGoal of the restored state, the others what `states` / `goals` held (zeros if not given); want_states / want_goals=False pass
+        NULL for that output -- and "bad": 1 if some selected env named a slot outside the pool (that env kept every byte)."""
+        from . import state_pool as sp
+        specs, init = self._pool_call(pool, mask, slots)
+        if want_states:
+            specs["state"] = ((self.N, self.S), np.float32)
+            if states is not None:
+                init["state"] = states
+        if self.G and want_goals:
+            specs["goal"] = ((self.N, self.G), np.float32)
+            if goals is not None:
+                init["goal"] = goals
+        ptr, fetch = self._dev_arrays(specs, init)
+        sp.restore_device(self, ptr["pool"], init["pool"].shape[0], ptr["mask"], ptr["slots"], sp.NEW_EPISODE if new_episode else sp.REWIND,
+                          ptr.get("state", 0), ptr.get("goal", 0), ptr["bad"])
+        out = fetch()
+        for key in ("pool", "mask", "slots"):
+            out.pop(key)
+        out["bad"] = int(out["bad"][0])
+        return out
+
     def set_terminal_outputs(self, term_states_ptr: int = 0, term_goals_ptr: int = 0):
         """include/dm_hip.h dm_set_terminal_outputs: bind device buffers (raw pointers: N x S float32, and N x G float32 for a goal scene) that every
         auto-reset launch fills, for the envs it resets, with RecordState / RecordGoal of the moment the episode ended; (0, 0) unbinds.  Rows of envs that

@@ -3353,6 +3353,131 @@ __global__ void __launch_bounds__(64) k_env_reset_where_at(ModelDev<Real> m, Env
     sim.store(st, e);
 }
 
+// ---- the device state pool (include/dm_hip.h dm_state_save / dm_state_restore; the slot layout: StatePoolLayout, dm_types.h)
+// One segment between an env row and a slot, consecutive lanes on consecutive words.  16-byte accesses only where both sides and the length allow them (a test on
+// the addresses, wave-uniform): the env rows of width P or D start wherever e * P falls, and a misaligned vector access takes the slow path on the device and faults
+// the emulator (NOTES.md).  Lengths are multiples of 4 bytes.
+struct alignas(16) PoolQuad { uint32_t w[4]; };
+DM_DEV void pool_copy(void* dst, const void* src, size_t bytes) {
+    const int l = threadIdx.x;
+    if ((((uintptr_t)dst | (uintptr_t)src | (uintptr_t)bytes) & 15) == 0) {
+        PoolQuad* d = static_cast<PoolQuad*>(dst); const PoolQuad* s = static_cast<const PoolQuad*>(src);
+        for (int i = l; i < (int)(bytes / 16); i += kWave) d[i] = s[i];
+    } else {
+        uint32_t* d = static_cast<uint32_t*>(dst); const uint32_t* s = static_cast<const uint32_t*>(src);
+        for (int i = l; i < (int)(bytes / 4); i += kWave) d[i] = s[i];
+    }
+}
+
+// The envs a device mask selects write their record into slot slots[e] of the caller's pool of M slots.  Grid N; a workgroup whose mask word is 0 returns before it
+// touches anything, one whose slot is outside [0, M) too, and its lane 0 stores 1 to bad[0] (null: not wanted; the convention of k_env_reset_where_at).  Both tests
+// are wave-uniform.  Whole rows are copied, the per-env columns included (k_state_restore leaves those out).  Two envs of one call that name the same slot break the
+// caller's contract: that slot's content is then unspecified (some mixture of their words), nothing else is touched.  No EnvSim, no LDS, no atomics.
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_state_save(ModelDev<Real> m, EnvState<Real> st, StatePoolLayout lay, unsigned char* pool, int M, const int* mask, const int* slots, int* bad) {
+    const int e = blockIdx.x, l = threadIdx.x;
+    if (mask[e] == 0) return;
+    const int sl = slots[e];
+    if (sl < 0 || sl >= M) {
+        if (bad && l == 0) bad[0] = 1;
+        return;
+    }
+    unsigned char* rec = pool + (size_t)sl * lay.bytes;
+    const size_t R = sizeof(Real), P = m.P;
+    pool_copy(rec + lay.off[SP_POSE], st.pose + e * P, P * R);
+    pool_copy(rec + lay.off[SP_VEL], st.vel + e * P, P * R);
+    pool_copy(rec + lay.off[SP_TAR], st.tar + e * P, P * R);
+    pool_copy(rec + lay.off[SP_TAU], st.tau + (size_t)e * m.D, m.D * R);
+    pool_copy(rec + lay.off[SP_KIN], st.kin + (size_t)e * 8, 8 * R);
+    pool_copy(rec + lay.off[SP_CLOCK], st.clock + (size_t)e * 6, 6 * sizeof(double));
+    pool_copy(rec + lay.off[SP_FLAG], st.flag + (size_t)e * 4, 4 * sizeof(int));
+    if (st.hist) pool_copy(rec + lay.off[SP_HIST], st.hist + e * 2 * P, 2 * P * R);
+    if (st.obj) pool_copy(rec + lay.off[SP_OBJ], st.obj + (size_t)e * OB_WIDTH, OB_WIDTH * R);
+    if (st.goal) pool_copy(rec + lay.off[SP_GOAL], st.goal + (size_t)e * GS_WIDTH, GS_WIDTH * sizeof(double));
+    if (st.pert) pool_copy(rec + lay.off[SP_PERT], st.pert + (size_t)e * PT_WIDTH, PT_WIDTH * sizeof(double));
+    if (st.manif) pool_copy(rec + lay.off[SP_MANIF], st.manif + (size_t)e * m.J * MF_STRIDE, (size_t)m.J * MF_STRIDE * R);
+}
+
+// SP_NEW_EPISODE of k_state_restore: a new episode that starts where the slot's env stood, written out beside reset_episode_at (reset_episode, reset_env and
+// reset_goal_env stay as they are).  The env record in LDS holds the slot's rows and the destination's own episode counter.  What a reset does to the episode and
+// nothing of what it does to the scene: the time limit is drawn with the destination's counter (stream 1) and the timer starts over, the counter advances by one,
+// valid is 1 and the over and contact latches are cleared as reset_env clears them, the pose history is the kinematic character one control period before the slot's
+// control clock (init_hist, on the slot's clip).  Pose, velocity, targets, latched torque, kin origin, the kin and control clocks, the action flag, clip, goal, free
+// body, active perturbation forces and manifolds stay the slot's; the goal and perturbation draw counters were left the destination's by the copy.
+template <typename Real, typename C>
+DM_DEV void start_episode_from_record(EnvSim<Real, C>& sim, Lds<Real, C>& lds, const EnvState<Real>& st, int e, bool lane0) {
+    const ModelDev<Real>& m = sim.m;
+    const uint64_t ep = (uint64_t)lds.flg[FLG_EPISODE];
+    const double* grow = st.goal ? st.goal + (size_t)e * GS_WIDTH : nullptr;
+    const double mt = draw_time_limit<true>(m, e, ep, grow);
+    sim.sync();                            // every lane has read the episode counter
+    if (lane0) {
+        lds.clk[CLK_TIMER] = 0; lds.clk[CLK_TIMER_MAX] = mt;
+        lds.flg[FLG_CONTACT] = 0; lds.flg[FLG_VALID] = 1; lds.flg[FLG_OVER] = 0; lds.flg[FLG_EPISODE] += 1;
+    }
+    sim.sync();
+    if (st.hist) {
+        const ModelDev<Real> mc = sim.model_of_clip(grow ? (int)grow[GS_CLIP] : 0);
+        EnvSim<Real, C> rs(mc, lds, sim.l);
+        rs.li = sim.li;
+        rs.init_hist(st, e);
+    }
+}
+
+// The envs a device mask selects take the record of slot slots[e] (many envs may name one slot); grid, mask and the invalid-slot return as k_state_save.  The slot's
+// rows go to the env's rows in HBM, except what belongs to the env and not to its state: the diagnostic counters beside the windows (kin column 7, clock column 5)
+// and the env's own draw keys (GS_KSEED, GS_KON, PT_KSEED; dm_set_env_keys).  Behind a barrier the record is loaded as every kernel loads it, the FLG_OVER latch is
+// rebuilt from valid == 0 and pass 1 of emit writes RecordState into row e of `states` (null: not wanted), RecordGoal into the context's last-goals row and row e of
+// `goals` (null: not wanted), as k_env_reset_where does behind its reset.  No reward, flag or AMP row is written.
+//   SP_REWIND:      the record as stored, the pose history included; nothing is stored back behind the emit, the env rows hold the slot's bytes
+//   SP_NEW_EPISODE: the destination keeps its episode counter and its goal / perturbation draw counters, the pose history is not copied, and
+//                   start_episode_from_record runs between load and emit; the record is stored back
+template <typename Real, typename C>
+__global__ void __launch_bounds__(64) k_state_restore(ModelDev<Real> m, EnvState<Real> st, StatePoolLayout lay, const unsigned char* pool, int M, const int* mask, const int* slots,
+                                                      int flags, float* states, float* goals_own, float* goals, int* bad) {
+    __shared__ Lds<Real, C> lds;
+    const int e = blockIdx.x, l = threadIdx.x;
+    if (mask[e] == 0) return;
+    const int sl = slots[e];
+    if (sl < 0 || sl >= M) {
+        if (bad && l == 0) bad[0] = 1;
+        return;
+    }
+    const bool fresh = (flags & SP_NEW_EPISODE) != 0;
+    const unsigned char* rec = pool + (size_t)sl * lay.bytes;
+    const size_t R = sizeof(Real), P = m.P;
+    pool_copy(st.pose + e * P, rec + lay.off[SP_POSE], P * R);
+    pool_copy(st.vel + e * P, rec + lay.off[SP_VEL], P * R);
+    pool_copy(st.tar + e * P, rec + lay.off[SP_TAR], P * R);
+    pool_copy(st.tau + (size_t)e * m.D, rec + lay.off[SP_TAU], m.D * R);
+    if (l < 7) st.kin[(size_t)e * 8 + l] = reinterpret_cast<const Real*>(rec + lay.off[SP_KIN])[l];
+    if (l < 5) st.clock[(size_t)e * 6 + l] = reinterpret_cast<const double*>(rec + lay.off[SP_CLOCK])[l];
+    if (l < 4 && !(fresh && l == FLG_EPISODE)) st.flag[(size_t)e * 4 + l] = reinterpret_cast<const int*>(rec + lay.off[SP_FLAG])[l];
+    if (st.hist && !fresh) pool_copy(st.hist + e * 2 * P, rec + lay.off[SP_HIST], 2 * P * R);
+    if (st.obj) pool_copy(st.obj + (size_t)e * OB_WIDTH, rec + lay.off[SP_OBJ], OB_WIDTH * R);
+    if (st.goal && l < GS_WIDTH && l != GS_KSEED && l != GS_KON && !(fresh && l == GS_DRAWS))
+        st.goal[(size_t)e * GS_WIDTH + l] = reinterpret_cast<const double*>(rec + lay.off[SP_GOAL])[l];
+    if (st.pert && l < PT_WIDTH && l != PT_KSEED && !(fresh && l == PT_DRAWS))
+        st.pert[(size_t)e * PT_WIDTH + l] = reinterpret_cast<const double*>(rec + lay.off[SP_PERT])[l];
+    if (st.manif) pool_copy(st.manif + (size_t)e * m.J * MF_STRIDE, rec + lay.off[SP_MANIF], (size_t)m.J * MF_STRIDE * R);
+    EnvSim<Real, C> sim(m, lds, l);
+    sim.sync();                            // the rows this workgroup stored are visible to its loads (as the goal row in k_env_reset_where)
+    sim.load(st, e);
+    if (st.goal) sim.clip = (int)st.goal[(size_t)e * GS_WIDTH + GS_CLIP];
+    if (l == 0 && !lds.flg[FLG_VALID]) lds.flg[FLG_OVER] = 2;      // (as k_env_reset_where)
+    sim.sync();
+    if (fresh) start_episode_from_record(sim, lds, st, e, l == 0);
+    if (st.goal) sim.goal_sync_flags(st, e);
+    StepIO<Real> io = StepIO<Real>();
+    io.states = states; io.goals = goals_own;
+    sim.emit(io, DebugTaps<Real>(), e, false);
+    if (st.goal && m.scene_goal) {
+        sim.emit_goal(io, st, e, false);
+        if (goals && goals_own && l < m.goal_dim) goals[(size_t)e * m.goal_dim + l] = goals_own[(size_t)e * m.goal_dim + l];
+    }
+    if (fresh) sim.store(st, e);
+}
+
 // component taps for parity tests: SPD torque for the stored state / one substep with the stored torque
 template <typename Real, typename C>
 __global__ void __launch_bounds__(64) k_env_probe(ModelDev<Real> m, EnvState<Real> st, DebugTaps<Real> dbg, int what, double dt) {

@@ -326,14 +326,17 @@ struct LaunchTable {
     decltype(&launch_reset_where<Real, ClsBiped>) reset_where[kNumCls];
     decltype(&launch_kin_query<Real, ClsBiped>) kin_query[kNumCls];
     decltype(&launch_reset_where_at<Real, ClsBiped>) reset_where_at[kNumCls];
+    decltype(&launch_state_save<Real, ClsBiped>) state_save[kNumCls];
+    decltype(&launch_state_restore<Real, ClsBiped>) state_restore[kNumCls];
     int base[kNumCls];
-    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, link_state{}, reset_where{}, kin_query{}, reset_where_at{}, base{} {
+    constexpr LaunchTable() : step{}, reset{}, query{}, probe{}, expert{}, tw_sample{}, link_state{}, reset_where{}, kin_query{}, reset_where_at{}, state_save{}, state_restore{}, base{} {
 #define DM_ROW(id, pack, Cls, V) if (!step[k##Cls][V][pack - 1].launch) step[k##Cls][V][pack - 1] = {id, &launch_step_family<Real, id>};      // (of two rows for one combination the first is dispatched)
         DM_STEP_FAMILIES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls) reset[k##Cls] = &launch_reset<Real, Cls>; query[k##Cls] = &launch_query<Real, Cls>; probe[k##Cls] = &launch_probe<Real, Cls>; \
                     link_state[k##Cls] = &launch_link_state<Real, Cls>; reset_where[k##Cls] = &launch_reset_where<Real, Cls>; \
-                    kin_query[k##Cls] = &launch_kin_query<Real, Cls>; reset_where_at[k##Cls] = &launch_reset_where_at<Real, Cls>;
+                    kin_query[k##Cls] = &launch_kin_query<Real, Cls>; reset_where_at[k##Cls] = &launch_reset_where_at<Real, Cls>; \
+                    state_save[k##Cls] = &launch_state_save<Real, Cls>; state_restore[k##Cls] = &launch_state_restore<Real, Cls>;
         DM_MISC_CLASSES(DM_ROW)
 #undef DM_ROW
 #define DM_ROW(Cls) expert[k##Cls] = &launch_amp_expert<Real, Cls>; tw_sample[k##Cls] = &launch_time_warp_sample<Real, Cls>;
@@ -398,6 +401,9 @@ struct CtxBase {
     virtual int reset_where(const int* mask_dev, float* states_dev, float* goals_dev) = 0;
     virtual int kin_query(int K, const double* times_dev, const int* clips_dev, int flags, float* links_dev, float* env_dev, float* pose_dev, float* vel_dev) = 0;      // dm_kin_query.h
     virtual int reset_where_at(const int* mask_dev, const int* clips_dev, const double* times_dev, const double* yaw_dev, float* states_dev, float* goals_dev, int* bad_dev) = 0;
+    virtual dmk::StatePoolLayout state_pool_layout() const = 0;      // dm_state_pool.h
+    virtual int state_save(void* pool_dev, int slots, const int* mask_dev, const int* slots_dev, int* bad_dev) = 0;
+    virtual int state_restore(const void* pool_dev, int slots, const int* mask_dev, const int* slots_dev, int flags, float* states_dev, float* goals_dev, int* bad_dev) = 0;
     virtual bool has_obj() const = 0; virtual bool has_tape() const = 0;
     virtual int probe(int what, double dt) = 0;
     virtual int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) = 0;
@@ -710,6 +716,15 @@ struct CtxT : CtxBase {
     }
     int reset_where_at(const int* mask_dev, const int* clips_dev, const double* times_dev, const double* yaw_dev, float* states_dev, float* goals_dev, int* bad_dev) override {
         launch_table<Real>().reset_where_at[cls](N, stream, md, st, mask_dev, clips_dev, times_dev, yaw_dev, states_dev, d_goals, goals_dev, bad_dev);
+        return 0;
+    }
+    StatePoolLayout state_pool_layout() const override { return dmk::state_pool_layout<Real>(hm.P, hm.D, hm.J, st); }
+    int state_save(void* pool_dev, int slots, const int* mask_dev, const int* slots_dev, int* bad_dev) override {
+        launch_table<Real>().state_save[cls](N, stream, md, st, state_pool_layout(), (unsigned char*)pool_dev, slots, mask_dev, slots_dev, bad_dev);
+        return 0;
+    }
+    int state_restore(const void* pool_dev, int slots, const int* mask_dev, const int* slots_dev, int flags, float* states_dev, float* goals_dev, int* bad_dev) override {
+        launch_table<Real>().state_restore[cls](N, stream, md, st, state_pool_layout(), (const unsigned char*)pool_dev, slots, mask_dev, slots_dev, flags, states_dev, d_goals, goals_dev, bad_dev);
         return 0;
     }
     bool has_obj() const override { return st.obj != nullptr; }
@@ -1506,6 +1521,7 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_optim.h"         // Adam, global-norm clipping and the non-finite guard: one optimiser step for every trainer (after dm_train_gated.h: the layouts, train_refresh)
 #include "dm_link_state.h"   // link states as device tensors and the reset selected by a device mask: the entry points of k_link_state / k_env_reset_where
 #include "dm_kin_query.h"    // the kinematic character at caller-given times and a masked reset at a caller-given start: the entry points of k_kin_query / k_env_reset_where_at
+#include "dm_state_pool.h"   // a pool of whole env records in device memory: the entry points of k_state_save / k_state_restore
 #include "dm_time_warp.h"    // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs
 

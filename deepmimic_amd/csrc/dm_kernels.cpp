@@ -64,6 +64,14 @@ template <typename Real, typename C>
 void launch_reset_where_at(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, const int* clips, const double* times, const double* yaws, float* states, float* goals_own, float* goals, int* bad) {
     RT_LAUNCH((k_env_reset_where_at<Real, C>), grid, s, m, st, mask, clips, times, yaws, states, goals_own, goals, bad);
 }
+template <typename Real, typename C>
+void launch_state_save(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, unsigned char* pool, int M, const int* mask, const int* slots, int* bad) {
+    RT_LAUNCH((k_state_save<Real, C>), grid, s, m, st, lay, pool, M, mask, slots, bad);
+}
+template <typename Real, typename C>
+void launch_state_restore(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, const unsigned char* pool, int M, const int* mask, const int* slots, int flags, float* states, float* goals_own, float* goals, int* bad) {
+    RT_LAUNCH((k_state_restore<Real, C>), grid, s, m, st, lay, pool, M, mask, slots, flags, states, goals_own, goals, bad);
+}
 
 // this object's family (dm_families.h): the reset / query / probe family expands its class lists, any other id instantiates the launcher of its row
 #if DM_TU_F64
@@ -80,7 +88,9 @@ typedef float TuReal;
     template void launch_link_state<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, int, float*, float*, float*, float*, float*); \
     template void launch_reset_where<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, float*, float*, float*); \
     template void launch_kin_query<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, int, const double*, const int*, int, float*, float*, float*, float*); \
-    template void launch_reset_where_at<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, const int*, const double*, const double*, float*, float*, float*, int*);
+    template void launch_reset_where_at<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, const int*, const double*, const double*, float*, float*, float*, int*); \
+    template void launch_state_save<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const StatePoolLayout&, unsigned char*, int, const int*, const int*, int*); \
+    template void launch_state_restore<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const StatePoolLayout&, const unsigned char*, int, const int*, const int*, int, float*, float*, float*, int*);
 #define DM_INST_EXPERT(C)                                                                                                                                \
     template void launch_amp_expert<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const double*, const double*, float*, const int*);            \
     template void launch_time_warp_sample<TuReal, C>(unsigned, rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, TuReal*, int*, const int*, int, int*);

@@ -42,6 +42,10 @@ template <typename Real, typename C>
 void launch_kin_query(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, int K, const double* times, const int* clips, int flags, float* links, float* env_out, float* pose_out, float* vel_out);
 template <typename Real, typename C>
 void launch_reset_where_at(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, const int* clips, const double* times, const double* yaws, float* states, float* goals_own, float* goals, int* bad);
+template <typename Real, typename C>
+void launch_state_save(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, unsigned char* pool, int M, const int* mask, const int* slots, int* bad);
+template <typename Real, typename C>
+void launch_state_restore(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, const unsigned char* pool, int M, const int* mask, const int* slots, int flags, float* states, float* goals_own, float* goals, int* bad);
 // test support (dm_wave_probe.h, in the object of DM_MISC_FAMILY): one wave-level primitive of dm_device.h / dm_device_duo.h per launch, `grid` wavefronts
 template <typename Real>
 void launch_wave_probe(unsigned grid, rt_stream s, int op, int arg, const double* in, double* out);

@@ -290,6 +290,25 @@ struct EnvState {
 };
 enum { MF_STRIDE = 32, MF_PT = 6 };
 
+// The device state pool (include/dm_hip.h dm_state_*; k_state_save / k_state_restore, dm_device.h).  A slot is one env's record in the context's precision: the rows of
+// EnvState the next control step or query depends on, back to back in the order of SP_*, each segment starting on a 16-byte boundary, the slot a multiple of 16 bytes.
+// No pointer, no env id: a pool copied elsewhere restores the same bytes.  aovf is scratch and has no segment; a row the context lacks has none either (offset -1).
+enum { SP_POSE = 0, SP_VEL, SP_TAR, SP_TAU, SP_KIN, SP_CLOCK, SP_FLAG, SP_HIST, SP_OBJ, SP_GOAL, SP_PERT, SP_MANIF, SP_NSEG };
+// modes of k_state_restore (DM_POOL_* of include/dm_hip.h)
+enum { SP_REWIND = 0, SP_NEW_EPISODE = 1, SP_ALL_FLAGS = 1 };
+struct StatePoolLayout { int off[SP_NSEG]; int bytes; };      // byte offsets inside a slot (-1: no such segment), slot size
+template <typename Real>
+inline StatePoolLayout state_pool_layout(int P, int D, int J, const EnvState<Real>& st) {
+    const size_t R = sizeof(Real);
+    const size_t len[SP_NSEG] = {P * R, P * R, P * R, D * R, 8 * R, 6 * sizeof(double), 4 * sizeof(int), st.hist ? 2 * P * R : 0, st.obj ? OB_WIDTH * R : 0,
+                                 st.goal ? GS_WIDTH * sizeof(double) : 0, st.pert ? PT_WIDTH * sizeof(double) : 0, st.manif ? (size_t)J * MF_STRIDE * R : 0};
+    StatePoolLayout lay;
+    size_t at = 0;
+    for (int k = 0; k < SP_NSEG; ++k) { lay.off[k] = len[k] ? (int)at : -1; at += (len[k] + 15) & ~(size_t)15; }
+    lay.bytes = (int)at;
+    return lay;
+}
+
 // Per-call I/O of the batched step (device pointers; any may be null)
 template <typename Real>
 struct StepIO {

@@ -16,8 +16,26 @@ from .core import BatchEnv
 from .episodes import EpisodeStats, decode_block, merge_blocks
 from .kin_query import KinQuery, reset_where_at_device
 from .link_state import KIN, SIM, LinkState, reset_where_device
+from . import state_pool as sp
 from .model import SceneTables
 from .time_warp import TimeWarp, buffer_size, why_no_warper
+
+
+class _EnvStatePool(sp.StatePool):
+    """the StatePool of a TorchVecEnv: the calls go to torch's current stream, and a restore writes the env's `obs` / `goal` rows unless told otherwise"""
+
+    def __init__(self, venv, slots: int):
+        super().__init__(venv.env, slots, device=venv.device)
+        self.venv = venv
+
+    def save(self, mask, slots):
+        self.venv._enter()
+        return super().save(mask, slots)
+
+    def restore(self, mask, slots, new_episode: bool = False, states=None, goals=None):
+        v = self.venv
+        v._enter()
+        return super().restore(mask, slots, new_episode=new_episode, states=v.obs if states is None else states, goals=v.goal if goals is None else goals)
 
 
 class TorchVecEnv:
@@ -53,7 +71,7 @@ class TorchVecEnv:
         state is refreshed -- in `step` and in `update_link_state()` -- dm_kin_query samples the kinematic character at clock + o_k and hands out
         info["kin_ahead_link_state"] [N, K, J, 22], info["kin_ahead_link_env"] [N, K, 8], info["kin_ahead_pose"] / info["kin_ahead_vel"] [N, K, P]: the target
         frames a tracking policy is fed (deepmimic_amd/kin_query.py).  `kin_query()` asks for other times, clips or the clip's own frame; `set_start_sampler()`
-        lets the task choose where new episodes start."""
+        lets the task choose where new episodes start; `state_pool()` keeps whole env states on the device to rewind to or to start episodes from."""
         import torch
         self.torch = torch
         self.device = torch.device(device)
@@ -101,6 +119,8 @@ class TorchVecEnv:
         self._clip_table = None
         self._start_sampler = None
         self.start_bad = None                                       # int32 [1], set_start_sampler: becomes 1 when a sampler handed in an invalid start
+        self._pool = None                                           # state_pool(): the pool a start sampler's "slots" index
+        self._pool_mask = None
 
     def _enter(self):
         h = stream_handle(self.device)
@@ -224,7 +244,11 @@ class TorchVecEnv:
         states included, describing the END of the step -- and resets through dm_reset_where_at with the dict's optional "clips" (int32 [N], -1: drawn), "times"
         (float64 [N] clip times, NaN: drawn) and "yaw" (float64 [N], NaN: the scene's rule) on this device; rows of envs that are not done are ignored.  An invalid
         value (clip id outside the dataset, negative or infinite time, infinite yaw) leaves that env as it is and sets `start_bad[0]`, which nobody reads on the
-        way: check it when a run misbehaves."""
+        way: check it when a run misbehaves.
+        With a pool (`state_pool()`) the dict may hold "slots" (int32 [N], -1: none) instead of or beside the others: a done env with slots[i] >= 0 starts a new
+        episode at the state stored in that slot (StatePool.restore(new_episode=True)) and the other done envs are reset as above -- two launches with disjoint
+        masks.  A slot index outside the pool leaves the env as it is and sets the pool's `bad[0]`.  Not with time_warp=True (a ValueError in `step`): the
+        sample buffer of a time-warp episode starts on the reference motion."""
         if not self.deferred_reset:
             raise ValueError("set_start_sampler needs deferred_reset=True: the in-kernel auto-reset draws every start on the device")
         self._start_sampler = fn
@@ -239,11 +263,32 @@ class TorchVecEnv:
             if x is not None:
                 tensor_arg("start sampler's " + key, x, self.device, dtype, [(self.n,)])
             ptr[key] = x.data_ptr() if x is not None else 0
-        unknown = set(start or {}) - {"clips", "times", "yaw"}
+        unknown = set(start or {}) - {"clips", "times", "yaw", "slots"}
         if unknown:
             raise ValueError("start sampler: unknown keys %s" % sorted(unknown))
-        reset_where_at_device(self.env, self._done_i32.data_ptr(), ptr["clips"], ptr["times"], ptr["yaw"], self.obs.data_ptr(),
+        mask, slots = self._done_i32, (start or {}).get("slots")
+        if slots is not None:
+            if self._pool is None:
+                raise ValueError("start sampler's slots need a pool: call state_pool() first")
+            if self.tw is not None:
+                raise ValueError("start sampler's slots cannot be used with time_warp=True")
+            tensor_arg("start sampler's slots", slots, self.device, t.int32, [(self.n,)])
+            if self._pool_mask is None:
+                self._pool_mask = (t.zeros_like(self._done_i32), t.zeros_like(self._done_i32))
+            from_pool, mask = self._pool_mask
+            t.mul(self._done_i32, slots >= 0, out=from_pool); t.sub(self._done_i32, from_pool, out=mask)
+        reset_where_at_device(self.env, mask.data_ptr(), ptr["clips"], ptr["times"], ptr["yaw"], self.obs.data_ptr(),
                               self.goal.data_ptr() if self.goal_dim else 0, self.start_bad.data_ptr())
+        if slots is not None:
+            sp.restore_device(self.env, self._pool.data.data_ptr(), self._pool.slots, from_pool.data_ptr(), slots.data_ptr(), sp.NEW_EPISODE, self.obs.data_ptr(),
+                              self.goal.data_ptr() if self.goal_dim else 0, self._pool.bad.data_ptr())
+
+    def state_pool(self, slots: int):
+        """a pool of `slots` whole env states on this device (deepmimic_amd/state_pool.py): `save(mask, slots)` and `restore(mask, slots, new_episode=False)` take
+        int32 (or bool) tensors [N] and run on torch's current stream without a host read; a restore writes the `obs` / `goal` rows of the restored envs.  The
+        pool made last is the one a start sampler's "slots" index (set_start_sampler)."""
+        self._pool = _EnvStatePool(self, slots)
+        return self._pool
 
     def episode_totals(self) -> dict:
         """figures of the episodes finished since construction or the last `stats.clear_totals()` (episodes.decode_block): one device-to-host copy"""

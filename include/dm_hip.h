@@ -833,6 +833,41 @@ int dm_kin_query(dm_ctx* ctx, int K, const double* times_dev, const int32_t* cli
 int dm_reset_where_at(dm_ctx* ctx, const int32_t* mask_dev, const int32_t* clips_dev, const double* times_dev, const double* yaw_dev, float* states_dev,
                       float* goals_dev, int32_t* bad_dev /* NULL */);
 
+/* ---- A pool of whole env records in device memory: save the envs a device mask selects into slots of the pool, and start envs from slots -- a rewind, or a new
+ * episode from a stored state (deepmimic_amd/csrc/dm_state_pool.h, k_state_save and k_state_restore of dm_device.h, deepmimic_amd/state_pool.py).  The pool is the
+ * caller's device memory (16-byte aligned, dm_state_pool_bytes(ctx, slots) bytes), as with dm_replay_*; save and restore are asynchronous on the ctx's stream, read
+ * nothing back and synchronise nothing; a refused call launches nothing and names its reason through dm_last_error.
+ *
+ * A slot is one env's record in the ctx's precision: the rows of the env the next control step or query depends on -- pose, vel, tar, tau, kin, clock, flag and,
+ * where the ctx has them, hist (the AMP pose history), obj (the free body), goal, pert and manif (DM-physics v2) -- back to back in that order, every segment on a
+ * 16-byte boundary, the slot a multiple of 16 bytes.  It holds no pointer and no env id: a pool copied elsewhere on the device, or to the host and back, restores
+ * the same bytes.  dm_state_pool_dims: out[0] the slot size in bytes, out[1 .. 12] the byte offset of each segment in the order above (-1: the ctx has no such row).
+ * Only contexts with equal dims may share a pool.
+ *
+ * dm_state_save: every env with mask_dev[i] != 0 writes its record into slot slots_dev[i] of pool_dev.  Two selected envs of one call that name the same slot break
+ * the contract: that slot's content is then unspecified, nothing else is touched.
+ * dm_state_restore: every env with mask_dev[i] != 0 takes the record of slot slots_dev[i]; many envs may name one slot.  Three things belong to the env and not to
+ * its state and stay as the destination has them: the diagnostic counters ("fallback", "borrowed" of dm_get_debug), the env's own draw key in the goal row and in
+ * the perturbation row (dm_set_env_keys).  Then, as dm_reset_where behind its reset, RecordState goes to row i of states_dev (may be NULL) and RecordGoal to the
+ * ctx's last-goals row and to row i of goals_dev (may be NULL); no reward, flag or AMP row is written.  flags:
+ *   DM_POOL_REWIND       the record as stored, the pose history included.  The same actions then reproduce the stored env's rollout bit for bit on the env that saved
+ *                        it; on another env of the ctx everything that is not a draw reproduces too.
+ *   DM_POOL_NEW_EPISODE  a new episode that starts at the stored state: the destination keeps its episode counter, advanced by one as a reset advances it, and its
+ *                        goal and perturbation draw counters, so that the draws behind the start do not repeat whenever a slot is used; the episode timer starts
+ *                        over (time 0, the limit drawn with the new counter as every reset draws it); the pose history is re-initialised as a reset does; valid is
+ *                        1 and the contact latch is cleared.  Pose, velocity, targets, latched torque, kin origin, the kin and control clocks, clip, goal target and
+ *                        goal timers, the free body, active perturbation forces and manifolds are the slot's.
+ * A selected env whose slot is outside [0, slots) keeps every byte of its state (a save writes nothing), and the kernel stores 1 to bad_dev[0] (int32, may be NULL;
+ * the caller zeroes it before the call).
+ * Refused: a NULL ctx, pool_dev, mask_dev or slots_dev; a pool that is not 16-byte aligned; slots <= 0; unknown flag bits; goals_dev on a scene without a goal; a
+ * context with a draw tape bound.  dm_state_pool_bytes returns a negative value when it refuses. */
+enum { DM_POOL_REWIND = 0, DM_POOL_NEW_EPISODE = 1 };
+int64_t dm_state_pool_bytes(const dm_ctx* ctx, int slots);
+int dm_state_pool_dims(const dm_ctx* ctx, int32_t* out /* [13] */);
+int dm_state_save(dm_ctx* ctx, void* pool_dev, int slots, const int32_t* mask_dev, const int32_t* slots_dev, int32_t* bad_dev /* NULL */);
+int dm_state_restore(dm_ctx* ctx, const void* pool_dev, int slots, const int32_t* mask_dev, const int32_t* slots_dev, int flags, float* states_dev /* NULL */,
+                     float* goals_dev /* NULL */, int32_t* bad_dev /* NULL */);
+
 /* ---- PPO actor and critic minibatch updates on the device (deepmimic_amd/csrc/dm_train.h, deepmimic_amd/train.py): PPOAgent._update_actor / _update_critic and
  * MPISolver.update (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples, so that
  * exp(logp_new - logp_old) is 1 (to rounding) at the weights that sampled.  Stateless like dm_ppo_*, dm_replay_* and dm_episode_stats: the caller owns every byte, all
