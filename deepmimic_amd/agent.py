@@ -144,7 +144,7 @@ class PPOAgent:
     KIND = "PPO"
 
     def __init__(self, env, cfg: AgentConfig, rollout_steps: int = 32, seed: int = 0, mini_batch_size: Optional[int] = None, optimizer: str = "momentum",
-                 init_from: Optional[str] = None, reward_fn=None, goal_fn=None, goal_dim: int = 0, **opt):
+                 init_from: Optional[str] = None, reward_fn=None, goal_fn=None, goal_dim: int = 0, push_fn=None, **opt):
         """env: a `TorchVecEnv` (an AMP agent: with amp_obs=True).  rollout_steps: T; a rollout is T x N samples, the file's BatchSize is logged next to it, not
         enforced.  mini_batch_size: M (None: the file's MiniBatchSize).  optimizer / **opt (max_grad_norm, skip_nonfinite, betas, eps): the trainers'.
         init_from: a checkpoint prefix whose nets and normalisers the agent starts from instead of random weights.
@@ -156,7 +156,11 @@ class PPOAgent:
         a goal of its own and `TorchVecEnv(..., deferred_reset=True)` with link states or kin_lookahead (info is what `env.update_link_state()` returns, plus the
         step's keys behind a step).  Per step of `collect` and `test`: env.step; reward_fn and goal_fn on the end-of-step tensors -- that goal is the terminal
         goal where done; env.update_link_state(), after which the done envs show their new episode (the others the same bytes); goal_fn again: the goal the
-        next action is taken from."""
+        next action is taken from.
+        push_fn: pushes chosen by the task -- a callable (info, t) -> None or a dict of `TorchVecEnv.push`'s arguments, called by `collect` before every env.step
+        (t: the step of the rollout) and applied with env.push(**dict); it needs `TorchVecEnv(..., pushes=True)`.  info holds the tensors the action was computed
+        from: the last step's info dict (empty before the first step behind a reset of every env) plus "obs", "goal" where there is one, and "pushes".
+        pushes.RandomPushes is such a callable.  `test` does not push.  None: `collect` does what it did."""
         import torch
         self.torch = torch
         if cfg.agent_type != self.KIND:
@@ -165,7 +169,10 @@ class PPOAgent:
         if bad:
             raise TypeError("unknown optimiser option %s" % bad[0])
         self.env, self.cfg, self.seed = env, cfg, int(seed)
-        self.reward_fn, self.goal_fn = reward_fn, goal_fn
+        self.reward_fn, self.goal_fn, self.push_fn = reward_fn, goal_fn, push_fn
+        if push_fn is not None and not getattr(env, "has_pushes", False):
+            raise ValueError("push_fn needs TorchVecEnv(..., pushes=True)")
+        self._step_info = {}                                        # push_fn: the info dict of the last env.step
         self.device = env.device
         self.T, self.N, self.S, self.G, self.A = int(rollout_steps), env.n, env.obs_dim, env.goal_dim, env.act_dim
         if goal_fn is None and goal_dim:
@@ -328,6 +335,7 @@ class PPOAgent:
         elif self.G:
             self.env.goal.copy_(self.torch.from_numpy(np.ascontiguousarray(self.env.env.query_goal(), dtype=np.float32)))
         self.stats.reset_carry()
+        self._step_info = {}
 
     def _call_goal_fn(self, info):
         return tensor_arg("goal_fn's result", self.goal_fn(info), self.device, self.torch.float32, [(self.N, self.G)], contiguous=False)
@@ -364,7 +372,10 @@ class PPOAgent:
             self.actor.forward_device_ex(ro.obs[t].data_ptr(), self.N, ro.act[t].data_ptr(), ro.goal[t].data_ptr() if G else 0, G, logp_ptr=ro.logp[t].data_ptr(),
                                          exp_flags_ptr=ro.flags[t].data_ptr(), exp_rate=self.exp_rate, sample=True, seed=k["actor_seed"], step=k["actor_step0"] + t,
                                          stream=stream)
+            if self.push_fn is not None:
+                self._push(ro, t)
             _, reward, done, info = env.step(ro.act[t])
+            self._step_info = info
             if self.reward_fn is not None:
                 reward = tensor_arg("reward_fn's result", self.reward_fn(info, reward), self.device, self.torch.float32, [(self.N,)], contiguous=False)
             ro.reward[t].copy_(reward); ro.terminate[t].copy_(info["terminate"]); ro.done[t].copy_(done); ro.valid[t].copy_(info["valid"])
@@ -381,6 +392,18 @@ class PPOAgent:
         if G:
             ro.goal[self.T].copy_(self._cur_goal())
         return ro
+
+    def _push(self, ro, t):
+        """push_fn in front of env.step: the tensors the action of step t was computed from, then the pushes it chose"""
+        info = dict(self._step_info)
+        info["obs"] = ro.obs[t]
+        if self.G:
+            info["goal"] = ro.goal[t]
+        if getattr(self.env, "pushes", None) is not None:
+            info["pushes"] = self.env.pushes
+        push = self.push_fn(info, t)
+        if push is not None:
+            self.env.push(**push)
 
     # ---- the update
     def _valid_lists(self, ro):

@@ -56,6 +56,8 @@ SIGNATURES = {
     "dm_state_pool_dims": ([_p, _pi32], None),
     "dm_state_save": ([_p, _p, _i, _p, _p, _p], None),
     "dm_state_restore": ([_p, _p, _i, _p, _p, _i, _p, _p, _p], None),
+    "dm_push_where": ([_p, _p, _p, _p, _p, _p, _i, _p], None),
+    "dm_push_state": ([_p, _p], None),
     "dm_train_param_count": ([_p], _i64),
     "dm_train_workspace_bytes": ([_p, _i], _i64),
     "dm_train_actor_grad": ([_p] * 4 + [_i] * 2 + [_p] * 8 + [_i64, _p], None),

@@ -165,8 +165,13 @@ def fill_scene_tables(tables: SceneTables, test_mode: bool = False, self_collisi
         setattr(st, k, float(getattr(c, k)))
     st.ball_mass = BALL_MASS; st.ball_friction = BALL_FRICTION * 0.9; st.ball_lin_damping = BALL_LIN_DAMPING; st.ball_ang_damping = BALL_ANG_DAMPING
     # random perturbations: with the default (infinite) interval none ever fires -- the path stays off, as in the reference
-    st.enable_rand_perturbs = int(bool(c.enable_rand_perturbs) and np.isfinite(c.perturb_time_min))
-    if st.enable_rand_perturbs:
+    # task_pushes: the rows exist either way (deepmimic_amd/pushes.py); without a finite schedule the interval handed down is infinite -- include/dm_hip.h: "the rows
+    # exist, nothing fires by itself" -- and the other ranges stay 0
+    scheduled = bool(c.enable_rand_perturbs) and bool(np.isfinite(c.perturb_time_min))
+    st.enable_rand_perturbs = int(scheduled or bool(getattr(c, "task_pushes", False)))
+    if st.enable_rand_perturbs and not scheduled:
+        st.perturb_time_min = st.perturb_time_max = float(np.inf)
+    if scheduled:
         st.perturb_time_min, st.perturb_time_max = float(c.perturb_time_min), float(c.perturb_time_max)
         st.min_perturb, st.max_perturb = float(c.min_perturb), float(c.max_perturb)
         st.min_perturb_duration, st.max_perturb_duration = float(c.min_pertrub_duration), float(c.max_perturb_duration)
@@ -195,7 +200,8 @@ class BatchEnv:
         c = tables.cfg
         st, self._keep = fill_scene_tables(tables, test_mode=test_mode, self_collision=self_collision, erp=erp, solver_iters=solver_iters)
         tmin, tmax = float(st.time_lim_min), float(st.time_lim_max)
-        self.has_perturbs = bool(st.enable_rand_perturbs)
+        self.has_perturbs = bool(st.enable_rand_perturbs)           # the context has perturbation rows (snapshots carry them)
+        self.has_pushes = self.has_perturbs                         # ... which is what push / clear_pushes / push_state need (cfg.task_pushes, or a finite random schedule)
         if c.timer_type not in ("uniform", "exp"):
             raise ValueError("unsupported timer type %r (util/Timer.cpp:27-45: uniform | exp)" % c.timer_type)
         self._timer = (c.timer_type, tmin, tmax, float(c.time_lim_exp)); self._timer_pinned = tmin == tmax
@@ -617,6 +623,25 @@ class BatchEnv:
             out.pop(key)
         out["bad"] = int(out["bad"][0])
         return out
+
+    # ---- task-chosen pushes (deepmimic_amd/pushes.py): host conveniences around the device calls
+    def push(self, mask, links, forces, durations, slots=None, frame: str = "world") -> int:
+        """include/dm_hip.h dm_push_where from host arrays: for the envs with mask[i] != 0 the force forces[i] ([N, 3], newtons; frame "world", or "heading": the
+        character's heading frame at the time of the call) acts on body part links[i] for durations[i] seconds from the next scene update on; links[i] == -1 clears.
+        slots: 0 / 1 per env, -1 or None: a free slot, else the one nearest its end.  Scalars and single rows are broadcast over the envs.  Returns bad: 1 if some
+        selected env had an invalid value (that env kept every byte)."""
+        from . import pushes
+        return pushes.push_host(self, mask, links, forces, durations, slots, frame)
+
+    def clear_pushes(self, mask=None) -> int:
+        """free both slots of the selected envs (None: of every env)"""
+        from . import pushes
+        return pushes.push_host(self, np.ones(self.N, np.int32) if mask is None else mask, -1, np.zeros(3), 0.0, -1)
+
+    def push_state(self):
+        """include/dm_hip.h dm_push_state as a host array: float32 [N, 2, 6] = per slot {link (-1: free), force xyz, duration, elapsed} (columns: deepmimic_amd/pushes.py)"""
+        from . import pushes
+        return pushes.push_state_host(self)
 
     def set_terminal_outputs(self, term_states_ptr: int = 0, term_goals_ptr: int = 0):
         """include/dm_hip.h dm_set_terminal_outputs: bind device buffers (raw pointers: N x S float32, and N x G float32 for a goal scene) that every

@@ -3491,4 +3491,67 @@ __global__ void __launch_bounds__(64) k_env_probe(ModelDev<Real> m, EnvState<Rea
     sim.store(st, e);
 }
 
+// ---- task-chosen pushes (include/dm_hip.h dm_push_where / dm_push_state; the rows: PT_* of dm_types.h, applied by pert_tick / pert_gen_force above)
+// One lane per env (grid ceil(N / 64)), no EnvSim, no LDS, no atomics: a lane touches only its own env's perturbation row and reads the root quaternion of its
+// pose row, so the kernel is the same for every class, packing and physics version -- one instantiation per precision (the heading is computed in Real).
+// For every env with mask[e] != 0: force forces[e] on body part links[e] for durs[e] seconds, written into a slot exactly as pert_tick writes a drawn one,
+// {part + 1, f, dur, 0}: it acts from the first scene update of the next launch, for whole updates while elapsed < duration.  slots[e] 0 / 1 names the slot; -1 or a
+// null array picks it by pert_tick's rule for a drawn force, RESTATED here (calling one function from both places would have to leave all the step-kernel objects
+// byte for byte as they are): a free slot, lowest index first, else the slot nearest its end (the largest elapsed - duration).  links[e] == -1 frees the named slot, or
+// both for slot -1.  PS_HEADING: the force is given in the character's heading frame and stored as rot_y(calc_heading(root rotation)) * f, computed in Real at the
+// time of the call (the frame of LS_ENV's heading column); otherwise the doubles are stored as given.  PT_TIMER, PT_NEXT, PT_DRAWS and PT_KSEED are not touched and no
+// draw is made.  An env with a link outside [-1, J), a non-finite force component, a negative or NaN duration or a slot outside [-1, PT_SLOTS) keeps every byte and
+// its lane stores 1 to bad[0] (null: not wanted; a plain store of the same value from any lane, the convention of k_env_reset_where_at); no table is indexed with
+// such a value.
+template <typename Real>
+__global__ void __launch_bounds__(64) k_push_where(int N, int J, int P, const Real* pose, double* pert, const int* mask, const int* links, const double* forces, const double* durs,
+                                                   const int* slots, int flags, int* bad) {
+    const int e = blockIdx.x * kWave + threadIdx.x;
+    if (e >= N || mask[e] == 0) return;
+    const int lk = links[e], sl = slots ? slots[e] : -1;
+    const double fx = forces[(size_t)e * 3], fy = forces[(size_t)e * 3 + 1], fz = forces[(size_t)e * 3 + 2], dur = durs[e];
+    if (lk < -1 || lk >= J || sl < -1 || sl >= PT_SLOTS || !(fx - fx == 0.0 && fy - fy == 0.0 && fz - fz == 0.0) || !(dur >= 0.0)) {
+        if (bad) bad[0] = 1;
+        return;
+    }
+    double* p = pert + (size_t)e * PT_WIDTH;
+    if (lk < 0) {
+        for (int i = 0; i < PT_SLOTS; ++i) if (sl < 0 || sl == i) p[PT_SLOT0 + i * PT_SLOT_W + PT_LINK] = 0;
+        return;
+    }
+    int slot = sl;
+    if (slot < 0) {                                     // (pert_tick's choice for a drawn force)
+        slot = 0; double best = -1e300;
+        for (int i = 0; i < PT_SLOTS; ++i) {
+            const double* ps = p + PT_SLOT0 + i * PT_SLOT_W;
+            const double key = (ps[PT_LINK] == 0.0) ? 1e300 : ps[PT_TIME] - ps[PT_DUR];
+            if (key > best) { best = key; slot = i; }
+        }
+    }
+    double wx = fx, wy = fy, wz = fz;
+    if (flags & PS_HEADING) {
+        const V3<Real> w = rot_y(calc_heading(ldq(pose + (size_t)e * P + 3))) * mk3((Real)fx, (Real)fy, (Real)fz);
+        wx = (double)w.x; wy = (double)w.y; wz = (double)w.z;
+    }
+    double* ps = p + PT_SLOT0 + slot * PT_SLOT_W;
+    ps[PT_LINK] = (double)(lk + 1); ps[PT_FX] = wx; ps[PT_FY] = wy; ps[PT_FZ] = wz; ps[PT_DUR] = dur; ps[PT_TIME] = 0;
+}
+
+// The forces that are acting, float32 whatever the precision: out [N][PT_SLOTS][PS_W] = {link (-1: a free slot, whose other columns are 0), force (3), duration,
+// elapsed}.  One lane per env as k_push_where.  An expired force leaves its slot at the next scene update (pert_tick): until then it is shown with elapsed >= duration.
+// (A template so that only the object of the reset / query / probe family holds it; the rows are doubles in either precision.)
+template <typename Real>
+__global__ void __launch_bounds__(64) k_push_state(int N, const double* pert, float* out) {
+    const int e = blockIdx.x * kWave + threadIdx.x;
+    if (e >= N) return;
+    for (int i = 0; i < PT_SLOTS; ++i) {
+        const double* ps = pert + (size_t)e * PT_WIDTH + PT_SLOT0 + i * PT_SLOT_W;
+        float* o = out + ((size_t)e * PT_SLOTS + i) * PS_W;
+        const bool on = ps[PT_LINK] > 0.0;
+        o[PS_LINK] = on ? (float)(ps[PT_LINK] - 1.0) : -1.0f;
+        o[PS_FX] = on ? (float)ps[PT_FX] : 0.0f; o[PS_FY] = on ? (float)ps[PT_FY] : 0.0f; o[PS_FZ] = on ? (float)ps[PT_FZ] : 0.0f;
+        o[PS_DUR] = on ? (float)ps[PT_DUR] : 0.0f; o[PS_TIME] = on ? (float)ps[PT_TIME] : 0.0f;
+    }
+}
+
 }  // namespace dmk

@@ -404,6 +404,9 @@ struct CtxBase {
     virtual dmk::StatePoolLayout state_pool_layout() const = 0;      // dm_state_pool.h
     virtual int state_save(void* pool_dev, int slots, const int* mask_dev, const int* slots_dev, int* bad_dev) = 0;
     virtual int state_restore(const void* pool_dev, int slots, const int* mask_dev, const int* slots_dev, int flags, float* states_dev, float* goals_dev, int* bad_dev) = 0;
+    virtual int push_where(const int* mask_dev, const int* links_dev, const double* forces_dev, const double* durations_dev, const int* slots_dev, int flags, int* bad_dev) = 0;      // dm_push.h
+    virtual int push_state(float* out_dev) = 0;
+    virtual bool has_pert() const = 0;
     virtual bool has_obj() const = 0; virtual bool has_tape() const = 0;
     virtual int probe(int what, double dt) = 0;
     virtual int get_state(double* pose, double* vel, double* tar, double* kin, double* clk, int* flg) = 0;
@@ -579,7 +582,8 @@ struct CtxT : CtxBase {
             if (!st.goal || !d_goals) return fail("device allocation failed");
             rt_memset(st.goal, 0, sizeof(double) * (size_t)N * GS_WIDTH, stream);      // (GS_KON = 0: the ctx's own draw key; every other slot is written by the first reset)
         }
-        // random perturbations (scenes/SceneSimChar.cpp:92-99)
+        // random perturbations (scenes/SceneSimChar.cpp:92-99).  perturb_time_min = perturb_time_max = +inf passes the checks below: the rows exist and nothing
+        // fires by itself (pert_uniform hands back the infinite bound, pert_tick's `t >= PT_NEXT` never holds) -- the rows then serve dm_push_where alone
         st.pert = nullptr; md.perturb_on = c.enable_rand_perturbs ? 1 : 0;
         if (c.enable_rand_perturbs) {
             md.perturb_time_min = c.perturb_time_min; md.perturb_time_max = c.perturb_time_max; md.perturb_min = c.min_perturb; md.perturb_max = c.max_perturb;
@@ -727,6 +731,12 @@ struct CtxT : CtxBase {
         launch_table<Real>().state_restore[cls](N, stream, md, st, state_pool_layout(), (const unsigned char*)pool_dev, slots, mask_dev, slots_dev, flags, states_dev, d_goals, goals_dev, bad_dev);
         return 0;
     }
+    int push_where(const int* mask_dev, const int* links_dev, const double* forces_dev, const double* durations_dev, const int* slots_dev, int flags, int* bad_dev) override {
+        dmk::launch_push_where<Real>(stream, md, st, mask_dev, links_dev, forces_dev, durations_dev, slots_dev, flags, bad_dev);
+        return 0;
+    }
+    int push_state(float* out_dev) override { dmk::launch_push_state<Real>(stream, st, out_dev); return 0; }
+    bool has_pert() const override { return st.pert != nullptr; }
     bool has_obj() const override { return st.obj != nullptr; }
     bool has_tape() const override { return md.draw_tape != nullptr; }
     int clips(int* out, const int* in) override {                     // N: GS_CLIP, the clip the env was reset to
@@ -1522,6 +1532,7 @@ int dm_gather_wait(dm_ctx* ctx, dm_comm* c, int slot) {
 #include "dm_link_state.h"   // link states as device tensors and the reset selected by a device mask: the entry points of k_link_state / k_env_reset_where
 #include "dm_kin_query.h"    // the kinematic character at caller-given times and a masked reset at a caller-given start: the entry points of k_kin_query / k_env_reset_where_at
 #include "dm_state_pool.h"   // a pool of whole env records in device memory: the entry points of k_state_save / k_state_restore
+#include "dm_push.h"         // task-chosen pushes from device tensors and the forces that are acting: the entry points of k_push_where / k_push_state
 #include "dm_time_warp.h"    // the test-mode time-warp return of `--scene imitate_amp`: the sampler's entry point and the alignment kernel
 #include "dm_math_probe.h"    // test support: one helper of dm_math.h per launch, on rows of the caller's inputs
 

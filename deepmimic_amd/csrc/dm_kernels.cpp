@@ -72,6 +72,14 @@ template <typename Real, typename C>
 void launch_state_restore(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, const unsigned char* pool, int M, const int* mask, const int* slots, int flags, float* states, float* goals_own, float* goals, int* bad) {
     RT_LAUNCH((k_state_restore<Real, C>), grid, s, m, st, lay, pool, M, mask, slots, flags, states, goals_own, goals, bad);
 }
+template <typename Real>
+void launch_push_where(rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, const int* links, const double* forces, const double* durs, const int* slots, int flags, int* bad) {
+    RT_LAUNCH((k_push_where<Real>), (st.N + kWave - 1) / kWave, s, st.N, m.J, m.P, (const Real*)st.pose, st.pert, mask, links, forces, durs, slots, flags, bad);
+}
+template <typename Real>
+void launch_push_state(rt_stream s, const EnvState<Real>& st, float* out) {
+    RT_LAUNCH((k_push_state<Real>), (st.N + kWave - 1) / kWave, s, st.N, (const double*)st.pert, out);
+}
 
 // this object's family (dm_families.h): the reset / query / probe family expands its class lists, any other id instantiates the launcher of its row
 #if DM_TU_F64
@@ -97,6 +105,8 @@ typedef float TuReal;
 DM_MISC_CLASSES(DM_INST_MISC)
 DM_EXPERT_CLASSES(DM_INST_EXPERT)
 template void launch_wave_probe<TuReal>(unsigned, rt_stream, int, int, const double*, double*);
+template void launch_push_where<TuReal>(rt_stream, const ModelDev<TuReal>&, const EnvState<TuReal>&, const int*, const int*, const double*, const double*, const int*, int, int*);
+template void launch_push_state<TuReal>(rt_stream, const EnvState<TuReal>&, float*);
 #else
 template void launch_step_family<TuReal, DM_TU_ID>(DM_STEP_ARGS);
 #endif

@@ -46,6 +46,11 @@ template <typename Real, typename C>
 void launch_state_save(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, unsigned char* pool, int M, const int* mask, const int* slots, int* bad);
 template <typename Real, typename C>
 void launch_state_restore(unsigned grid, rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const StatePoolLayout& lay, const unsigned char* pool, int M, const int* mask, const int* slots, int flags, float* states, float* goals_own, float* goals, int* bad);
+// task-chosen pushes (k_push_where / k_push_state, in the object of DM_MISC_FAMILY): one lane per env, one instantiation per precision
+template <typename Real>
+void launch_push_where(rt_stream s, const ModelDev<Real>& m, const EnvState<Real>& st, const int* mask, const int* links, const double* forces, const double* durs, const int* slots, int flags, int* bad);
+template <typename Real>
+void launch_push_state(rt_stream s, const EnvState<Real>& st, float* out);
 // test support (dm_wave_probe.h, in the object of DM_MISC_FAMILY): one wave-level primitive of dm_device.h / dm_device_duo.h per launch, `grid` wavefronts
 template <typename Real>
 void launch_wave_probe(unsigned grid, rt_stream s, int op, int arg, const double* in, double* out);

@@ -268,6 +268,10 @@ enum { PT_TIMER = 0, PT_NEXT, PT_DRAWS, PT_SLOT0, PT_LINK = 0, PT_FX, PT_FY, PT_
 enum { OB_PX = 0, OB_QW = 3, OB_VX = 7, OB_WX = 10, OB_WIDTH = 16 };
 // row widths of dm_link_state's float32 outputs (k_link_state, dm_device.h): per link, per env, the free body
 enum { LS_LINK_W = 22, LS_ENV_W = 8, LS_OBJ_W = 13 };
+// columns of dm_push_state's float32 rows [N][PT_SLOTS][PS_W] (k_push_state, dm_device.h): link (-1: free), force, duration, elapsed; flags of dm_push_where
+// (k_push_where; DM_PUSH_* of include/dm_hip.h)
+enum { PS_LINK = 0, PS_FX, PS_FY, PS_FZ, PS_DUR, PS_TIME, PS_W = 6 };
+enum { PS_WORLD = 0, PS_HEADING = 1, PS_ALL_FLAGS = 1 };
 // flags of dm_kin_query (k_kin_query, dm_device.h; DM_KIN_* of include/dm_hip.h) and its largest number of times per env
 enum { KQ_TIMES_PER_ENV = 1, KQ_TIMES_ABSOLUTE = 2, KQ_ORIGIN_IDENTITY = 4, KQ_ALL_FLAGS = 7, KQ_MAX_K = 64 };
 
@@ -285,7 +289,7 @@ struct EnvState {
     Real* hist;      // N x 2P  pose | vel at the last action latch (cSceneImitateAMP::mPrevPose / mPrevVel); null unless imitate_amp
     Real* obj;       // N x OB_WIDTH  the free body of an OBJ class (dribble_amp's ball); null otherwise
     double* goal;    // N x GS_WIDTH  goal state of the task scenes + the clip the env was reset to; null unless a goal scene / multi-clip dataset
-    double* pert;    // N x PT_WIDTH  random-perturbation clock and active forces; null unless enable_rand_perturbs
+    double* pert;    // N x PT_WIDTH  random-perturbation clock and active forces (drawn ones and dm_push_where's); null unless enable_rand_perturbs
     Real* manif;     // N x J x MF_STRIDE  physics 2: per link [count, 4 x (point on the link in body coordinates (3), point on the plane x, z, distance)]; null otherwise
 };
 enum { MF_STRIDE = 32, MF_PT = 6 };

@@ -7,4 +7,4 @@ $(error no family ids found in $(FAMILIES_H))
 endif
 KOBJS := $(foreach i,$(KIDS),$(OBJDIR)/k_f32_$(i).o $(OBJDIR)/k_f64_$(i).o)
 # HOST_HDRS: the headers dm_host.cpp includes besides HDRS, relative to this directory; both dm_host.o rules depend on every one (tests/test_build_rules.py)
-HOST_HDRS := dm_policy.h dm_policy_host.h dm_scene_load.h dm_norm.h dm_returns.h dm_ppo_batch.h dm_replay.h dm_episode.h dm_amp_rewards.h dm_math_probe.h dm_time_warp.h dm_link_state.h dm_kin_query.h dm_state_pool.h dm_train.h dm_train_gated.h dm_optim.h
+HOST_HDRS := dm_policy.h dm_policy_host.h dm_scene_load.h dm_norm.h dm_returns.h dm_ppo_batch.h dm_replay.h dm_episode.h dm_amp_rewards.h dm_math_probe.h dm_time_warp.h dm_link_state.h dm_kin_query.h dm_state_pool.h dm_push.h dm_train.h dm_train_gated.h dm_optim.h

@@ -199,6 +199,9 @@ class SceneConfig:
     min_pertrub_duration: float = 0.1
     max_perturb_duration: float = 0.5
     perturb_part_ids: Optional[List[int]] = None
+    # task-chosen pushes (deepmimic_amd/pushes.py): the context carries the perturbation rows whether or not the random schedule runs -- with enable_rand_perturbs off
+    # (or its default infinite interval) nothing fires by itself and the rows serve BatchEnv.push / TorchVecEnv.push alone; not an arg-file key
+    task_pushes: bool = False
 
 
 # cSceneDribbleAMP::BuildTarObjs (SceneDribbleAMP.cpp:398-420): the ball's constants are literals there, not arg-file keys

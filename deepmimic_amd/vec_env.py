@@ -9,6 +9,7 @@ own streams, below) is the faster form of the same thing: +2 ... 15 % depending 
 `--timer_type exp` scenes are served like the uniform timer since round 4: the in-kernel auto-reset draws min(min + Exp, max) (util/Timer.cpp:64-67)."""
 from __future__ import annotations
 
+import copy
 from typing import Dict, Tuple
 
 from .binding import stream_handle, tensor_arg
@@ -16,6 +17,7 @@ from .core import BatchEnv
 from .episodes import EpisodeStats, decode_block, merge_blocks
 from .kin_query import KinQuery, reset_where_at_device
 from .link_state import KIN, SIM, LinkState, reset_where_device
+from . import pushes as pu
 from . import state_pool as sp
 from .model import SceneTables
 from .time_warp import TimeWarp, buffer_size, why_no_warper
@@ -42,7 +44,7 @@ class TorchVecEnv:
     def __init__(self, tables: SceneTables, num_envs: int, device: str = "cuda:0", seed: int = 0, timestep: float = 1.0 / 600,
                  updates_per_step: int = 20, amp_obs: bool = False, terminal_obs: bool = True, episode_stats: bool = False, episode_bins: int = 0,
                  episode_bin_steps: int = 1, time_warp: bool = False, link_state: bool = False, kin_link_state: bool = False, deferred_reset: bool = False,
-                 kin_lookahead=(), **env_kwargs):
+                 kin_lookahead=(), pushes: bool = False, **env_kwargs):
         """terminal_obs (default on): keep `terminal_obs` / `terminal_goal` tensors bound to the context (BatchEnv.set_terminal_outputs), handed out as
         info["terminal_obs"] / info["terminal_goal"] by `step`; off: the launches write nothing extra and the two keys are absent.
         episode_stats (default off: no extra launch, no extra key): `step` runs deepmimic_amd.episodes.EpisodeStats.update behind the step launch on the same
@@ -71,8 +73,17 @@ class TorchVecEnv:
         state is refreshed -- in `step` and in `update_link_state()` -- dm_kin_query samples the kinematic character at clock + o_k and hands out
         info["kin_ahead_link_state"] [N, K, J, 22], info["kin_ahead_link_env"] [N, K, 8], info["kin_ahead_pose"] / info["kin_ahead_vel"] [N, K, P]: the target
         frames a tracking policy is fed (deepmimic_amd/kin_query.py).  `kin_query()` asks for other times, clips or the clip's own frame; `set_start_sampler()`
-        lets the task choose where new episodes start; `state_pool()` keeps whole env states on the device to rewind to or to start episodes from."""
+        lets the task choose where new episodes start; `state_pool()` keeps whole env states on the device to rewind to or to start episodes from.
+        pushes (default off: no extra launch, no extra key, the context as before): the task places forces on body parts (deepmimic_amd/pushes.py).  The env works
+        on its own copy of the scene config with `task_pushes` set, so the context carries the perturbation rows; `push()` / `clear_pushes()` write them from
+        device tensors, and `reset` and `step` refresh `pushes`, float32 [N, 2, 6] = per slot {link (-1: free), force xyz, duration, elapsed}, handed out as
+        info["pushes"]: one dm_push_state launch.  With deferred_reset it is taken before the reset, like the link states: a finished env shows what was acting
+        when its episode ended (the reset then clears its slots)."""
         import torch
+        if pushes:
+            tables = copy.copy(tables)
+            tables.cfg = copy.copy(tables.cfg)
+            tables.cfg.task_pushes = True
         self.torch = torch
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -121,6 +132,10 @@ class TorchVecEnv:
         self.start_bad = None                                       # int32 [1], set_start_sampler: becomes 1 when a sampler handed in an invalid start
         self._pool = None                                           # state_pool(): the pool a start sampler's "slots" index
         self._pool_mask = None
+        self.has_pushes = bool(self.env.has_pushes)                 # pushes=True, or a scene with a finite random schedule: push() / clear_pushes() work
+        self.pushes = torch.zeros((self.n, pu.PUSH_SLOTS, pu.PUSH_W), **f32) if pushes else None
+        self.push_bad = torch.zeros(1, **i32) if self.has_pushes else None      # int32 [1]: becomes 1 when a push() named an invalid value (read by check=True)
+        self._push_all = None
 
     def _enter(self):
         h = stream_handle(self.device)
@@ -140,6 +155,8 @@ class TorchVecEnv:
         self._enter()
         self.env.reset()
         self._launch(0, 0, False)                                   # RecordState of the reset state, no update
+        if self.pushes is not None:
+            pu.push_state_device(self.env, self.pushes.data_ptr())
         self._leave()
         if self.stats is not None:
             self.stats.reset_carry()                                # episodes in flight are dropped, not counted
@@ -177,6 +194,9 @@ class TorchVecEnv:
                 info["terminal_goal"] = self.terminal_goal
         done = (self.episode_end != 0) | (self.valid == 0)
         self._link_info(info)                                       # (auto-reset: done envs are in their new episode; deferred: every env at the end of the step)
+        if self.pushes is not None:
+            pu.push_state_device(self.env, self.pushes.data_ptr())
+            info["pushes"] = self.pushes
         if self.deferred_reset:
             # what the auto-reset launch does behind its outputs, as launches of their own: the rows of the moment the episode ended go to terminal_obs /
             # terminal_goal (other rows keep their bytes), then the done envs start their next episode and obs / goal get its first rows
@@ -289,6 +309,50 @@ class TorchVecEnv:
         pool made last is the one a start sampler's "slots" index (set_start_sampler)."""
         self._pool = _EnvStatePool(self, slots)
         return self._pool
+
+    def push(self, mask, links, forces, durations, slots=None, frame: str = "world", check: bool = True):
+        """place task-chosen forces (deepmimic_amd/pushes.py; include/dm_hip.h dm_push_where), on torch's current stream: for every env with mask[i] != 0 (int32 or
+        bool [N]) the force forces[i] (float32 or float64 [N, 3], newtons) acts on body part links[i] (int32 [N], a row of `link_names`; -1 clears) for
+        durations[i] seconds (float32 or float64 [N]; +inf: until the episode's reset) from the first scene update of the next `step` on.  slots: int32 [N], 0 / 1,
+        or -1 / None for a free slot, else the one nearest its end.  frame "world", or "heading": the force is given in the character's heading frame (x forward)
+        and keeps the world direction it has at the time of the call.  The tensors are converted on the device.  check (default on): one host read of the
+        kernel's bad word, a ValueError when some selected env had an invalid value -- a link outside [-1, J), a non-finite force, a negative or NaN duration, a
+        slot outside [-1, 2); that env kept every byte, the others were served.  check=False reads nothing (`push_bad` keeps the word)."""
+        t = self.torch
+        if not self.has_pushes:
+            raise ValueError("this env has no perturbation rows: build it with TorchVecEnv(..., pushes=True)")
+        flags = pu.frame_flag(frame)
+        if isinstance(mask, t.Tensor) and mask.dtype == t.bool:
+            mask = mask.to(t.int32)
+        tensor_arg("mask", mask, self.device, t.int32, [(self.n,)])
+        tensor_arg("links", links, self.device, t.int32, [(self.n,)])
+        if slots is not None:
+            tensor_arg("slots", slots, self.device, t.int32, [(self.n,)])
+        for name, x, shape in (("forces", forces, (self.n, 3)), ("durations", durations, (self.n,))):
+            if not isinstance(x, t.Tensor) or x.device != self.device or x.dtype not in (t.float32, t.float64) or tuple(x.shape) != shape:
+                raise ValueError("%s must be a float32 or float64 tensor of shape %s on %s" % (name, shape, self.device))
+        forces, durations = forces.to(t.float64).contiguous(), durations.to(t.float64).contiguous()
+        self._enter()
+        if check:
+            self.push_bad.zero_()
+        pu.push_where_device(self.env, mask.data_ptr(), links.data_ptr(), forces.data_ptr(), durations.data_ptr(), slots.data_ptr() if slots is not None else 0,
+                             flags, self.push_bad.data_ptr())
+        self._leave()
+        if check and int(self.push_bad.item()):
+            raise ValueError("push: an env had an invalid value (a link outside [-1, %d), a non-finite force, a negative or NaN duration, or a slot outside [-1, 2)); "
+                             "it kept its pushes, the other envs were served" % self.env.J)
+
+    def clear_pushes(self, mask=None):
+        """free both push slots of the envs with mask[i] != 0 (int32 or bool [N]; None: of every env), on torch's current stream, no host read"""
+        t = self.torch
+        if not self.has_pushes:
+            raise ValueError("this env has no perturbation rows: build it with TorchVecEnv(..., pushes=True)")
+        if self._push_all is None:
+            i32 = dict(dtype=t.int32, device=self.device)
+            self._push_all = (t.ones(self.n, **i32), t.full((self.n,), -1, **i32), t.zeros((self.n, 3), dtype=t.float64, device=self.device),
+                              t.zeros(self.n, dtype=t.float64, device=self.device))
+        ones, minus, f0, d0 = self._push_all
+        self.push(ones if mask is None else mask, minus, f0, d0, slots=minus, check=False)
 
     def episode_totals(self) -> dict:
         """figures of the episodes finished since construction or the last `stats.clear_totals()` (episodes.decode_block): one device-to-host copy"""

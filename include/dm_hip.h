@@ -106,7 +106,10 @@ typedef struct {
      * sim/PerturbManager.cpp; sim/World.cpp:93-96): every U[perturb_time_min, perturb_time_max] seconds a force of U[min_perturb,
      * max_perturb] N in a uniformly drawn direction acts at the centre of mass of a random body part for U[min, max duration] seconds
      * (`min_pertrub_duration` [sic] / `max_perturb_duration`).  perturb_part_mask: bit j = part j may be hit (--perturb_part_ids), 0 = any.
-     * Cleared and re-armed by every scene reset.  Needs 2 * perturb_time_min >= max_perturb_duration (two forces at once at most). */
+     * Cleared and re-armed by every scene reset.  Needs 2 * perturb_time_min >= max_perturb_duration (two forces at once at most).
+     * perturb_time_min = perturb_time_max = +infinity is accepted and means "the rows exist, nothing fires by itself": the context carries the per-env
+     * perturbation rows and runs the kernels that apply them, every reset makes its one draw, and no force is ever drawn -- the rows then serve dm_push_where
+     * alone (the other ranges may be 0). */
     int enable_rand_perturbs;
     double perturb_time_min, perturb_time_max, min_perturb, max_perturb, min_perturb_duration, max_perturb_duration;
     int perturb_part_mask;
@@ -867,6 +870,33 @@ int dm_state_pool_dims(const dm_ctx* ctx, int32_t* out /* [13] */);
 int dm_state_save(dm_ctx* ctx, void* pool_dev, int slots, const int32_t* mask_dev, const int32_t* slots_dev, int32_t* bad_dev /* NULL */);
 int dm_state_restore(dm_ctx* ctx, const void* pool_dev, int slots, const int32_t* mask_dev, const int32_t* slots_dev, int flags, float* states_dev /* NULL */,
                      float* goals_dev /* NULL */, int32_t* bad_dev /* NULL */);
+
+/* ---- Task-chosen pushes: place forces on body parts from device tensors, and read out the forces that are acting (deepmimic_amd/csrc/dm_push.h, k_push_where and
+ * k_push_state of dm_device.h, deepmimic_amd/pushes.py).  The forces live in the two slots of the env's perturbation row (dm_get_perturb_state) and are applied by the
+ * step kernels exactly as a drawn perturbation is: at the body part's centre of mass, for whole scene updates.  The ctx needs the rows: enable_rand_perturbs, where
+ * an infinite interval gives rows without the random schedule (dm_scene_tables).  With the random schedule on, both share the two slots.  Every pointer but the ctx
+ * is a device pointer; both calls are asynchronous on the ctx's stream, read nothing back and synchronise nothing; a refused call launches nothing and names its
+ * reason through dm_last_error.
+ *
+ * dm_push_where: for every env with mask_dev[i] != 0, the force forces_dev[i] (N x 3 doubles, newtons) acts on body part links_dev[i] for durations_dev[i]
+ * seconds: from the first scene update of the next launch, for whole updates while elapsed < duration -- ceil(duration / dt) updates, across control steps; a zero
+ * duration never acts, +infinity lasts until the episode's reset clears it (every scene reset clears both slots; dm_state_restore brings the forces stored in a
+ * slot of the pool).  slots_dev[i] 0 or 1 names the slot of the row; -1, or a NULL array, takes the rule of a drawn force: a free slot, lowest index first, else
+ * the slot nearest its end (the largest elapsed - duration), whose force is replaced.  links_dev[i] == -1 frees the named slot, or both for slot -1.
+ * flags: DM_PUSH_WORLD, the force is in world coordinates and stored as given; DM_PUSH_HEADING, it is given in the character's heading frame (x forward, y up,
+ * the frame of dm_link_state's heading column) and stored as rot_y(heading of the root rotation) * f, computed in the ctx's precision at the time of the call:
+ * a fixed world direction afterwards.  The row's clock, next time, draw counter and draw key are not touched and no draw is made.  Two calls with the same
+ * arguments leave the same bytes.
+ * A selected env with a link outside [-1, num_joints), a non-finite force component, a negative or NaN duration, or a slot outside [-1, 2) keeps every byte, and
+ * the kernel stores 1 to bad_dev[0] (int32, may be NULL; the caller zeroes it before the call); the other envs of the call are served.
+ * Refused: a NULL ctx, mask_dev, links_dev, forces_dev or durations_dev; unknown flag bits; a ctx without perturbation rows.
+ *
+ * dm_push_state: out_dev [N][2][6] float32 whatever the precision: per slot {link (-1: free, the other columns are 0 then), fx, fy, fz, duration, elapsed}.  A
+ * force whose time is up leaves its slot at the next scene update. */
+enum { DM_PUSH_WORLD = 0, DM_PUSH_HEADING = 1 };
+int dm_push_where(dm_ctx* ctx, const int32_t* mask_dev, const int32_t* links_dev, const double* forces_dev /* [N][3] */, const double* durations_dev,
+                  const int32_t* slots_dev /* NULL */, int flags, int32_t* bad_dev /* NULL */);
+int dm_push_state(dm_ctx* ctx, float* out_dev /* [N][2][6] */);
 
 /* ---- PPO actor and critic minibatch updates on the device (deepmimic_amd/csrc/dm_train.h, deepmimic_amd/train.py): PPOAgent._update_actor / _update_critic and
  * MPISolver.update (learning/ppo_agent.py:95-139, 286-309, learning/solvers/mpi_solver.py:33-54) for the plain three-layer nets, on the context that samples, so that
